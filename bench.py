@@ -23,7 +23,19 @@ always says which configuration ran.
 
 Prints ONE JSON line on rank 0.  `roofline` prices the fused rollout kernel against HBM
 (algorithmic bytes per env-step = act 4 + obs 96 + reward 4 + flags 2 + 2*state/H, SURVEY.md
-§8d); `cpu_baseline` times the CPU oracle (oracle/salp_oracle.c) on the host cores.
+§8d) from the events around the timed launches.
+
+A plain run sets up, warms up, times the K launches and prints the line.  `--full` adds the
+measurements that take runs of their own, after the timed region: `secondary_kernels` (the 12-,
+16- and 5-food kernels), `step_per_launch`, `sac_first_capture` (BASELINE configs[4]) and
+`cpu_baseline` (the CPU oracle, oracle/salp_oracle.c, on the host cores).
+
+`--dump-outputs DIR` writes what the last timed launch returned, for a fixed seeded sample of
+k = DUMP_ENVS envs (rank 0's shard at --gpus G > 1), as float32 .npy files: obs [chunk, k, obs_dim],
+reward, terminated, truncated [chunk, k] (and actions when --actions generated), with the sampled
+env indices in env_index.npy (float64).  A chunk too long for DUMP_BYTES in all gets fewer envs
+(and one too long for a single env, only its last steps).  The inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -213,6 +225,31 @@ def step_mode(device, envs: int, preset: str, iters: int = 200, warmup: int = 20
         return {"preset": preset, "envs": envs, "error": f"{type(e).__name__}: {e}"}
 
 
+DUMP_ENVS = 2048             # --dump-outputs: at most this many envs sampled (~55 MB at the default chunk) ...
+DUMP_BYTES = 60 << 20        # ... and fewer envs, then only the last steps, where a long chunk would go past this
+
+
+def dump_outputs(out_dir: str, res: dict, n: int, generated_actions: bool) -> list:
+    """Writes the sampled outputs of one rollout (torch tensors [H, n, ...], see the module docstring); returns the
+    file names."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    names = ["obs", "reward", "terminated", "truncated"] + (["actions"] if generated_actions else [])
+    H = int(res["obs"].shape[0])
+    step_bytes = 4 * sum(int(np.prod(res[name].shape[2:])) for name in names)      # float32 values per env and step
+    k = max(1, min(n, DUMP_ENVS, DUMP_BYTES // (H * step_bytes + 8)))
+    h0 = max(0, H - (DUMP_BYTES - 8 * k) // (k * step_bytes))                      # > 0 only if one env's H steps do not fit
+    idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+    files = ["env_index.npy"]
+    np.save(os.path.join(out_dir, "env_index.npy"), idx.astype(np.float64))
+    for name in names:
+        a = res[name][h0:].index_select(1, torch.from_numpy(idx).to(res[name].device)).to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        files.append(f"{name}.npy")
+    return files
+
+
 CONFIG2_ENVS = 262144        # BASELINE configs[2]: one GPU
 CONFIG3_TOTAL_ENVS = 1048576  # BASELINE configs[3]: sharded over the GPUs of one node
 
@@ -254,6 +291,11 @@ def main():
     ap.add_argument("--actions", default="hbm", choices=["hbm", "generated"],
                     help="hbm: a random action block resident in HBM, read by the kernel; generated: the kernel draws the "
                          "actions from each env's Philox action stream and writes them out (same 4 B per env-step)")
+    ap.add_argument("--full", action="store_true", help="after the headline also run the extras below (secondary kernels, "
+                    "step-per-launch, SAC first-capture probe, CPU baseline); the --no-* / --sac-probe / --probe-seconds / "
+                    "--cpu-seconds options shape them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of what the last timed launch returned to DIR/<name>.npy (rank 0)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sac-probe", action="store_true", help="skip the configs[4] first-food-capture probe")
@@ -327,6 +369,7 @@ def main():
     # --gather all: two output blocks, so that the collective of launch k (which reads block k % 2) runs beside
     # launch k + 1 (which writes the other one); a block is only rewritten after its collective has completed
     outs, works = [None, None], [None, None]
+    last = [None]      # what the latest launch returned (--dump-outputs)
     gather_steps = max(1, min(H, int((2 << 30) // max(1, n * cfg.obs_dim * 4))))   # steps per all-gather piece (<= ~2 GB per rank)
     if senv is not None and gather == "all":
         assert senv.env_index_base == plan["env_index_base"](rank) and senv.local_envs == n
@@ -344,7 +387,7 @@ def main():
                 works[b] = None
             st = torch.cuda.Event(enable_timing=True)
             st.record()                      # after the wait for this block's previous collective: the kernel alone
-            out = senv.engine.rollout(act, out=outs[b], **rkw)
+            out = last[0] = senv.engine.rollout(act, out=outs[b], **rkw)
             ev = torch.cuda.Event(enable_timing=True)
             ev.record()
             # the block goes out in pieces of at most ~2 GB per rank (whole steps): one collective of 12.6 GB per rank
@@ -357,7 +400,7 @@ def main():
             return st, ev
         st = torch.cuda.Event(enable_timing=True)
         st.record()
-        out = senv.engine.rollout(act, **rkw)
+        out = last[0] = senv.engine.rollout(act, **rkw)
         ev = torch.cuda.Event(enable_timing=True)
         ev.record()
         if gather == "final":   # staged + double-buffered: the next launch starts at once, the collective runs beside it
@@ -393,7 +436,7 @@ def main():
             starts[k], ends[k] = sharded_launch(k)
         else:
             starts[k].record()
-            env.rollout(act, **rkw)
+            last[0] = env.rollout(act, **rkw)
             ends[k] = torch.cuda.Event(enable_timing=True)
             ends[k].record()
     drain()
@@ -412,6 +455,9 @@ def main():
 
     stats = env.stats()
     assert stats["env_steps"] == n * H * K, (stats["env_steps"], n * H * K)  # nothing skipped in the timed region
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[0], n, generated_actions=act is None)
+    last[0] = None      # no reference left to the output block: --full gives it back before its extras
 
     total_env_steps = float(world) * n * H * K
     value = total_env_steps / elapsed
@@ -516,36 +562,37 @@ def main():
                          "note": "wall time per rank from launch to drained exchange, max over ranks (no barrier inside)"}
         line["other_exchange_modes"] = alt
 
-    # Extras that run before the one JSON line is printed are bounded by a wall-clock limit: if they hang (a GPU fault
-    # in the probe, a collective that never completes) the watchdog prints the headline as it stands and ends the process.
     emitted = {"done": False}
+    if args.full:
+        # Extras that run before the one JSON line is printed are bounded by a wall-clock limit: if they hang (a GPU fault
+        # in the probe, a collective that never completes) the watchdog prints the headline as it stands and ends the process.
 
-    def emit_and_exit():
-        if rank == 0 and not emitted["done"]:
-            emitted["done"] = True
-            line.setdefault("extras_timed_out", True)
-            print(json.dumps(line), flush=True)
-        os._exit(0)
+        def emit_and_exit():
+            if rank == 0 and not emitted["done"]:
+                emitted["done"] = True
+                line.setdefault("extras_timed_out", True)
+                print(json.dumps(line), flush=True)
+            os._exit(0)
 
-    import threading
-    watchdog = threading.Timer(max(5.0, args.probe_seconds), emit_and_exit)
-    watchdog.daemon = True
-    watchdog.start()
-    if world == 1 and not args.no_secondary and not force_sharded and plan["config"] == 2:
-        if senv is None:       # give the headline's 6.7-GB output block back first
-            env.close()
-            env = None
-            torch.cuda.empty_cache()
-        line["secondary_kernels"] = secondary_kernels(device, n, H)
-        line["step_per_launch"] = [step_mode(device, n, args.preset), step_mode(device, n, "sac_gail"), step_mode(device, 4096, "sac_gail")]
-    if not args.no_sac_probe and not rehearsal and not force_sharded and (world == 1 or args.sac_probe):
-        probe = sac_first_capture(device, world if senv is not None else 1, rank)   # every rank takes part (collectives)
-        line["sac_first_capture"] = probe
-    watchdog.cancel()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        line["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
-    elif rank == 0:
-        line["cpu_baseline"] = None
+        import threading
+        watchdog = threading.Timer(max(5.0, args.probe_seconds), emit_and_exit)
+        watchdog.daemon = True
+        watchdog.start()
+        if world == 1 and not args.no_secondary and not force_sharded and plan["config"] == 2:
+            if senv is None:       # give the headline's 6.7-GB output block back first
+                env.close()
+                env = None
+                torch.cuda.empty_cache()
+            line["secondary_kernels"] = secondary_kernels(device, n, H)
+            line["step_per_launch"] = [step_mode(device, n, args.preset), step_mode(device, n, "sac_gail"), step_mode(device, 4096, "sac_gail")]
+        if not args.no_sac_probe and not rehearsal and not force_sharded and (world == 1 or args.sac_probe):
+            probe = sac_first_capture(device, world if senv is not None else 1, rank)   # every rank takes part (collectives)
+            line["sac_first_capture"] = probe
+        watchdog.cancel()
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            line["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
+        elif rank == 0:
+            line["cpu_baseline"] = None
     if rank == 0 and not emitted["done"]:
         emitted["done"] = True
         print(json.dumps(line), flush=True)

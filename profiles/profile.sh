@@ -17,5 +17,5 @@ pass pmc_sq1 SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES 
 pass pmc_sq2 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT SQ_INSTS_LDS
 pass pmc_sq3 SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_WR SQ_INSTS_SMEM
 pass pmc_grbm GRBM_GUI_ACTIVE
-python3 bench.py --no-sac-probe $@ > $OUT/bench_plain.json 2> $OUT/bench_plain.err
+timeout -k 10 600 python3 bench.py --full --no-sac-probe $@ > $OUT/bench_plain.json 2> $OUT/bench_plain.err
 cat $OUT/bench_plain.json

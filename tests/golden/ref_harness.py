@@ -2,9 +2,9 @@
 
 TEST TOOLING ONLY (never imported by the product, bench.py or any `-m gpu` test;
 /root/reference does not exist on the GPU box).  It is used by
-`tests/golden/gen_golden.py` to emit the committed golden vectors and by the
-`not gpu` test `tests/test_oracle_vs_reference.py`, which skips itself when
-/root/reference is absent.
+`tests/golden/gen_golden.py` and the other generators under tests/golden/ to emit
+the committed golden vectors (tests/test_oracle_vs_reference.py reads those of
+`gen_crosscheck_golden.py`).
 
 What it does:
   * `SalpSnakeEnv` (src/salp/environments/salp_snake_env.py:17) subclasses a parent

@@ -97,6 +97,50 @@ def test_bench_shard_plan_is_baseline_configs_2_and_3():
         bench.shard_plan(2, envs_per_gpu=8, total_envs=16)
 
 
+def test_bench_dump_outputs_is_a_seeded_float32_sample(tmp_path):
+    """bench.py --dump-outputs: the same seeded env sample every run, float32 files, flags as 0 / 1."""
+    import torch
+    import bench
+    H, n, D = 3, 5000, 24
+    g = torch.Generator().manual_seed(0)
+    res = dict(obs=torch.rand((H, n, D), generator=g), reward=torch.rand((H, n), generator=g),
+               terminated=(torch.rand((H, n), generator=g) < 0.1).to(torch.uint8),
+               truncated=(torch.rand((H, n), generator=g) < 0.1).to(torch.uint8), final_obs=None, actions=None)
+    files = bench.dump_outputs(str(tmp_path / "a"), res, n, generated_actions=False)
+    bench.dump_outputs(str(tmp_path / "b"), res, n, generated_actions=False)
+    assert sorted(files) == ["env_index.npy", "obs.npy", "reward.npy", "terminated.npy", "truncated.npy"]
+    idx = np.load(tmp_path / "a" / "env_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == bench.DUMP_ENVS and len(np.unique(idx)) == bench.DUMP_ENVS
+    ii = idx.astype(np.int64)
+    for name in files:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert np.array_equal(a, b) and a.dtype in (np.float32, np.float64), name
+        if name != "env_index.npy":
+            assert a.dtype == np.float32 and np.array_equal(a, res[name[:-4]][:, ii].numpy().astype(np.float32)), name
+    assert bench.DUMP_ENVS * 250 * (D + 3) * 4 <= bench.DUMP_BYTES < 64 * 10**6  # the bench's default chunk: DUMP_ENVS envs
+
+
+def test_bench_dump_outputs_stays_within_its_byte_budget(tmp_path, monkeypatch):
+    """A longer chunk gets fewer envs, one that a single env cannot fit only its last steps: never more than DUMP_BYTES."""
+    import torch
+    import bench
+    H, n, D = 40, 300, 24
+    g = torch.Generator().manual_seed(1)
+    res = dict(obs=torch.rand((H, n, D), generator=g), reward=torch.rand((H, n), generator=g),
+               terminated=torch.zeros((H, n), dtype=torch.uint8), truncated=torch.ones((H, n), dtype=torch.uint8),
+               actions=torch.rand((H, n, 2), generator=g))
+    for budget, envs, steps in ((10**9, 300, H), (100_000, 100_000 // (H * 29 * 4 + 8), H), (2_000, 1, (2_000 - 8) // (29 * 4))):
+        monkeypatch.setattr(bench, "DUMP_BYTES", budget)
+        out = tmp_path / str(budget)
+        files = bench.dump_outputs(str(out), res, n, generated_actions=True)
+        arrays = {f[:-4]: np.load(out / f) for f in files}
+        assert sum(a.nbytes for a in arrays.values()) <= budget
+        ii = arrays["env_index"].astype(np.int64)
+        assert len(ii) == envs and arrays["obs"].shape == (steps, envs, D) and arrays["actions"].shape == (steps, envs, 2)
+        for name in ("obs", "reward", "terminated", "truncated", "actions"):
+            assert np.array_equal(arrays[name], res[name][H - steps:][:, ii].numpy().astype(np.float32)), name
+
+
 def test_adaptive_food_curriculum_follows_the_reference_rule():
     """continuous_trainer.py:375-415: window of 10 episodes, > 0.6 removes a food, < 0.25 adds one, within [2, 12],
     window cleared after a change; the change is the base_num_food_items write."""

@@ -1,13 +1,26 @@
-"""Live cross-check of the CPU oracle against the reference's Python implementation (only where
-/root/reference exists, i.e. the build container): longer randomized runs than the committed vectors."""
+"""Cross-check of the CPU oracle against the reference's Python implementation on longer randomized runs than the
+other committed vectors: the reference's outputs are recorded in tests/golden/crosscheck_*.npz and its
+configs/*.yaml in tests/golden/ref_configs/ (both made by tests/golden/gen_crosscheck_golden.py)."""
+import glob
+import json
+import os
+
 import numpy as np
 import pytest
 
 import oracle_lib as ol
-import ref_harness as rh
 import underwater_swimmer_rl_amd as pkg
 
-pytestmark = pytest.mark.skipif(not rh.reference_available(), reason="/root/reference not present on this machine")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def load_case(preset, over):
+    for path in sorted(glob.glob(os.path.join(GOLDEN, "crosscheck_*.npz"))):
+        z = np.load(path, allow_pickle=False)
+        case = json.loads(str(z["case_json"]))
+        if case["preset"] == preset and case["overrides"] == over:
+            return {k: z[k] for k in z.files}, case
+    raise FileNotFoundError(f"no crosscheck fixture for {preset} {over}")
 
 
 @pytest.mark.parametrize("preset,over", [
@@ -16,31 +29,31 @@ pytestmark = pytest.mark.skipif(not rh.reference_available(), reason="/root/refe
     ("sac_gail", dict(num_food_items=4, random_food_count=True, max_steps_without_food=80)),
 ])
 def test_bit_exact_against_reference(preset, over):
+    z, case = load_case(preset, over)
     cfg = pkg.load_env_config(preset, **over)
     n, T, seed = 3, 2500, 4321
+    assert (case["n"], case["T"], case["seed"]) == (n, T, seed)
     orc = ol.OracleVec(cfg, n, seed=seed)
-    refs = [rh.ReferenceEnv(seed, i, **cfg.env_kwargs()) for i in range(n)]
-    assert np.array_equal(orc.observe(), np.stack([r.reset() for r in refs]))
-    rng = np.random.default_rng(11)
-    act = rng.uniform(-1, 1, size=(T, n, cfg.act_dim)).astype(np.float32)
-    if not cfg.forced_breathing:
-        act[..., 0] = rng.uniform(0, 1, size=(T // 25 + 1, n)).repeat(25, axis=0)[:T]
+    assert np.array_equal(orc.observe(), z["reset_obs"])
+    act = z["actions"]
+    assert act.shape == (T, n, cfg.act_dim)
     out = orc.rollout(act, want_final=True)
+    final = {(int(t), int(i)): k for k, (t, i) in enumerate(z["done_tn"])}
+    ref_term, ref_trunc = z["terminated"].astype(bool), z["truncated"].astype(bool)
+    assert len(final) == int(np.count_nonzero(ref_term | ref_trunc))
     for t in range(T):
-        for i, r in enumerate(refs):
-            o, rew, term, trunc, info = r.step(act[t, i])
-            assert rew == out["reward64"][t, i], (t, i)
-            assert bool(term) == bool(out["terminated"][t, i]) and bool(trunc) == bool(out["truncated"][t, i]), (t, i)
+        for i in range(n):
+            assert z["reward"][t, i] == out["reward64"][t, i], (t, i)
+            term, trunc = ref_term[t, i], ref_trunc[t, i]
+            assert term == bool(out["terminated"][t, i]) and trunc == bool(out["truncated"][t, i]), (t, i)
             if term or trunc:
-                assert np.array_equal(o, out["final_obs"][t, i])
-                o = r.reset()
-            assert np.array_equal(o, out["obs"][t, i]), (t, i)
+                assert np.array_equal(z["final_obs"][final[(t, i)]], out["final_obs"][t, i])
+            assert np.array_equal(z["obs"][t, i], out["obs"][t, i]), (t, i)
 
 
 def test_presets_match_reference_yaml():
     """config.PRESETS restates configs/*.yaml `environment.params`."""
-    import os
     for name in ("single_food", "single_food_long_horizon", "sac_gail", "defaults"):
         a = pkg.load_env_config(name)
-        b = pkg.load_env_config(os.path.join(rh.REFERENCE_ROOT, "configs", f"{name}.yaml"))
+        b = pkg.load_env_config(os.path.join(GOLDEN, "ref_configs", f"{name}.yaml"))
         assert a == b, name
