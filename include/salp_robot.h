@@ -10,6 +10,9 @@
  *   salp_robot_vec_step         SalpRobotEnv.step             salp_robot_env.py:139-201 — ONE env step is one
  *                               whole breathing cycle: Robot.set_control + step_through_cycle
  *                               (robot.py:335-358, 422-445), up to ~1450 Euler steps of dt = 0.01 s
+ *   salp_robot_vec_step_history  the same step, plus the per-Euler-step history that step_through_cycle
+ *                               collects with Robot.get_current_values (robot.py:398-445) for a range of envs
+ *   salp_robot_vec_history_capacity  samples per env that salp_robot_vec_step_history may write
  *
  * Actions are float32 [n][3] in the env's Box ([0,1], [0,1], [-1,1]): contraction / 0.06 m, coast time
  * / 10 s, nozzle yaw / (pi/2).  They are widened to fp64 before the rescale of salp_robot_env.py:129-137.
@@ -21,6 +24,32 @@
  * Same conventions as salp_vec.h (status codes, SALP_DEVICE_PTRS, streams, same-step autoreset).
  * The target point of each episode (np.random.uniform, :247-250) comes from
  *   Philox4x32-10(counter = (env_lo, env_hi, episode#, 16), key = seed): x from u53(w0,w1), y from u53(w2,w3).
+ *
+ * Cycle history (salp_robot_vec_step_history).  The reference's env step fills one history per Euler step
+ * (`[initial] + one per step`) and returns it in `info` (salp_robot_env.py:194-198).  Here it is recorded for the
+ * envs [hist_begin, hist_begin + hist_count) only, as float32 [hist_count][capacity][SALP_H_COUNT]:
+ *   - samples: for an env whose cycle ran T Euler steps, sample 0 is the state at the cycle start (after
+ *     set_control) and sample k the state after Euler step k; with stride s the samples are at steps
+ *     0, s, 2s, ... plus step T whenever T % s != 0, so the record always ends on the state the observation
+ *     reports.  history_len[j] = number of samples of env hist_begin + j (T + 1 at stride 1); samples past it
+ *     are not written.
+ *   - channels SALP_H_*: position xyz, body-frame velocity, Euler angles (roll, pitch, yaw), angular velocity,
+ *     length, width, phase (0 REFILL / 1 JET / 2 COAST / 3 REST, robot.py:194) and the rescaled nozzle yaw
+ *     (constant over a cycle).  These are what the env info, the renderer and compare_trajectories read; the
+ *     reference's other histories (acceleration, Euler-angle rate, jet / drag forces and torques, area, volume,
+ *     mass, drag coefficient) have no consumer and are not recorded.
+ *   - an env that terminates or truncates reports the cycle that just ran, before its autoreset.
+ *   - known difference: sample 0 has the init shape and REST in length / width / phase; the reference carries
+ *     the previous cycle's last values, which differ only when that cycle's last Euler step landed exactly on
+ *     a phase boundary, and then by <= 1 ulp in the shape.
+ *   - capacity must be >= salp_robot_vec_history_capacity(h, stride) (= the longest cycle the 14.6 s cut allows
+ *     at the configured dt, in samples; -1 if that cycle exceeds 2^24 Euler steps, a dt the history calls refuse).
+ *     stride < 1, a range outside [0, n), a smaller capacity or a NULL history with hist_count > 0 return -1 and
+ *     launch nothing; hist_count == 0 is salp_robot_vec_step.
+ *   - with SALP_DEVICE_PTRS history must be 16-byte aligned, nothing is allocated (graph-capturable), and nothing
+ *     past history_len[j] is written.  Host pointers are staged like the other outputs: the device buffer is
+ *     hist_count * capacity * 64 bytes, and hist_count rows of the call's longest record are copied back (in rows
+ *     with a shorter record the samples past history_len are overwritten with unspecified values).
  */
 #ifndef SALP_ROBOT_H
 #define SALP_ROBOT_H
@@ -57,6 +86,11 @@ enum {
   SALP_R_TARGET = 18, SALP_R_PREV_DIST = 20, SALP_R_VOLUME = 21, SALP_R_ANGLE1 = 22, SALP_R_ANGLE2 = 23,
   SALP_R_TIME = 24, SALP_R_CYCLE = 25, SALP_R_RNG = 26, SALP_R_COUNT = 27
 };
+/* channels of one float32 cycle-history sample [SALP_H_COUNT] (salp_robot_vec_step_history) */
+enum {
+  SALP_H_POS = 0, SALP_H_VEL = 3, SALP_H_EULER = 6, SALP_H_OMEGA = 9, SALP_H_LENGTH = 12, SALP_H_WIDTH = 13,
+  SALP_H_STATE = 14, SALP_H_NOZZLE_YAW = 15, SALP_H_COUNT = 16
+};
 
 typedef struct salp_robot_vec salp_robot_vec_t;
 
@@ -72,6 +106,14 @@ int salp_robot_vec_reset(salp_robot_vec_t* h, const uint8_t* mask, float* obs, u
 int salp_robot_vec_step(salp_robot_vec_t* h, const float* act, float* obs, float* reward, uint8_t* terminated,
                         uint8_t* truncated, float* final_obs, int32_t* inner_steps, uint32_t flags, void* stream);
 int salp_robot_vec_get_state(salp_robot_vec_t* h, double* state, uint32_t flags, void* stream);
+/* most samples per env one salp_robot_vec_step_history call writes at this stride (-1 if h is NULL or stride < 1) */
+int32_t salp_robot_vec_history_capacity(const salp_robot_vec_t* h, int32_t stride);
+/* salp_robot_vec_step plus the cycle history of envs [hist_begin, hist_begin + hist_count): history float
+ * [hist_count][capacity][SALP_H_COUNT], history_len (nullable) int32 [hist_count] (see the top of this file) */
+int salp_robot_vec_step_history(salp_robot_vec_t* h, const float* act, float* obs, float* reward, uint8_t* terminated,
+                                uint8_t* truncated, float* final_obs, int32_t* inner_steps, int64_t hist_begin,
+                                int64_t hist_count, int32_t stride, int32_t capacity, float* history,
+                                int32_t* history_len, uint32_t flags, void* stream);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,7 @@
 
 #include <new>
 #include <string>
+#include <vector>
 
 #include "../../include/salp_robot.h"
 #include "salp_device.h"   // philox4x32_10, u53
@@ -253,244 +254,77 @@ __global__ __launch_bounds__(kSchedBlock) void robot_schedule_scatter(RobotParam
   if (i < P.n) order[hist[b] + rank] = (int32_t)i;
 }
 
-// SalpRobotEnv.step (salp_robot_env.py:139-201): one breathing cycle per env.
+// ---- per-Euler-step history (salp_robot_vec_step_history) ----------------------------------------------
+// Recorded envs are the contiguous range [begin, begin + count); env i writes its samples to
+// hist[(i - begin) * capacity * SALP_H_COUNT ...], one contiguous 64-byte sample per recorded step as four 16-byte
+// stores.  The layout is env-major, so it does not depend on which lane the longest-cycle-first schedule put an env
+// in.  Measured against a time-major layout [capacity][SALP_H_COUNT][count] and against non-temporal stores
+// (profiles/robot_history_perf.py --layouts; the experiment builds -DSALP_ROBOT_HIST_TIME_MAJOR /
+// -DSALP_ROBOT_HIST_NONTEMPORAL select those): plain stores let L2 merge each lane's four 16-byte pieces into one
+// full 64-byte line before it goes to HBM, 4-5x the write rate of non-temporal ones, and beat time-major too.
+struct RobotHistory {
+  float* hist;          // [count][capacity][SALP_H_COUNT]
+  int32_t* len;         // [count], nullable
+  int64_t begin, count;
+  int32_t stride, capacity;
+};
+
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+template <typename T>
+__device__ __forceinline__ void history_store(T v, T* p) {
+#ifdef SALP_ROBOT_HIST_NONTEMPORAL
+  __builtin_nontemporal_store(v, p);
+#else
+  *p = v;
+#endif
+}
+
+// Sample k of history row j, in the channel order of SALP_H_* (include/salp_robot.h)
+__device__ __forceinline__ void store_history_sample(const RobotHistory& H, int64_t j, int32_t k, const Rb& r, double length,
+                                                     double width, int state, float yaw) {
+  static_assert(SALP_H_COUNT == 16 && SALP_H_POS == 0 && SALP_H_VEL == 3 && SALP_H_EULER == 6 && SALP_H_OMEGA == 9 &&
+                SALP_H_LENGTH == 12 && SALP_H_WIDTH == 13 && SALP_H_STATE == 14 && SALP_H_NOZZLE_YAW == 15, "channel order");
+  const f4 a = {(float)r.pos[0], (float)r.pos[1], (float)r.pos[2], (float)r.vel[0]};
+  const f4 b = {(float)r.vel[1], (float)r.vel[2], (float)r.eul[0], (float)r.eul[1]};
+  const f4 c = {(float)r.eul[2], (float)r.om[0], (float)r.om[1], (float)r.om[2]};
+  const f4 d = {(float)length, (float)width, (float)state, yaw};
+#ifdef SALP_ROBOT_HIST_TIME_MAJOR
+  float* p = H.hist + (int64_t)k * SALP_H_COUNT * H.count + j;   // channel q of sample k at p[q * count]
+  const int64_t n = H.count;
+  history_store(a.x, p); p += n; history_store(a.y, p); p += n; history_store(a.z, p); p += n; history_store(a.w, p); p += n;
+  history_store(b.x, p); p += n; history_store(b.y, p); p += n; history_store(b.z, p); p += n; history_store(b.w, p); p += n;
+  history_store(c.x, p); p += n; history_store(c.y, p); p += n; history_store(c.z, p); p += n; history_store(c.w, p); p += n;
+  history_store(d.x, p); p += n; history_store(d.y, p); p += n; history_store(d.z, p); p += n; history_store(d.w, p);
+#else
+  f4* p = reinterpret_cast<f4*>(H.hist + (j * H.capacity + k) * SALP_H_COUNT);
+  history_store(a, p + 0);
+  history_store(b, p + 1);
+  history_store(c, p + 2);
+  history_store(d, p + 3);
+#endif
+}
+
 #ifndef SALP_ROBOT_WAVES
 #define SALP_ROBOT_WAVES 2
 #endif
+// SalpRobotEnv.step (salp_robot_env.py:139-201): one breathing cycle per env (salp_robot_step_body.h)
 __global__ __launch_bounds__(kRBlock) __attribute__((amdgpu_waves_per_eu(SALP_ROBOT_WAVES, SALP_ROBOT_WAVES)))
 void salp_robot_step_kernel(RobotParams P, RobotState S, const float* act, float* obs,
                                                                   float* reward, uint8_t* terminated, uint8_t* truncated,
                                                                   float* final_obs, int32_t* inner_steps, const int32_t* order) {
-  const int64_t i0 = (int64_t)blockIdx.x * kRBlock + threadIdx.x;
-  const bool active = i0 < P.n;
-  // `order` (robot_schedule_* below) lists the envs longest cycle first, so that the lanes of a wavefront
-  // run about the same number of Euler steps; results do not depend on which lane an env runs in.
-  const int64_t i = active ? (order ? (int64_t)order[i0] : i0) : (P.n - 1);
-  const uint64_t genv = P.env_base + (uint64_t)i;
-  Rb r;
-  load_robot(r, S, P, i);
+  constexpr bool kRecord = false;
+  const RobotHistory H = {};
+#include "salp_robot_step_body.h"
+}
 
-  // _rescale_action (:129-137) in fp64
-  const double contraction = (double)act[i * 3 + 0] * 0.06;
-  const double coast_time = (double)act[i * 3 + 1] * 10.0;
-  const double yaw = (double)act[i * 3 + 2] * (kPi / 2);
-  // Nozzle.solve_angles (robot.py:55-85): target = R_br^T @ -(cos yaw, sin yaw, 0) = (-0, -sin yaw, cos yaw).
-  // Every angle here is within [-pi, pi]: sincos_small (salp_device.h) is exact to < 1 ulp there.
-  {
-    double sy, cy;
-    sincos_small(yaw, sy, cy);
-    const double t1 = -sy, t2 = cy;
-    double a2 = acos(clipd(2 * t2 - 1, -1.0, 1.0));
-    if (a2 <= -kPi) a2 += 2 * kPi; else if (a2 > kPi) a2 -= 2 * kPi;
-    double a1 = 0.0;
-    if (a2 != 0.0) {
-      double sa2, ca2;
-      sincos_small(a2, sa2, ca2);
-      const double a = 0.5 * (ca2 - 1);
-      const double b = sqrt(2.0) * sa2 / 2;
-      a1 = asin(clipd(t1 / sqrt(a * a + b * b), -1.0, 1.0)) - atan2(b, a);
-    }
-    if (a1 <= -kPi) a1 += 2 * kPi; else if (a1 > kPi) a1 -= 2 * kPi;
-    r.angle1 = a1; r.angle2 = a2;
-  }
-  // Nozzle.get_nozzle_direction (robot.py:115-130): R_br @ R_mb @ R_nm @ (cos g, 0, sin g), constant over the cycle
-  double dir[3];
-  {
-    double cg, sg, c2, s2, c1, s1;
-    sincos_small(P.nz_gamma, sg, cg);
-    sincos_small(r.angle2, s2, c2);
-    sincos_small(r.angle1, s1, c1);
-    // R_nm = R_theta_fixed @ R_nozzle(angle2); v1 = R_nm @ (cg, 0, sg)
-    const double nx = (cg * c2) * cg + (-sg) * sg;
-    const double ny = s2 * cg;
-    const double nzv = (sg * c2) * cg + cg * sg;
-    // R_mb = rotation about z by angle1
-    const double mx = c1 * nx + (-s1) * ny, my = s1 * nx + c1 * ny, mz = nzv;
-    // R_br = [[0,0,-1],[0,1,0],[1,0,0]]
-    dir[0] = -mz; dir[1] = my; dir[2] = mx;
-  }
-  // Robot.set_control (robot.py:335-358)
-  r.cycle += 1;
-  const double contract_rate = 0.06 / 3, release_rate = 0.06 / 1.5;
-  const double refill_time = contraction / contract_rate;
-  const double jet_time = contraction / release_rate;
-  // The cycle length comes straight from the caller's action.  Inside the action Box [0, 1]^3 it is at most
-  // 0.06 * 75 + 10 = 14.5 s; the device loop below is bounded by that maximum (kMaxCycleTime), so an unsquashed
-  // or diverged policy output (1e9, +inf) cannot spin a wavefront for ever — the reference would stall ONE CPU
-  // env for the corresponding 1e11 Euler steps; here a cycle longer than the Box allows is cut at the Box
-  // maximum (include/salp_robot.h).  A non-finite length runs no Euler step at all.
-  double total = active ? refill_time + jet_time + coast_time : 0.0;   // padding lanes do not step
-  total = (total <= kMaxCycleTime) ? total : ((total > kMaxCycleTime) ? kMaxCycleTime : 0.0);
-  double cycle_time = 0.0;
-  int steps = 0;
-  const double dt = P.dt;
-
-  // Robot.step_through_cycle (robot.py:422-445): lanes finish at different times.
-  //  * quantities that depend only on the body shape (mass, inertia, drag factors and their reciprocals)
-  //    are kept in registers and recomputed only on a step where some lane's shape moves or has just
-  //    stopped moving; during coast / rest (most of a cycle) the whole wavefront skips that block;
-  //  * sin/cos of the Euler angles are carried from step to step (see rotate_sincos below in the loop);
-  //  * divisions by dt, by cos(pitch) and by the mass / inertia diagonal are reciprocals (Newton-refined
-  //    v_rcp_f64) times a product: a few ulp from the reference's quotient, far inside the parity
-  //    tolerance, which is a tolerance already because the reference multiplies 3x3 blocks through BLAS.
-  const double inv_dt = rcp_nr(dt);
-  const double init_aspect = P.init_length / P.init_width;
-  const double contracted_length = P.init_length - P.max_contraction;
-  const double min_aspect = contracted_length / (P.init_length - contracted_length + P.init_width);
-  const double inv_aspect_span = rcp_nr(init_aspect - min_aspect);
-  const double t_jet_end = refill_time + jet_time, t_coast_end = t_jet_end + coast_time;
-  double mass = 0, inv_m = 0, kd = 0, ktc = 0, ax = 0, I0 = 0, I1 = 0, I2 = 0, iI0 = 0, iI1 = 0, iI2 = 0;
-  bool settled = false;    // the previous step of this lane already had the rest shape (and prevI == I)
-  // sin / cos of the three Euler angles are carried through the cycle: exact at its start, then advanced by each
-  // step's increment with rotate_sincos (increments are ~1e-3 rad; an increment above 0.25 rad anywhere in the
-  // wavefront takes the exact path for that step).  Drift over a whole cycle stays below 1e-12.
-  double sp, cp, st, ct, ss, cs;
-  sincos_euler(r.eul[0], sp, cp);
-  sincos_euler(r.eul[1], st, ct);
-  sincos_euler(r.eul[2], ss, cs);
-#pragma unroll 1
-  while (__any(cycle_time < total)) {
-    if (cycle_time < total) {
-      // Robot.step (robot.py:387-396)
-      cycle_time += dt;
-      r.time += dt;
-      int state;   // update_state :360-373
-      if (cycle_time <= refill_time) state = 0;
-      else if (cycle_time <= t_jet_end) state = 1;
-      else if (cycle_time <= t_coast_end) state = 2;
-      else state = 3;
-      double jf0 = 0.0, jf1 = 0.0, jf2 = 0.0, td0 = 0.0, td1 = 0.0, td2 = 0.0;
-      if (__any(state < 2 || !settled)) {
-        // update_properties :375-385
-        const double prev_volume = r.volume;
-        double length, width;
-        if (state == 0) { length = P.init_length - cycle_time * contract_rate; width = P.init_width + cycle_time * contract_rate; }
-        else if (state == 1) {
-          length = P.init_length - contraction + (cycle_time - refill_time) * release_rate;
-          width = P.init_width + contraction - (cycle_time - refill_time) * release_rate;
-        } else { length = P.init_length; width = P.init_width; }
-        const double hl = length / 2, hw = width / 2;
-        const double area = kPi * hl * hw;
-        r.volume = water_volume(length, width);
-        const double water_mass = P.density * r.volume;
-        mass = P.dry_mass + water_mass + P.nz_mass;
-        inv_m = rcp_nr(mass);
-        // drag coefficient, robot.py:627-649
-        const double aspect = length * rcp_nr(width);
-        const double nr = clipd((aspect - min_aspect) * inv_aspect_span, 0.0, 1.0);
-        const double cd = P.cd_max - nr * (P.cd_max - P.cd_min);
-        kd = -0.5 * P.density * area * cd;
-        ktc = -P.density * cd * hw * sq(sq(hl));
-        if (state == 1) {   // jet force, :494-505
-          const double volume_rate = -(r.volume - prev_volume) * inv_dt;
-          const double jet_speed = volume_rate / P.nz_area;
-          const double mass_rate = (water_mass - prev_volume * P.density) * inv_dt;
-          jf0 = 0.1 * mass_rate * (dir[0] * jet_speed);
-          jf1 = 0.1 * mass_rate * (dir[1] * jet_speed);
-          jf2 = 0.1 * mass_rate * (dir[2] * jet_speed);
-        }
-        ax = arm_x(P, length);
-        double I[3];
-        inertia_diag(P, mass, length, width, ax * ax, I);
-        I0 = I[0]; I1 = I[1]; I2 = I[2];
-        iI0 = rcp_nr(I0); iI1 = rcp_nr(I1); iI2 = rcp_nr(I2);
-        td0 = ((I0 - r.prevI[0]) * inv_dt) * r.om[0];
-        td1 = ((I1 - r.prevI[1]) * inv_dt) * r.om[1];
-        td2 = ((I2 - r.prevI[2]) * inv_dt) * r.om[2];
-        r.prevI[0] = I0; r.prevI[1] = I1; r.prevI[2] = I2;
-        settled = state >= 2;
-      }
-      // _newton_equations :494-505
-      const double wxv0 = r.om[1] * r.vel[2] - r.om[2] * r.vel[1];
-      const double wxv1 = r.om[2] * r.vel[0] - r.om[0] * r.vel[2];
-      const double wxv2 = r.om[0] * r.vel[1] - r.om[1] * r.vel[0];
-      const double vnorm = sqrt_nr(r.vel[0] * r.vel[0] + r.vel[1] * r.vel[1] + r.vel[2] * r.vel[2]);
-      const double kq = kd * vnorm;
-      const double acc0 = inv_m * (jf0 + (kq * r.vel[0] + kd * r.vel[0]) + mass * wxv0);
-      const double acc1 = inv_m * (jf1 + (kq * r.vel[1] + kd * r.vel[1]) + mass * wxv1);
-      const double acc2 = inv_m * (jf2 + (kq * r.vel[2] + kd * r.vel[2]) + mass * wxv2);
-      // _euler_equations :507-522
-      const double Iw0 = I0 * r.om[0], Iw1 = I1 * r.om[1], Iw2 = I2 * r.om[2];
-      const double c0 = r.om[1] * Iw2 - r.om[2] * Iw1;
-      const double c1 = r.om[2] * Iw0 - r.om[0] * Iw2;
-      const double c2 = r.om[0] * Iw1 - r.om[1] * Iw0;
-      const double wnorm = sqrt_nr(r.om[0] * r.om[0] + r.om[1] * r.om[1] + r.om[2] * r.om[2]);
-      const double kt = ktc * wnorm;
-      // jet torque = arm x jet_force, arm = (ax, 0, 0)
-      const double jt1 = -ax * jf2, jt2 = ax * jf1;
-      const double al0 = iI0 * (kt * r.om[0] + -c0 - td0);
-      const double al1 = iI1 * (jt1 + kt * r.om[1] + -c1 - td1);
-      const double al2 = iI2 * (jt2 + kt * r.om[2] + -c2 + 0.1 * vnorm - td2);
-      // _update_motion_states :524-532
-      r.vel[0] += acc0 * dt; r.vel[1] += acc1 * dt; r.vel[2] += acc2 * dt;
-      r.om[0] += al0 * dt; r.om[1] += al1 * dt; r.om[2] += al2 * dt;
-      {
-        const double ict = rcp_nr(ct);
-        const double tt = st * ict;
-        const double e0 = r.om[0] + (sp * tt) * r.om[1] + (cp * tt) * r.om[2];
-        const double e1 = cp * r.om[1] + (-sp) * r.om[2];
-        const double e2 = (sp * ict) * r.om[1] + (cp * ict) * r.om[2];
-        const double d0 = e0 * dt, d1 = e1 * dt, d2 = e2 * dt;
-        r.eul[0] += d0; r.eul[1] += d1; r.eul[2] += d2;
-        if (__any(fabs(d0) > 0.25 || fabs(d1) > 0.25 || fabs(d2) > 0.25)) {
-          sincos_euler(r.eul[0], sp, cp);
-          sincos_euler(r.eul[1], st, ct);
-          sincos_euler(r.eul[2], ss, cs);
-        } else {
-          rotate_sincos(sp, cp, d0);
-          rotate_sincos(st, ct, d1);
-          rotate_sincos(ss, cs, d2);
-        }
-      }
-      {
-        // R = R_z @ R_y @ R_x
-        const double r00 = cs * ct, r01 = cs * st * sp - ss * cp, r02 = cs * st * cp + ss * sp;
-        const double r10 = ss * ct, r11 = ss * st * sp + cs * cp, r12 = ss * st * cp - cs * sp;
-        const double r20 = -st, r21 = ct * sp, r22 = ct * cp;
-        r.vw[0] = r00 * r.vel[0] + r01 * r.vel[1] + r02 * r.vel[2];
-        r.vw[1] = r10 * r.vel[0] + r11 * r.vel[1] + r12 * r.vel[2];
-        r.vw[2] = r20 * r.vel[0] + r21 * r.vel[1] + r22 * r.vel[2];
-      }
-      r.pos[0] += r.vw[0] * dt; r.pos[1] += r.vw[1] * dt; r.pos[2] += r.vw[2] * dt;
-      ++steps;
-    }
-  }
-
-  // _calculate_reward (:203-243) and termination (:171-185)
-  const double dx = r.pos[0] - r.target[0], dy = r.pos[1] - r.target[1];
-  const double dist = sqrt(dx * dx + dy * dy);
-  const double r_track = (-dist + r.prev_dist) * 100;
-  r.prev_dist = dist;
-  const double ex = -(dx / (dist + 1e-6)), ey = -(dy / (dist + 1e-6));
-  const double vn = sqrt(r.vw[0] * r.vw[0] + r.vw[1] * r.vw[1]);
-  const double r_heading = (r.vw[0] / (vn + 1e-6)) * ex + (r.vw[1] / (vn + 1e-6)) * ey;
-  double rew = r_track + 0.5 * r_heading;
-  bool term = false, trunc = false;
-  if (dist < 0.01) { term = true; rew += 10.0; }
-  else if (dist > 5.0) { trunc = true; rew -= 5.0; }
-  if (r.cycle >= P.max_cycles) trunc = true;
-
-  float o[6];
-  if (term || trunc) {
-    if (final_obs && active) {
-      observe_robot(r, o);
-#pragma unroll
-      for (int k = 0; k < 6; ++k) final_obs[i * 6 + k] = o[k];
-    }
-    reset_robot(r, P, genv);
-  }
-  if (active) {
-    observe_robot(r, o);
-    if (obs) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) obs[i * 6 + k] = o[k];
-    }
-    if (reward) reward[i] = (float)rew;
-    if (terminated) terminated[i] = term ? 1 : 0;
-    if (truncated) truncated[i] = trunc ? 1 : 0;
-    if (inner_steps) inner_steps[i] = steps;
-    store_robot(r, S, P, i);
-  }
+// The same step, plus the cycle history of the envs [H.begin, H.begin + H.count)
+__global__ __launch_bounds__(kRBlock) __attribute__((amdgpu_waves_per_eu(SALP_ROBOT_WAVES, SALP_ROBOT_WAVES)))
+void salp_robot_step_record_kernel(RobotParams P, RobotState S, const float* act, float* obs, float* reward,
+                                   uint8_t* terminated, uint8_t* truncated, float* final_obs, int32_t* inner_steps,
+                                   const int32_t* order, RobotHistory H) {
+  constexpr bool kRecord = true;
+#include "salp_robot_step_body.h"
 }
 
 thread_local std::string g_rerr;
@@ -528,6 +362,8 @@ struct salp_robot_vec {
   uint32_t* bins;     // [kSchedBins]
   int32_t* order;     // [n]
   bool schedule;      // walk the envs longest cycle first (see robot_schedule_*)
+  int64_t max_steps;  // Euler steps of the longest cycle the kMaxCycleTime cut allows at this dt (0: not counted
+                      // yet, -1: more than kMaxHistorySteps); robot_max_steps
 };
 
 // Below this many envs every wavefront has an execution unit to itself and the launch lasts as long as
@@ -535,7 +371,8 @@ struct salp_robot_vec {
 static const int64_t kScheduleMinEnvs = 32768;
 
 static int launch_robot_step(salp_robot_vec* h, const float* act, float* obs, float* reward, uint8_t* terminated,
-                             uint8_t* truncated, float* final_obs, int32_t* inner_steps, hipStream_t st) {
+                             uint8_t* truncated, float* final_obs, int32_t* inner_steps, hipStream_t st,
+                             const RobotHistory* hist = nullptr) {
   const unsigned grid = (unsigned)((h->n + kRBlock - 1) / kRBlock);
   const int32_t* order = nullptr;
   if (h->schedule) {
@@ -546,8 +383,12 @@ static int launch_robot_step(salp_robot_vec* h, const float* act, float* obs, fl
     hipLaunchKernelGGL(robot_schedule_scatter, dim3(sgrid), dim3(kSchedBlock), 0, st, h->P, act, h->bins, h->order);
     order = h->order;
   }
-  hipLaunchKernelGGL(salp_robot_step_kernel, dim3(grid), dim3(kRBlock), 0, st, h->P, h->S, act, obs, reward, terminated,
-                     truncated, final_obs, inner_steps, order);
+  if (hist && hist->count > 0)
+    hipLaunchKernelGGL(salp_robot_step_record_kernel, dim3(grid), dim3(kRBlock), 0, st, h->P, h->S, act, obs, reward,
+                       terminated, truncated, final_obs, inner_steps, order, *hist);
+  else
+    hipLaunchKernelGGL(salp_robot_step_kernel, dim3(grid), dim3(kRBlock), 0, st, h->P, h->S, act, obs, reward, terminated,
+                       truncated, final_obs, inner_steps, order);
   RHIP_TRY(hipGetLastError());
   return 0;
 }
@@ -630,7 +471,10 @@ void salp_robot_vec_destroy(salp_robot_vec_t* h) {
 int64_t salp_robot_vec_num_envs(const salp_robot_vec_t* h) { return h ? h->n : 0; }
 
 static int robot_stage(salp_robot_vec* h, size_t bytes) {
-  if (bytes <= h->stage_bytes) return 0;
+  // grows on demand; shrinks again when a call needs less than a quarter of a large buffer (a history step with host
+  // pointers can stage gigabytes, the plain step after record_history(False) a few megabytes).  Every host-pointer
+  // call ends with a stream synchronisation, so the old buffer is idle here.
+  if (bytes <= h->stage_bytes && !(h->stage_bytes > ((size_t)64 << 20) && bytes < h->stage_bytes / 4)) return 0;
   if (h->stage) { (void)hipFree(h->stage); h->stage = nullptr; h->stage_bytes = 0; }
   RHIP_TRY(hipMalloc(&h->stage, bytes));
   h->stage_bytes = bytes;
@@ -693,6 +537,104 @@ int salp_robot_vec_step(salp_robot_vec_t* h, const float* act, float* obs, float
   if (terminated) RHIP_TRY(hipMemcpyAsync(terminated, d_te, n, hipMemcpyDeviceToHost, st));
   if (truncated) RHIP_TRY(hipMemcpyAsync(truncated, d_tr, n, hipMemcpyDeviceToHost, st));
   if (inner_steps) RHIP_TRY(hipMemcpyAsync(inner_steps, d_in, n * 4, hipMemcpyDeviceToHost, st));
+  RHIP_TRY(hipStreamSynchronize(st));
+  return 0;
+}
+
+// Longest cycle a history may have to hold, in Euler steps: the step kernel's own count for a cycle of kMaxCycleTime
+// (the same fp64 accumulation of dt), counted on first use.  A dt so small that this exceeds kMaxHistorySteps is
+// refused by the history calls rather than counted (below ~1e-17 s the sum would never reach 14.6 s).
+constexpr int64_t kMaxHistorySteps = (int64_t)1 << 24;
+static int64_t robot_max_steps(const salp_robot_vec* h) {
+  if (h->max_steps == 0) {
+    int64_t k = -1;
+    if (kMaxCycleTime / h->P.dt <= (double)kMaxHistorySteps) {
+      double t = 0.0;
+      k = 0;
+      while (t < kMaxCycleTime && k <= kMaxHistorySteps) { t += h->P.dt; ++k; }
+      if (k > kMaxHistorySteps) k = -1;
+    }
+    const_cast<salp_robot_vec*>(h)->max_steps = k;   // the same value whichever thread counts it
+  }
+  return h->max_steps;
+}
+static int64_t history_capacity(const salp_robot_vec* h, int32_t stride) {   // ceil(T_max / stride) + 1 samples, or -1
+  const int64_t t = robot_max_steps(h);
+  return t < 0 ? -1 : (t + stride - 1) / stride + 1;
+}
+
+int32_t salp_robot_vec_history_capacity(const salp_robot_vec_t* h, int32_t stride) {
+  if (!h || stride < 1) return -1;
+  return (int32_t)history_capacity(h, stride);
+}
+
+int salp_robot_vec_step_history(salp_robot_vec_t* h, const float* act, float* obs, float* reward, uint8_t* terminated,
+                                uint8_t* truncated, float* final_obs, int32_t* inner_steps, int64_t hist_begin,
+                                int64_t hist_count, int32_t stride, int32_t capacity, float* history,
+                                int32_t* history_len, uint32_t flags, void* stream) {
+  if (!h || !act) return rfail(-1, "handle / act is NULL");
+  if (stride < 1) return rfail(-1, "history stride must be >= 1");
+  if (hist_count < 0 || hist_begin < 0 || hist_begin > h->n || hist_count > h->n - hist_begin)
+    return rfail(-1, "history env range [hist_begin, hist_begin + hist_count) is outside [0, n_envs)");
+  if (hist_count == 0)
+    return salp_robot_vec_step(h, act, obs, reward, terminated, truncated, final_obs, inner_steps, flags, stream);
+  const int64_t need_cap = history_capacity(h, stride);
+  if (need_cap < 0) return rfail(-1, "dt is too small to record a history (more than 2^24 Euler steps per cycle)");
+  if ((int64_t)capacity < need_cap)
+    return rfail(-1, "history capacity " + std::to_string(capacity) + " is below salp_robot_vec_history_capacity = " +
+                     std::to_string(need_cap));
+  if (!history) return rfail(-1, "history is NULL while hist_count > 0");
+  if ((flags & 1u) && ((uintptr_t)history % 16u) != 0) return rfail(-1, "device history must be 16-byte aligned");
+  DeviceScope dev_scope;
+  RHIP_TRY(dev_scope.enter(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  RobotHistory H;
+  H.begin = hist_begin; H.count = hist_count; H.stride = stride; H.capacity = capacity;
+  if (flags & 1u) {
+    H.hist = history; H.len = history_len;
+    return launch_robot_step(h, act, obs, reward, terminated, truncated, final_obs, inner_steps, st, &H);
+  }
+  // host pointers: everything staged as in salp_robot_vec_step.  The history goes back as hist_count rows of the
+  // longest record of this call (one 2-D copy after the lengths are known); nothing is copied in, so in rows with
+  // a shorter record the samples past history_len are overwritten with unspecified values.
+  const size_t n = (size_t)h->n;
+  const size_t hb = (size_t)hist_count * (size_t)capacity * SALP_H_COUNT * sizeof(float);
+  const size_t lb = (size_t)hist_count * sizeof(int32_t);
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t need = up(n * 12) + 2 * up(n * 24) + up(n * 4) + 2 * up(n) + up(n * 4) + up(lb) + hb + 1024;
+  int rc = robot_stage(h, need);
+  if (rc) return rc;
+  char* b = (char*)h->stage;
+  float* d_act = (float*)b; b += up(n * 12);
+  float* d_obs = (float*)b; b += up(n * 24);
+  float* d_fin = (float*)b; b += up(n * 24);
+  float* d_rew = (float*)b; b += up(n * 4);
+  uint8_t* d_te = (uint8_t*)b; b += up(n);
+  uint8_t* d_tr = (uint8_t*)b; b += up(n);
+  int32_t* d_in = (int32_t*)b; b += up(n * 4);
+  int32_t* d_len = (int32_t*)b; b += up(lb);
+  float* d_hist = (float*)b;
+  RHIP_TRY(hipMemcpyAsync(d_act, act, n * 12, hipMemcpyHostToDevice, st));
+  if (final_obs) RHIP_TRY(hipMemcpyAsync(d_fin, final_obs, n * 24, hipMemcpyHostToDevice, st));
+  H.hist = d_hist; H.len = d_len;
+  rc = launch_robot_step(h, d_act, obs ? d_obs : nullptr, reward ? d_rew : nullptr, terminated ? d_te : nullptr,
+                         truncated ? d_tr : nullptr, final_obs ? d_fin : nullptr, inner_steps ? d_in : nullptr, st, &H);
+  if (rc) return rc;
+  if (obs) RHIP_TRY(hipMemcpyAsync(obs, d_obs, n * 24, hipMemcpyDeviceToHost, st));
+  if (final_obs) RHIP_TRY(hipMemcpyAsync(final_obs, d_fin, n * 24, hipMemcpyDeviceToHost, st));
+  if (reward) RHIP_TRY(hipMemcpyAsync(reward, d_rew, n * 4, hipMemcpyDeviceToHost, st));
+  if (terminated) RHIP_TRY(hipMemcpyAsync(terminated, d_te, n, hipMemcpyDeviceToHost, st));
+  if (truncated) RHIP_TRY(hipMemcpyAsync(truncated, d_tr, n, hipMemcpyDeviceToHost, st));
+  if (inner_steps) RHIP_TRY(hipMemcpyAsync(inner_steps, d_in, n * 4, hipMemcpyDeviceToHost, st));
+  std::vector<int32_t> len((size_t)hist_count);
+  RHIP_TRY(hipMemcpyAsync(len.data(), d_len, lb, hipMemcpyDeviceToHost, st));
+  RHIP_TRY(hipStreamSynchronize(st));
+  int32_t longest = 0;
+  for (int32_t v : len) longest = v > longest ? v : longest;
+  const size_t row = (size_t)capacity * SALP_H_COUNT * sizeof(float);
+  RHIP_TRY(hipMemcpy2DAsync(history, row, d_hist, row, (size_t)longest * SALP_H_COUNT * sizeof(float), (size_t)hist_count,
+                            hipMemcpyDeviceToHost, st));
+  if (history_len) memcpy(history_len, len.data(), lb);
   RHIP_TRY(hipStreamSynchronize(st));
   return 0;
 }

@@ -7,6 +7,8 @@
 
 One `step` is one whole breathing cycle of every robot (Robot.set_control + step_through_cycle,
 robot.py:335-358, 422-445): `info["inner_steps"]` is the number of Euler steps each robot took.
+`env.record_history(slice(a, b), stride)` adds the per-Euler-step history of those robots to `info`
+(`cycle_history`, `cycle_history_len`, `cycle_history_envs`; `env.history_of(i)` in the reference's shape).
 Same conventions as SalpVectorEnv: device tensors, same-step autoreset with `final_observation`,
 no CPU fallback."""
 from __future__ import annotations
@@ -23,8 +25,17 @@ from .spaces import Box, batch_space
 (R_POS, R_VEL, R_EULER, R_OMEGA, R_VEL_WORLD, R_PREV_I, R_TARGET, R_PREV_DIST, R_VOLUME, R_ANGLE1, R_ANGLE2, R_TIME,
  R_CYCLE, R_RNG, R_COUNT) = 0, 3, 6, 9, 12, 15, 18, 20, 21, 22, 23, 24, 25, 26, 27
 
+# channels of one cycle-history sample (SALP_H_* of include/salp_robot.h)
+(H_POS, H_VEL, H_EULER, H_OMEGA, H_LENGTH, H_WIDTH, H_STATE, H_NOZZLE_YAW, H_COUNT) = 0, 3, 6, 9, 12, 13, 14, 15, 16
+# history_of(i) keys (the reference's Robot.*_history names) -> (first channel, width; None = scalar per sample)
+HISTORY_CHANNELS = {"position_history": (H_POS, 3), "velocity_history": (H_VEL, 3), "euler_angle_history": (H_EULER, 3),
+                    "angular_velocity_history": (H_OMEGA, 3), "length_history": (H_LENGTH, None),
+                    "width_history": (H_WIDTH, None), "state_history": (H_STATE, None),
+                    "nozzle_yaw_history": (H_NOZZLE_YAW, None)}
+
 ROBOT_EXPORTS = ("salp_robot_last_error", "salp_robot_config_default", "salp_robot_vec_create", "salp_robot_vec_destroy",
-                 "salp_robot_vec_num_envs", "salp_robot_vec_reset", "salp_robot_vec_step", "salp_robot_vec_get_state")
+                 "salp_robot_vec_num_envs", "salp_robot_vec_reset", "salp_robot_vec_step", "salp_robot_vec_get_state",
+                 "salp_robot_vec_history_capacity", "salp_robot_vec_step_history")
 
 
 class CRobotConfig(ctypes.Structure):
@@ -52,6 +63,10 @@ def _lib():
         L.salp_robot_vec_reset.argtypes = [vp, vp, vp, u32, vp]
         L.salp_robot_vec_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]
         L.salp_robot_vec_get_state.argtypes = [vp, vp, u32, vp]
+        L.salp_robot_vec_history_capacity.argtypes = [vp, ctypes.c_int32]
+        L.salp_robot_vec_history_capacity.restype = ctypes.c_int32
+        L.salp_robot_vec_step_history.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, ctypes.c_int32, ctypes.c_int32,
+                                                  vp, vp, u32, vp]
         L._salp_robot_ready = True
     return L
 
@@ -93,6 +108,7 @@ class SalpRobotVectorEnv:
         self._obs, self._fin = self._new((n, 6), np.float32), self._new((n, 6), np.float32)
         self._rew, self._term, self._trunc = self._new((n,), np.float32), self._new((n,), np.uint8), self._new((n,), np.uint8)
         self._inner = self._new((n,), np.int32)
+        self._hist = None      # (begin, count, stride, capacity, history, history_len) while record_history is on
 
     def _new(self, shape, dtype):
         if self._torch is not None:
@@ -128,6 +144,53 @@ class SalpRobotVectorEnv:
         _check(self.L, self.L.salp_robot_vec_reset(self._h, self._p(zero), self._p(self._obs), self._flags, self._stream), "observe")
         return self._obs
 
+    def history_capacity(self, stride: int = 1) -> int:
+        """Most samples one cycle can record per env at this stride (salp_robot_vec_history_capacity)."""
+        c = self.L.salp_robot_vec_history_capacity(self._h, int(stride))
+        if c < 0:
+            raise ValueError(f"no history at stride {stride}: stride must be >= 1 and a cycle at most 2^24 Euler steps")
+        return int(c)
+
+    def record_history(self, envs=None, stride: int = 1):
+        """Records the per-Euler-step history of every later `step` for the envs `envs` (a slice with step 1, None for
+        all of them) every `stride` Euler steps; `record_history(False)` turns recording off.  The buffers are allocated
+        here and reused by every step: `info["cycle_history"]` float32 [R, capacity, 16] (channels H_*, samples past
+        `info["cycle_history_len"]` int32 [R] unspecified), `info["cycle_history_envs"]` = (begin, R)."""
+        if envs is False:
+            self._hist = None
+            return
+        if envs is None or envs is True:
+            envs = slice(0, self.num_envs)
+        if not isinstance(envs, slice) or envs.step not in (None, 1):
+            raise TypeError("envs must be a contiguous slice(a, b), None or False")
+        begin, end, _ = envs.indices(self.num_envs)
+        count = max(0, end - begin)
+        if count == 0:
+            raise ValueError(f"empty env range {envs}")
+        cap = self.history_capacity(stride)
+        self._hist = (begin, count, int(stride), cap, self._new((count, cap, H_COUNT), np.float32), self._new((count,), np.int32))
+
+    def history_of(self, i: int) -> dict:
+        """The reference-shaped cycle history (Robot.*_history after step_through_cycle) of recorded env `i` for the
+        last step: float64 numpy arrays of length L = its sample count ([L, 3] for vectors), `state_history` int."""
+        if self._hist is None:
+            raise RuntimeError("record_history is off")
+        begin, count = self._hist[0], self._hist[1]
+        if not begin <= i < begin + count:
+            raise IndexError(f"env {i} is not recorded (recorded: [{begin}, {begin + count}))")
+        j = i - begin
+        if self._torch is not None:
+            L = int(self._hist[5][j].item())
+            h = self._hist[4][j, :L].cpu().numpy()
+        else:
+            L = int(self._hist[5][j])
+            h = self._hist[4][j, :L]
+        out = {}
+        for key, (c, w) in HISTORY_CHANNELS.items():
+            out[key] = h[:, c:c + w].astype(np.float64) if w else h[:, c].astype(np.float64)
+        out["state_history"] = h[:, H_STATE].astype(np.int64)
+        return out
+
     def step(self, actions):
         if self._torch is not None:
             t = self._torch
@@ -135,14 +198,24 @@ class SalpRobotVectorEnv:
             a = a.to(self.device, t.float32).reshape(self.num_envs, 3).contiguous()
         else:
             a = np.ascontiguousarray(np.asarray(actions, np.float32).reshape(self.num_envs, 3))
-        _check(self.L, self.L.salp_robot_vec_step(self._h, self._p(a), self._p(self._obs), self._p(self._rew), self._p(self._term),
-                                                   self._p(self._trunc), self._p(self._fin), self._p(self._inner), self._flags,
-                                                   self._stream), "step")
+        if self._hist is None:
+            _check(self.L, self.L.salp_robot_vec_step(self._h, self._p(a), self._p(self._obs), self._p(self._rew), self._p(self._term),
+                                                       self._p(self._trunc), self._p(self._fin), self._p(self._inner), self._flags,
+                                                       self._stream), "step")
+        else:
+            begin, count, stride, cap, hist, hlen = self._hist
+            _check(self.L, self.L.salp_robot_vec_step_history(
+                self._h, self._p(a), self._p(self._obs), self._p(self._rew), self._p(self._term), self._p(self._trunc),
+                self._p(self._fin), self._p(self._inner), begin, count, stride, cap, self._p(hist), self._p(hlen), self._flags,
+                self._stream), "step")
         if self._torch is not None:
             term, trunc = self._term.view(self._torch.bool), self._trunc.view(self._torch.bool)
         else:
             term, trunc = self._term.view(np.bool_), self._trunc.view(np.bool_)
         info = {"inner_steps": self._inner, "final_observation": self._fin, "_final_observation": term | trunc}
+        if self._hist is not None:
+            info["cycle_history"], info["cycle_history_len"] = self._hist[4], self._hist[5]
+            info["cycle_history_envs"] = (self._hist[0], self._hist[1])
         return self._obs, self._rew, term, trunc, info
 
     def get_state(self) -> np.ndarray:
