@@ -13,6 +13,8 @@
  *   salp_robot_vec_step_history  the same step, plus the per-Euler-step history that step_through_cycle
  *                               collects with Robot.get_current_values (robot.py:398-445) for a range of envs
  *   salp_robot_vec_history_capacity  samples per env that salp_robot_vec_step_history may write
+ *   salp_robot_vec_trajectory   compare_actions_with_states (compare_trajectories.py:19-117) for every robot of the
+ *                               handle at once, each with its own physical parameters (system identification)
  *
  * Actions are float32 [n][3] in the env's Box ([0,1], [0,1], [-1,1]): contraction / 0.06 m, coast time
  * / 10 s, nozzle yaw / (pi/2).  They are widened to fp64 before the rescale of salp_robot_env.py:129-137.
@@ -50,6 +52,33 @@
  *     past history_len[j] is written.  Host pointers are staged like the other outputs: the device buffer is
  *     hist_count * capacity * 64 bytes, and hist_count rows of the call's longest record are copied back (in rows
  *     with a shorter record the samples past history_len are overwritten with unspecified values).
+ *
+ * Trajectory comparison (salp_robot_vec_trajectory).  Robot i of the handle runs what compare_actions_with_states
+ * does with one Robot: Robot.reset (robot.py:287-333: origin, zero velocities and angles, rest shape, cycle time 0),
+ * then for t in [0, cycles) nozzle.set_yaw_angle + solve_angles + set_control + step_through_cycle with actions[t]
+ * (compare_trajectories.py:51-72), and reports states[t][i] = position x, y, body-frame velocity x, y, yaw, yaw rate.
+ *   - the call neither reads nor writes the env state of the handle (SALP_R_* rows, target draws, schedule): a
+ *     later salp_robot_vec_step behaves as if it never happened.
+ *   - actions are fp64 in the reference's units: contraction (m), coast time (s), nozzle yaw (rad), not the env's Box;
+ *     no rescale.  [cycles][3], shared by every robot; with SALP_ROBOT_PER_ROBOT_ACTIONS [cycles][n_envs][3] (run in
+ *     index order, no longest-cycle-first schedule).  The cycle-length guard of the env step applies: a cycle longer
+ *     than 14.6 s is cut there, and a non-finite length runs no Euler step.
+ *   - params (nullable) double [SALP_RP_COUNT][n_envs]: robot i takes column i for what the reference takes from
+ *     Robot(...), Nozzle(...), set_environment(density) and _drag_coefficents; dt, the tank, max_cycles and the
+ *     contract / release rates stay the handle's (nozzle_length3 is drawing code only).  NULL = the handle's config
+ *     for every robot, bit-identical to a table filled with it.  The table is not validated (it may live on the
+ *     device): a zero, negative or NaN entry gives that robot meaningless or non-finite output and nothing else;
+ *     cycle lengths depend only on the actions and dt, and other robots move by no more than the wave-uniform exact
+ *     sin / cos and sqrt fallbacks couple lanes (< 1e-12 relative per cycle).
+ *   - expected (nullable) double [cycles][6]; metrics double [n_envs][SALP_RM_COUNT] needs it: the means over t of
+ *     |d(x, y)|, |d(vx, vy)|, |d yaw| (not wrapped), |d yaw rate| and the max over t of |d(x, y)|
+ *     (compare_trajectories.py:77-86), summed in fp64 in cycle order; a NaN error gives a NaN mean and max.
+ *   - states double [cycles][n_envs][6], metrics, inner_steps int32 [cycles][n_envs] (Euler steps per cycle,
+ *     len(position_history) - 1) are each nullable; a metrics-only call writes no per-cycle data.
+ *   - -1 and no launch: NULL handle or actions, cycles outside [1, SALP_ROBOT_MAX_TRAJECTORY_CYCLES], unknown flag
+ *     bits, metrics without expected, a dt the history calls refuse.  The cap bounds one launch on a shared GPU.
+ *   - SALP_DEVICE_PTRS: nothing is allocated or synchronised (graph-capturable); host pointers are staged and copied
+ *     back, and the call returns after the stream is synchronised.
  */
 #ifndef SALP_ROBOT_H
 #define SALP_ROBOT_H
@@ -92,6 +121,23 @@ enum {
   SALP_H_STATE = 14, SALP_H_NOZZLE_YAW = 15, SALP_H_COUNT = 16
 };
 
+/* rows of the per-robot parameter table double [SALP_RP_COUNT][n_envs] (salp_robot_vec_trajectory); the names are
+ * those of the salp_robot_config_t fields */
+enum {
+  SALP_RP_DRY_MASS = 0, SALP_RP_INIT_LENGTH = 1, SALP_RP_INIT_WIDTH = 2, SALP_RP_MAX_CONTRACTION = 3, SALP_RP_DENSITY = 4,
+  SALP_RP_DRAG_COEFFICIENT_MIN = 5, SALP_RP_DRAG_COEFFICIENT_MAX = 6, SALP_RP_NOZZLE_LENGTH1 = 7,
+  SALP_RP_NOZZLE_LENGTH2 = 8, SALP_RP_NOZZLE_AREA = 9, SALP_RP_NOZZLE_MASS = 10, SALP_RP_NOZZLE_GAMMA = 11,
+  SALP_RP_COUNT = 12
+};
+/* columns of the per-robot metrics double [n_envs][SALP_RM_COUNT] (salp_robot_vec_trajectory) */
+enum {
+  SALP_RM_POSITION_ERROR = 0, SALP_RM_VELOCITY_ERROR = 1, SALP_RM_ANGLE_ERROR = 2, SALP_RM_MAX_POSITION_ERROR = 3,
+  SALP_RM_ANGULAR_VELOCITY_ERROR = 4, SALP_RM_COUNT = 5
+};
+/* flag bit of salp_robot_vec_trajectory next to SALP_DEVICE_PTRS (1u): actions are [cycles][n_envs][3] */
+enum { SALP_ROBOT_PER_ROBOT_ACTIONS = 2u };
+enum { SALP_ROBOT_MAX_TRAJECTORY_CYCLES = 1024 };
+
 typedef struct salp_robot_vec salp_robot_vec_t;
 
 const char* salp_robot_last_error(void);   /* message of the calling thread's last failed salp_robot_* call */
@@ -114,6 +160,13 @@ int salp_robot_vec_step_history(salp_robot_vec_t* h, const float* act, float* ob
                                 uint8_t* truncated, float* final_obs, int32_t* inner_steps, int64_t hist_begin,
                                 int64_t hist_count, int32_t stride, int32_t capacity, float* history,
                                 int32_t* history_len, uint32_t flags, void* stream);
+/* compare_actions_with_states for every robot, each with its own parameters (see the top of this file): params
+ * (nullable) double [SALP_RP_COUNT][n], actions double [cycles][3] or [cycles][n][3], expected (nullable) double
+ * [cycles][6], states (nullable) double [cycles][n][6], metrics (nullable) double [n][SALP_RM_COUNT], inner_steps
+ * (nullable) int32 [cycles][n] */
+int salp_robot_vec_trajectory(salp_robot_vec_t* h, const double* params, const double* actions, int32_t cycles,
+                              const double* expected, double* states, double* metrics, int32_t* inner_steps,
+                              uint32_t flags, void* stream);
 
 #ifdef __cplusplus
 }

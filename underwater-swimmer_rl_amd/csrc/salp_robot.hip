@@ -155,12 +155,8 @@ __device__ __forceinline__ void inertia_diag(const RobotParams& P, double mass, 
 // (R_mb turns about z, the links lie on z; robot.py:132-151, 567-575)
 __device__ __forceinline__ double arm_x(const RobotParams& P, double length) { return -(P.nz_l1 + P.nz_l2) + -length / 2; }
 
-// robot.py:287-312 Robot.reset + salp_robot_env.py:98-128 (new target, prev_dist)
-__device__ __forceinline__ void reset_robot(Rb& r, const RobotParams& P, uint64_t genv) {
-  const U4 w = philox4x32_10((uint32_t)genv, (uint32_t)(genv >> 32), r.rng, 16u, P.seed_lo, P.seed_hi);
-  r.rng += 1u;
-  r.target[0] = P.x_min + P.x_span * u53(w.x, w.y);
-  r.target[1] = P.y_min + P.y_span * u53(w.z, w.w);
+// robot.py:287-312 Robot.reset: at rest at the origin, rest shape, cycle time 0
+__device__ __forceinline__ void rest_robot(Rb& r, const RobotParams& P) {
 #pragma unroll
   for (int k = 0; k < 3; ++k) { r.pos[k] = 0.0; r.vel[k] = 0.0; r.eul[k] = 0.0; r.om[k] = 0.0; r.vw[k] = 0.0; }
   r.time = 0.0; r.cycle = 0;
@@ -168,6 +164,14 @@ __device__ __forceinline__ void reset_robot(Rb& r, const RobotParams& P, uint64_
   r.volume = water_volume(length, width);
   const double mass = P.dry_mass + P.density * r.volume + P.nz_mass;
   inertia_diag(P, mass, length, width, sq(arm_x(P, length)), r.prevI);
+}
+// Robot.reset + salp_robot_env.py:98-128 (new target, prev_dist)
+__device__ __forceinline__ void reset_robot(Rb& r, const RobotParams& P, uint64_t genv) {
+  const U4 w = philox4x32_10((uint32_t)genv, (uint32_t)(genv >> 32), r.rng, 16u, P.seed_lo, P.seed_hi);
+  r.rng += 1u;
+  r.target[0] = P.x_min + P.x_span * u53(w.x, w.y);
+  r.target[1] = P.y_min + P.y_span * u53(w.z, w.w);
+  rest_robot(r, P);
   const double dx = r.pos[0] - r.target[0], dy = r.pos[1] - r.target[1];
   r.prev_dist = sqrt(dx * dx + dy * dy);
 }
@@ -325,6 +329,80 @@ void salp_robot_step_record_kernel(RobotParams P, RobotState S, const float* act
                                    const int32_t* order, RobotHistory H) {
   constexpr bool kRecord = true;
 #include "salp_robot_step_body.h"
+}
+
+// ---- trajectory comparison (salp_robot_vec_trajectory) -------------------------------------------------
+// compare_actions_with_states (compare_trajectories.py:19-117) for n robots, each with its own physical parameters:
+// Robot.reset, then `cycles` breathing cycles, each reported as (x, y, vx, vy, yaw, yaw rate).  One robot per lane,
+// in registers for the whole call; the handle's env state is neither read nor written.
+constexpr int32_t kMaxTrajectoryCycles = SALP_ROBOT_MAX_TRAJECTORY_CYCLES;
+
+struct RobotTrajectory {
+  const double* params;     // [SALP_RP_COUNT][n], nullable: every robot takes the handle's config
+  const double* actions;    // [cycles][3] (m, s, rad), or [cycles][n][3] with per_robot
+  const double* expected;   // [cycles][6], nullable
+  double* states;           // [cycles][n][6], nullable
+  double* metrics;          // [n][SALP_RM_COUNT], nullable (only with expected)
+  int32_t* inner_steps;     // [cycles][n], nullable
+  int32_t cycles, per_robot;
+};
+
+__global__ __launch_bounds__(kRBlock) __attribute__((amdgpu_waves_per_eu(SALP_ROBOT_WAVES, SALP_ROBOT_WAVES)))
+void salp_robot_trajectory_kernel(RobotParams P0, RobotTrajectory J) {
+  constexpr bool kRecord = false;
+  const RobotHistory H = {};
+  const int64_t i0 = (int64_t)blockIdx.x * kRBlock + threadIdx.x;
+  const bool active = i0 < P0.n;
+  const int64_t i = active ? i0 : (P0.n - 1);
+  const int64_t n = P0.n;
+  // this robot's parameters: one coalesced load per row of the table.  Without a table every lane takes the config's
+  // values and runs the same code, so that path is bit-identical to a table filled with them.
+  RobotParams P = P0;
+  if (J.params) {
+    static_assert(SALP_RP_DRY_MASS == 0 && SALP_RP_INIT_LENGTH == 1 && SALP_RP_INIT_WIDTH == 2 && SALP_RP_MAX_CONTRACTION == 3 &&
+                  SALP_RP_DENSITY == 4 && SALP_RP_DRAG_COEFFICIENT_MIN == 5 && SALP_RP_DRAG_COEFFICIENT_MAX == 6 &&
+                  SALP_RP_NOZZLE_LENGTH1 == 7 && SALP_RP_NOZZLE_LENGTH2 == 8 && SALP_RP_NOZZLE_AREA == 9 &&
+                  SALP_RP_NOZZLE_MASS == 10 && SALP_RP_NOZZLE_GAMMA == 11 && SALP_RP_COUNT == 12, "parameter rows");
+    const double* q = J.params + i;
+    P.dry_mass = q[0 * n]; P.init_length = q[1 * n]; P.init_width = q[2 * n]; P.max_contraction = q[3 * n];
+    P.density = q[4 * n]; P.cd_min = q[5 * n]; P.cd_max = q[6 * n]; P.nz_l1 = q[7 * n]; P.nz_l2 = q[8 * n];
+    P.nz_area = q[9 * n]; P.nz_mass = q[10 * n]; P.nz_gamma = q[11 * n];
+  }
+  Rb r;
+  rest_robot(r, P);
+  r.angle1 = 0.0; r.angle2 = 0.0;
+  // compare_trajectories.py:77-86: sums in cycle order, kept in metrics[i] between cycles (not in registers: the
+  // Euler loop needs them all); a NaN error makes the sums NaN and sticks in the max (like np.max; fmax drops it)
+  double* m = (active && J.metrics) ? J.metrics + i * SALP_RM_COUNT : nullptr;
+  for (int32_t t = 0; t < J.cycles; ++t) {
+    const double* a = J.actions + (J.per_robot ? ((int64_t)t * n + i) * 3 : (int64_t)t * 3);
+    const double contraction = a[0], coast_time = a[1], yaw = a[2];
+#include "salp_robot_cycle_body.h"
+    if (active) {
+      const int64_t o = (int64_t)t * n + i;
+      if (J.states) {   // time-major: the 64 lanes of a wavefront store 3 KB of contiguous bytes per cycle
+        double* s = J.states + o * 6;
+        s[0] = r.pos[0]; s[1] = r.pos[1]; s[2] = r.vel[0]; s[3] = r.vel[1]; s[4] = r.eul[2]; s[5] = r.om[2];
+      }
+      if (J.inner_steps) J.inner_steps[o] = steps;
+      if (m) {
+        const double* x = J.expected + (int64_t)t * 6;
+        const double d0 = r.pos[0] - x[0], d1 = r.pos[1] - x[1], d2 = r.vel[0] - x[2], d3 = r.vel[1] - x[3];
+        const double ep = sqrt(d0 * d0 + d1 * d1), ev = sqrt(d2 * d2 + d3 * d3);
+        const double ea = fabs(r.eul[2] - x[4]), eo = fabs(r.om[2] - x[5]);
+        if (t == 0) {
+          m[0] = ep; m[1] = ev; m[2] = ea; m[3] = ep; m[4] = eo;
+        } else {
+          m[0] += ep; m[1] += ev; m[2] += ea; m[4] += eo;
+          if (!(m[3] != m[3]) && !(ep <= m[3])) m[3] = ep;
+        }
+      }
+    }
+  }
+  if (m) {
+    const double c = (double)J.cycles;
+    m[0] = m[0] / c; m[1] = m[1] / c; m[2] = m[2] / c; m[4] = m[4] / c;
+  }
 }
 
 thread_local std::string g_rerr;
@@ -635,6 +713,59 @@ int salp_robot_vec_step_history(salp_robot_vec_t* h, const float* act, float* ob
   RHIP_TRY(hipMemcpy2DAsync(history, row, d_hist, row, (size_t)longest * SALP_H_COUNT * sizeof(float), (size_t)hist_count,
                             hipMemcpyDeviceToHost, st));
   if (history_len) memcpy(history_len, len.data(), lb);
+  RHIP_TRY(hipStreamSynchronize(st));
+  return 0;
+}
+
+int salp_robot_vec_trajectory(salp_robot_vec_t* h, const double* params, const double* actions, int32_t cycles,
+                              const double* expected, double* states, double* metrics, int32_t* inner_steps,
+                              uint32_t flags, void* stream) {
+  if (!h || !actions) return rfail(-1, "handle / actions is NULL");
+  if (cycles < 1 || cycles > kMaxTrajectoryCycles)
+    return rfail(-1, "cycles must be in [1, " + std::to_string(kMaxTrajectoryCycles) + "]");
+  if (flags & ~(1u | (uint32_t)SALP_ROBOT_PER_ROBOT_ACTIONS)) return rfail(-1, "unknown flag bits");
+  if (metrics && !expected) return rfail(-1, "metrics need expected states");
+  // the same refusal as the history calls: with such a dt one cycle of the 14.6 s cut exceeds 2^24 Euler steps
+  if (robot_max_steps(h) < 0) return rfail(-1, "dt is too small (more than 2^24 Euler steps per cycle)");
+  DeviceScope dev_scope;
+  RHIP_TRY(dev_scope.enter(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  const bool per_robot = (flags & SALP_ROBOT_PER_ROBOT_ACTIONS) != 0;
+  const unsigned grid = (unsigned)((h->n + kRBlock - 1) / kRBlock);
+  RobotTrajectory J;
+  J.cycles = cycles; J.per_robot = per_robot ? 1 : 0;
+  if (flags & 1u) {
+    J.params = params; J.actions = actions; J.expected = expected; J.states = states; J.metrics = metrics;
+    J.inner_steps = inner_steps;
+    hipLaunchKernelGGL(salp_robot_trajectory_kernel, dim3(grid), dim3(kRBlock), 0, st, h->P, J);
+    RHIP_TRY(hipGetLastError());
+    return 0;
+  }
+  // host pointers: staged and copied back like the other calls
+  const size_t n = (size_t)h->n, T = (size_t)cycles;
+  const size_t pb = params ? (size_t)SALP_RP_COUNT * n * 8 : 0, ab = T * (per_robot ? n : 1) * 24;
+  const size_t xb = expected ? T * 48 : 0, sb = states ? T * n * 48 : 0, mb = metrics ? n * SALP_RM_COUNT * 8 : 0;
+  const size_t ib = inner_steps ? T * n * 4 : 0;
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  int rc = robot_stage(h, up(pb) + up(ab) + up(xb) + up(sb) + up(mb) + up(ib) + 1024);
+  if (rc) return rc;
+  char* b = (char*)h->stage;
+  double* d_par = (double*)b; b += up(pb);
+  double* d_act = (double*)b; b += up(ab);
+  double* d_exp = (double*)b; b += up(xb);
+  double* d_st = (double*)b; b += up(sb);
+  double* d_met = (double*)b; b += up(mb);
+  int32_t* d_in = (int32_t*)b;
+  if (params) RHIP_TRY(hipMemcpyAsync(d_par, params, pb, hipMemcpyHostToDevice, st));
+  RHIP_TRY(hipMemcpyAsync(d_act, actions, ab, hipMemcpyHostToDevice, st));
+  if (expected) RHIP_TRY(hipMemcpyAsync(d_exp, expected, xb, hipMemcpyHostToDevice, st));
+  J.params = params ? d_par : nullptr; J.actions = d_act; J.expected = expected ? d_exp : nullptr;
+  J.states = states ? d_st : nullptr; J.metrics = metrics ? d_met : nullptr; J.inner_steps = inner_steps ? d_in : nullptr;
+  hipLaunchKernelGGL(salp_robot_trajectory_kernel, dim3(grid), dim3(kRBlock), 0, st, h->P, J);
+  RHIP_TRY(hipGetLastError());
+  if (states) RHIP_TRY(hipMemcpyAsync(states, d_st, sb, hipMemcpyDeviceToHost, st));
+  if (metrics) RHIP_TRY(hipMemcpyAsync(metrics, d_met, mb, hipMemcpyDeviceToHost, st));
+  if (inner_steps) RHIP_TRY(hipMemcpyAsync(inner_steps, d_in, ib, hipMemcpyDeviceToHost, st));
   RHIP_TRY(hipStreamSynchronize(st));
   return 0;
 }

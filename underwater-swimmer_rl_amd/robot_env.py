@@ -35,7 +35,7 @@ HISTORY_CHANNELS = {"position_history": (H_POS, 3), "velocity_history": (H_VEL, 
 
 ROBOT_EXPORTS = ("salp_robot_last_error", "salp_robot_config_default", "salp_robot_vec_create", "salp_robot_vec_destroy",
                  "salp_robot_vec_num_envs", "salp_robot_vec_reset", "salp_robot_vec_step", "salp_robot_vec_get_state",
-                 "salp_robot_vec_history_capacity", "salp_robot_vec_step_history")
+                 "salp_robot_vec_history_capacity", "salp_robot_vec_step_history", "salp_robot_vec_trajectory")
 
 
 class CRobotConfig(ctypes.Structure):
@@ -67,6 +67,7 @@ def _lib():
         L.salp_robot_vec_history_capacity.restype = ctypes.c_int32
         L.salp_robot_vec_step_history.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, ctypes.c_int32, ctypes.c_int32,
                                                   vp, vp, u32, vp]
+        L.salp_robot_vec_trajectory.argtypes = [vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp, u32, vp]
         L._salp_robot_ready = True
     return L
 
