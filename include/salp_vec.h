@@ -132,6 +132,20 @@ enum {
   SALP_I_COUNT
 };
 
+/* Ranges accepted by salp_vec_set_state.  The reference takes any attribute poke; this library packs the breathing integers
+ * into one word and wraps the heading in a bounded loop, so a snapshot must lie where the kernels and the reference agree:
+ *   SALP_F_WATER            in [0, 1] (not NaN).  The reference only ever produces t / inhale_duration and its decay; the
+ *                           literal-constant kernels take ellipse_a for max(ellipse_a, ellipse_b), which holds on [0, 1] only,
+ *                           and a released breath lasts int(exhale_duration * max(water, 0.3)) <= 255 steps only there.
+ *   SALP_F_THETA, _OMEGA    finite, |value| <= SALP_SET_STATE_MAX_ANGLE (100 rad, rad/step).  An unwrapped heading is observed
+ *                           as it is (theta / pi, as snake:392 would) and wrapped to [-pi, pi] by the next step exactly as
+ *                           legacy:329-332 does; fp32 keeps theta / pi and the food bearings to 1e-5 up to this magnitude.
+ *   SALP_I_PHASE 0..2, SALP_I_TIMER 0..255, SALP_I_EXHALE_DUR 0..255, SALP_I_SHAPE_HOLD 0..7   (the packed word's fields).
+ * With host pointers a snapshot outside these ranges is refused as a whole (SALP_ERR_INVALID, the message names the first
+ * offending env; no env is written).  With SALP_DEVICE_PTRS the call is asynchronous and cannot look at the data: the ranges
+ * are then the caller's obligation.  Positions, velocities, the nozzle angle and the counters are taken as given. */
+#define SALP_SET_STATE_MAX_ANGLE 100.0
+
 /* Per-step info columns (int32 [n_envs][SALP_INFO_COLS]); values are those of the step's own
  * (pre-autoreset) episode, as in the info dict of snake:195-200. */
 enum { SALP_INFO_FOOD_COLLECTED = 0, SALP_INFO_STEPS_SINCE_FOOD, SALP_INFO_COLLISION, SALP_INFO_COLS };
@@ -201,7 +215,8 @@ int salp_vec_rollout(salp_vec_t* h, const float* act, int32_t horizon, float* ob
 int salp_vec_observe(salp_vec_t* h, float* obs, uint32_t flags, void* stream);
 
 /* State snapshot (layout above).  f64: double [SALP_F_COUNT(F)][n_envs]; i32: int32
- * [SALP_I_COUNT][n_envs].  set_state ignores the derived ellipse rows. */
+ * [SALP_I_COUNT][n_envs].  set_state ignores the derived ellipse rows and accepts the ranges listed above the info columns
+ * ("Ranges accepted by salp_vec_set_state"). */
 int salp_vec_get_state(salp_vec_t* h, double* f64, int32_t* i32, uint32_t flags, void* stream);
 int salp_vec_set_state(salp_vec_t* h, const double* f64, const int32_t* i32, uint32_t flags,
                        void* stream);
@@ -226,8 +241,13 @@ int64_t salp_vec_global_step(const salp_vec_t* h);
  * generic instantiation), [2] 1 = the reference's constants compiled in as literals, [3] forced breathing, [4] the
  * output signature the kernel was compiled for: 1 = obs, reward, terminated, truncated and nothing else, 2 = those four plus
  * final_obs and / or info, 0 = some of the four is NULL (every store tested; always 0 for the generic instantiation), [5] 1 = actions drawn in the kernel,
- * [6] envs served by the unpredicated launch (whole wavefronts), [7] envs served by the predicated launch. */
+ * [6] envs served by the unpredicated launch (whole wavefronts), [7] envs served by the predicated launch.
+ * [4] is the signature of the kernel that ran: the unpredicated launch's when there was one, else the predicated launch's
+ * (predicated kernels exist for signatures 1 and 0 only: a call with final_obs / info runs them as 0). */
 int salp_vec_last_launch(const salp_vec_t* h, int64_t info[8]);
+/* The output signature of each half of that call: sig[0] the unpredicated launch, sig[1] the predicated launch, -1 for a
+ * half that was not launched (or before any call). */
+int salp_vec_last_launch_signatures(const salp_vec_t* h, int64_t sig[2]);
 /* What that kernel (the unpredicated one when both were launched) holds per workgroup of 256 threads, from the runtime
  * (hipFuncGetAttributes, hipOccupancyMaxActiveBlocksPerMultiprocessor): info[0] registers per thread (VGPRs), [1] static LDS
  * bytes, [2] scratch (spill) bytes per thread, [3] workgroups resident per CU = wavefronts per SIMD.  The design's occupancy

@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+import parity_cases as pc
+from parity_cases import CASES, EXPECT_KERNEL, make_actions, make_cfg   # noqa: F401  (the soak scripts reach them through this module)
 import underwater_swimmer_rl_amd as pkg
 from underwater_swimmer_rl_amd import _capi
 from underwater_swimmer_rl_amd._capi import SalpLib
@@ -77,80 +79,129 @@ def assert_state_parity(cfg, dev, orc, label=""):
     assert d.max() <= STATE_TOL, f"{label}: fp64 state diff {d.max()} in row {np.unravel_index(d.argmax(), d.shape)}"
 
 
-CASES = {
-    "single_food": dict(preset="single_food"),
-    "long_horizon": dict(preset="single_food_long_horizon"),
-    "sac_gail_F12": dict(preset="sac_gail"),
-    "free_breathing": dict(preset="single_food", forced_breathing=False),
-    "no_respawn_F3": dict(preset="sac_gail", num_food_items=3, respawn_food=False),
-    "random_count_F5": dict(preset="sac_gail", num_food_items=5, random_food_count=True),
-    "class_default_F5": dict(preset="sac_gail", num_food_items=5),          # the 8-slot register-food instantiation
-    "F8_all_slots": dict(preset="sac_gail", num_food_items=8, max_steps_without_food=150),
-    # K = 3 with non-default constants: the per-slot-count instantiations that read their constants from the launch parameters
-    "other_tank_F1": dict(preset="single_food", width=900, height=700, tank_margin=40.0),
-    "other_physics_F12": dict(preset="sac_gail", drag_coefficient=0.97, max_thrust_force=120.0, base_radius=26.0,
-                              inhale_duration=100, exhale_duration=130, nozzle_response_rate=0.08),
-    "other_tank_F5_free": dict(preset="sac_gail", num_food_items=5, width=1000, forced_breathing=False, min_food_distance=60.0),
-    "K2_generic": dict(preset="sac_gail", num_food_items=6, max_observed_food=2, proximity_reward_weight=2.0),
-    "K0_no_food_obs": dict(preset="single_food", max_observed_food=0),
-    "F0_empty": dict(preset="single_food", num_food_items=0),
-    "short_timeout": dict(preset="single_food", max_steps_without_food=40),
-    # the unpredicated (main-launch) forms of the instantiations that only ran predicated before round 3:
-    "F16_sixteen_slots": dict(preset="sac_gail", num_food_items=16, max_steps_without_food=200),        # <16, 3, STD>
-    "F16_sixteen_slots_other_tank": dict(preset="sac_gail", num_food_items=16, width=900, height=650),  # <16, 3, !STD>
-    "F14_K5_generic_lds": dict(preset="sac_gail", num_food_items=14, max_observed_food=5),              # <16, 8>: generic, foods in LDS
-    "F9_K5_generic_reg": dict(preset="sac_gail", num_food_items=9, max_observed_food=5),                # <12, 8>: generic, foods in VGPRs
-    "F3_other_tank": dict(preset="sac_gail", num_food_items=3, width=900, tank_margin=40.0),            # <4, 3, !STD>
-}
-# (food slots, observed capacity, literal constants) of the kernel each case must run (salp_vec_last_launch)
-EXPECT_KERNEL = {
-    "single_food": (1, 3, 1), "sac_gail_F12": (12, 3, 1), "class_default_F5": (8, 3, 1), "no_respawn_F3": (4, 3, 1),
-    "other_tank_F1": (1, 3, 0), "other_physics_F12": (12, 3, 0), "K2_generic": (12, 8, 0),
-    "F16_sixteen_slots": (16, 3, 1), "F16_sixteen_slots_other_tank": (16, 3, 0), "F14_K5_generic_lds": (16, 8, 0),
-    "F9_K5_generic_reg": (12, 8, 0), "F3_other_tank": (4, 3, 0),
-}
+def start_pair(cfg, n, seed, **kw):
+    """Device and oracle in the shared injected start state (tests/parity_cases.py), set through set_state on both."""
+    orc, f64, i32 = pc.start_oracle(cfg, n, seed, **kw)
+    dev = SalpLib(cfg, n, device_id=0, seed=seed)
+    dev.set_state(f64, i32, 0)
+    return dev, orc
 
 
-def make_cfg(spec):
-    spec = dict(spec)
-    return pkg.load_env_config(spec.pop("preset"), **spec)
-
-
-def make_actions(cfg, H, n, seed, scale=1.0):
-    rng = np.random.default_rng(seed)
-    act = rng.uniform(-scale, scale, size=(H, n, cfg.act_dim)).astype(np.float32)
-    if not cfg.forced_breathing:  # inhale control in [0,1], held for random stretches
-        hold = rng.uniform(0, 1, size=(H // 16 + 1, n)).repeat(16, axis=0)[:H]
-        act[..., 0] = hold.astype(np.float32)
-    return act
+def assert_final_obs(cfg, got_fin, ref, label=""):
+    """Terminal observations are delivered for finished envs, and only for them, with the oracle's values."""
+    done = (ref["terminated"] | ref["truncated"]).astype(bool)
+    assert done.any(), f"{label}: no episode ends: the terminal branch is not tested"
+    assert np.array_equal(np.isnan(got_fin[..., 0]), ~done), f"{label}: final_obs rows written do not match the finished envs"
+    d = obs_diff(cfg, got_fin[done], ref["final_obs"][done])
+    assert d.max() <= OBS_TOL, f"{label}: final_obs diff {d.max()}"
+    return float(d.max())
 
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_rollout_parity(name):
-    cfg = make_cfg(CASES[name])
-    n, H, seed = 2048, 384, 11
-    act = make_actions(cfg, H, n, seed=3)
-    got, dev = run_device(cfg, n, act, seed=seed, want_final=True)
-    orc = ol.OracleVec(cfg, n, seed=seed)
+    """Every case ends episodes in mixed wavefronts, by wall contact and by truncation (and captures food where it has any):
+    the start state of tests/parity_cases.py, injected into device and oracle alike.  The event counts are taken from the
+    ORACLE's output and held above floors (also on the CPU: tests/test_parity_recipe.py), so the terminal branch of the
+    kernel the case names — autoreset, final_obs store, post-reset observation — is always compared."""
+    cfg = pc.case_cfg(name)
+    n, H, seed = pc.N_ENVS, pc.HORIZON, pc.ENV_SEED
+    act = make_actions(cfg, H, n, seed=pc.ACTION_SEED)
+    dev, orc = start_pair(cfg, n, seed)
+    assert_state_parity(cfg, dev, orc, f"{name}: start state")
+    got, _ = run_device(cfg, n, act, want_final=True, dev=dev)
     ref = orc.rollout(act, want_final=True)
+    ev = pc.count_events(ref)
+    pc.assert_event_floors(name, ev)
     dmax, rmax = assert_parity(cfg, got, ref, name)
-    # terminal observations are delivered for finished envs only
+    fmax = assert_final_obs(cfg, got["final_obs"], ref, name)
     done = (ref["terminated"] | ref["truncated"]).astype(bool)
-    assert np.array_equal(np.isnan(got["final_obs"][..., 0]), ~done)
-    if done.any():
-        assert obs_diff(cfg, got["final_obs"][done], ref["final_obs"][done]).max() <= OBS_TOL
     assert_state_parity(cfg, dev, orc, name)
+    if name == "no_respawn_F3":     # lanes that run with fewer live foods than K, and terminations by completion
+        assert pc.steps_left_short_of_foods(cfg, ref) >= pc.NO_RESPAWN_SHORT_STEPS_FLOOR
+        assert (ref["terminated"].astype(bool) & (ref["info"][..., pc.INFO_COLLISION] == 0)).sum() > 0
     st = dev.stats()
     assert st["env_steps"] == n * H
     assert st["episodes"] == int(done.sum())
     assert st["terminated"] == int(ref["terminated"].sum()) and st["truncated"] == int(ref["truncated"].sum())
+    assert st["collisions"] == int(ref["info"][..., pc.INFO_COLLISION].sum()) and st["food_collected"] == ev["captures"]
     ll = dev.last_launch()      # 2048 envs = 32 whole wavefronts: the unpredicated kernel, non-FULL signature (final_obs)
     assert ll["envs_unpredicated"] == n and ll["envs_predicated"] == 0
     assert ll["full_signature"] == (2 if ll["observed_capacity"] == 3 else 0)    # main outputs + final_obs + info
-    if name in EXPECT_KERNEL:
-        assert (ll["food_slots"], ll["observed_capacity"], ll["literal_constants"]) == EXPECT_KERNEL[name], ll
-    print(f"{name}: max obs diff {dmax:.3g}, max rel reward diff {rmax:.3g}, episodes {st['episodes']}, kernel {ll}")
+    assert (ll["signature_unpredicated"], ll["signature_predicated"]) == (ll["full_signature"], -1)
+    assert (ll["food_slots"], ll["observed_capacity"], ll["literal_constants"]) == EXPECT_KERNEL[name], ll
+    print(f"{name}: max obs diff {dmax:.3g}, final_obs {fmax:.3g}, max rel reward diff {rmax:.3g}, episodes {st['episodes']}, "
+          f"wall terminations {ev['wall']}, truncations {ev['truncated']}, captures {ev['captures']}, mixed wavefront-steps "
+          f"{ev['mixed_wave_steps']}, kernel {EXPECT_KERNEL[name]} signature {ll['full_signature']}")
     dev.close()
+    orc.close()
+
+
+@pytest.mark.parametrize("name", list(pc.STEP_CASES))
+def test_step_acting_path_matches_oracle(name):
+    """salp_vec_step with every output (final_obs and info included) — what SAC's acting loop calls — on 64 whole wavefronts
+    of sac_gail, and its ragged twin (4096 + 37 envs: a step call of that size runs ONE predicated launch, which exists for
+    the every-store-tested signature only).  Every step's observation, reward, flags, info and the final_obs rows of the
+    finished envs against the oracle, then the state; wall terminations, truncations and captures all occur (floors on the
+    oracle's output, also in tests/test_parity_recipe.py); last_launch names the kernel after every step."""
+    cfg, orc, f64, i32, act = pc.step_case(name)
+    H, n = act.shape[:2]
+    ref = orc.rollout(act, want_final=True)
+    pc.assert_step_floors(name, pc.count_events(ref))
+    dev = SalpLib(cfg, n, device_id=0, seed=pc.STEP_ENV_SEED)
+    dev.set_state(f64, i32, 0)
+    obs = np.empty((n, cfg.obs_dim), np.float32)
+    rew = np.empty(n, np.float32)
+    term = np.empty(n, np.uint8)
+    trunc = np.empty(n, np.uint8)
+    info = np.empty((n, 3), np.int32)
+    fin = np.empty((n, cfg.obs_dim), np.float32)
+    ragged = n % 64 != 0
+    want = (dict(envs_unpredicated=0, envs_predicated=n, full_signature=0, signature_unpredicated=-1, signature_predicated=0)
+            if ragged else
+            dict(envs_unpredicated=n, envs_predicated=0, full_signature=2, signature_unpredicated=2, signature_predicated=-1))
+    dmax = rmax = fmax = 0.0
+    for t in range(H):
+        fin.fill(np.nan)
+        dev.step(act[t], obs, rew, term, trunc, fin, info, 0)
+        assert np.array_equal(term, ref["terminated"][t]) and np.array_equal(trunc, ref["truncated"][t]), f"flags differ at step {t}"
+        assert np.array_equal(info, ref["info"][t]), f"info differs at step {t}"
+        dmax = max(dmax, float(obs_diff(cfg, obs, ref["obs"][t]).max()))
+        r64 = ref["reward64"][t]
+        rmax = max(rmax, float((np.abs(rew - r64) / np.maximum(1.0, np.abs(r64))).max()))
+        done = (term | trunc).astype(bool)
+        assert np.array_equal(np.isnan(fin[:, 0]), ~done), f"final_obs rows at step {t}"
+        if done.any():
+            fmax = max(fmax, float(obs_diff(cfg, fin[done], ref["final_obs"][t][done]).max()))
+        assert dmax <= OBS_TOL and rmax <= REW_TOL and fmax <= OBS_TOL, f"step {t}: obs {dmax}, reward {rmax}, final_obs {fmax}"
+        ll = dev.last_launch()
+        assert (ll["food_slots"], ll["observed_capacity"], ll["literal_constants"]) == (12, 3, 1)
+        assert {k: ll[k] for k in want} == want, ll
+    assert_state_parity(cfg, dev, orc, f"step path {name}")
+    print(f"step path {name}: max obs diff {dmax:.3g}, final_obs {fmax:.3g}, reward {rmax:.3g}, {pc.count_events(ref)}")
+    dev.close()
+    orc.close()
+
+
+def test_split_launch_with_final_obs_matches_oracle():
+    """One rollout call split into the unpredicated launch (64 whole wavefronts, terminal-observation signature) and the
+    predicated launch over the last 37 envs (every store tested): n H > 2^22 env-steps, with the injected start state, so both
+    halves end episodes.  last_launch reports each half's own signature."""
+    cfg = pkg.load_env_config("sac_gail", max_steps_without_food=300)
+    n, H, seed = 4096 + 37, 1020, 13
+    dev, orc = start_pair(cfg, n, seed, threads=4)
+    act = make_actions(cfg, H, n, seed=14)
+    got, _ = run_device(cfg, n, act, want_final=True, dev=dev)
+    ref = orc.rollout(act, want_final=True)
+    ev_tail = pc.count_events({k: ref[k][:, 4096:] for k in ("terminated", "truncated", "info")})     # the predicated half
+    assert ev_tail["wall"] > 0 and ev_tail["truncated"] > 0 and ev_tail["captures"] > 0, ev_tail
+    assert_parity(cfg, got, ref, "split launch")
+    assert_final_obs(cfg, got["final_obs"], ref, "split launch")
+    assert_state_parity(cfg, dev, orc, "split launch")
+    ll = dev.last_launch()
+    assert (ll["envs_unpredicated"], ll["envs_predicated"]) == (4096, 37), ll
+    assert (ll["full_signature"], ll["signature_unpredicated"], ll["signature_predicated"]) == (2, 2, 0), ll
+    dev.close()
+    orc.close()
 
 
 @pytest.mark.parametrize("foods,slots", [(3, 4), (5, 8), (12, 12), (16, 16)])
@@ -216,6 +267,11 @@ def test_step_equals_rollout_and_info():
         assert np.array_equal(obs, got["obs"][t]) and np.array_equal(rew, got["reward"][t])
         assert np.array_equal(term, got["terminated"][t]) and np.array_equal(trunc, got["truncated"][t])
         assert np.array_equal(info, ref["info"][t]), f"info differs at step {t}"
+    # 777 envs: one predicated launch each; the rollout ran the main-only kernel, the step (info) the every-store-tested one
+    lr, ls = dev_r.last_launch(), dev_s.last_launch()
+    assert (lr["envs_unpredicated"], lr["envs_predicated"], ls["envs_unpredicated"], ls["envs_predicated"]) == (0, n, 0, n)
+    assert (lr["full_signature"], lr["signature_unpredicated"], lr["signature_predicated"]) == (1, -1, 1), lr
+    assert (ls["full_signature"], ls["signature_unpredicated"], ls["signature_predicated"]) == (0, -1, 0), ls
     dev_r.close()
     dev_s.close()
 
@@ -291,6 +347,256 @@ def test_set_state_injection_eval_style():
     assert_parity(cfg, got, ref, "injected")
     assert_state_parity(cfg, dev, orc, "injected")
     dev.close()
+
+
+# ---- injected-state edges: snapshots the reference's attribute pokes can produce and a plain reset never does -----------
+# Each runs a literal-constant kernel and one that reads its constants (they differ exactly here), on four whole wavefronts,
+# with the injected lanes mixed among untouched ones.  Either the device matches the oracle within the contract or
+# salp_vec_set_state refuses the snapshot (include/salp_vec.h, "Ranges accepted by salp_vec_set_state").
+EDGE_N = 256
+
+
+def edge_pair(cfg, seed, edit, n=EDGE_N):
+    """Device and oracle after `edit(f64, i32)` on the post-reset snapshot.  The oracle takes the ellipse rows as given
+    (salp_oracle.c set_state) while the device derives them, so an edit that changes water or the breathing integers also
+    writes the ellipse the reference's formulas (legacy:184-259) give for that state."""
+    dev = SalpLib(cfg, n, device_id=0, seed=seed)
+    orc = ol.OracleVec(cfg, n, seed=seed)
+    f64, i32 = orc.get_state()
+    edit(f64, i32)
+    dev.set_state(f64, i32, 0)
+    orc.set_state(f64, i32)
+    return dev, orc
+
+
+def compare_edge(cfg, dev, orc, act, label, kernel):
+    n = dev.n_envs
+    obs = np.empty((n, cfg.obs_dim), np.float32)
+    dev.observe(obs, 0)
+    d0 = obs_diff(cfg, obs, orc.observe())
+    assert d0.max() <= OBS_TOL, f"{label}: observe() diff {d0.max()} at {np.unravel_index(d0.argmax(), d0.shape)}"
+    got, _ = run_device(cfg, n, act, want_final=True, dev=dev)
+    ref = orc.rollout(act, want_final=True)
+    assert_parity(cfg, got, ref, label)
+    done = (ref["terminated"] | ref["truncated"]).astype(bool)
+    assert np.array_equal(np.isnan(got["final_obs"][..., 0]), ~done)
+    if done.any():
+        assert obs_diff(cfg, got["final_obs"][done], ref["final_obs"][done]).max() <= OBS_TOL, f"{label}: final_obs"
+    assert_state_parity(cfg, dev, orc, label)
+    ll = dev.last_launch()
+    assert (ll["food_slots"], ll["observed_capacity"], ll["literal_constants"]) == kernel and ll["envs_predicated"] == 0, ll
+    return got, ref
+
+
+def refused(dev, f64, i32, word):
+    """set_state refuses the snapshot with SALP_ERR_INVALID and a message naming the quantity; nothing is written."""
+    before = get_state(dev, dev.cfg)
+    with pytest.raises(_capi.SalpError, match=word) as e:
+        dev.set_state(f64, i32, 0)
+    assert "(-1)" in str(e.value)
+    after = get_state(dev, dev.cfg)
+    assert np.array_equal(before[0], after[0], equal_nan=True) and np.array_equal(before[1], after[1])
+
+
+WATER_CONFIGS = {      # forced and free breathing, each with literal constants and with constants read at run time
+    "literal_forced": (dict(preset="single_food"), (1, 3, 1)),
+    "literal_free_F12": (dict(preset="sac_gail", forced_breathing=False), (12, 3, 1)),
+    "runtime_forced_F3": (dict(preset="sac_gail", num_food_items=3, width=900, tank_margin=40.0), (4, 3, 0)),
+    # exhale_duration = 250: the longest released breath, int(250 max(water, 0.3)), must still fit the packed word's 8 bits
+    "runtime_free_exhale250": (dict(preset="single_food", forced_breathing=False, exhale_duration=250, base_radius=26.0), (1, 3, 0)),
+}
+
+
+@pytest.mark.parametrize("name", list(WATER_CONFIGS))
+def test_injected_water_level_in_range_matches_oracle(name):
+    """`env.water_volume = w; env.breathing_phase = 'inhaling'; env.breathing_timer = t` (legacy:184-259) with w anywhere in
+    [0, 1], not only the t / inhale_duration a run produces: timer at and below inhale_duration, so forced breathing releases on
+    the first step and free breathing releases where the action says so.  The released breath's ellipse comes from w; the
+    swimmer starts inside the wall's reach moving into it, so the radius of that very step decides the clamped position
+    (terminal observation, columns 0 and 6)."""
+    spec, kernel = WATER_CONFIGS[name]
+    cfg = make_cfg(spec)
+    rng = np.random.default_rng(31)
+    lanes = np.nonzero(np.arange(EDGE_N) % 3 == 0)[0]
+    water = rng.choice([0.0, 0.04, 0.05, 0.050000000000000044, 0.3, 0.62, 1.0 - 2.0 ** -53, 1.0], lanes.size)
+    timer = rng.choice([cfg.inhale_duration, cfg.inhale_duration - 1, cfg.inhale_duration // 2, 3], lanes.size)
+    R = cfg.base_radius
+
+    def edit(f64, i32):
+        i32[ol.I_PHASE, lanes], i32[ol.I_TIMER, lanes], i32[ol.I_SHAPE_HOLD, lanes] = 1, timer, 0
+        f64[ol.F_WATER, lanes] = water
+        f64[ol.F_ELLIPSE_A, lanes] = R * 1.3 + (R * 1.1 - R * 1.3) * water       # legacy:212-213 at progress = water
+        f64[ol.F_ELLIPSE_B, lanes] = R * 0.8 + (R * 1.1 - R * 0.8) * water
+        f64[ol.F_X, lanes], f64[ol.F_VX, lanes] = cfg.tank_margin + R, -1.0        # nearer than any radius: clamped to margin + r
+
+    dev, orc = edge_pair(cfg, 3, edit)
+    act = make_actions(cfg, 40, EDGE_N, seed=32)
+    if not cfg.forced_breathing:       # half of the injected lanes release at once, the others keep inhaling for a while
+        act[:6, lanes[::2], 0] = 0.0
+        act[:6, lanes[1::2], 0] = 1.0
+    got, ref = compare_edge(cfg, dev, orc, act, f"water {name}", kernel)
+    # the wall was met on that very step (x is clamped to margin + r; `x - r <= margin` can miss by a rounding, snake:219-230)
+    assert (ref["terminated"][0, lanes] & ref["info"][0, lanes, pc.INFO_COLLISION]).mean() > 0.5
+    dev.close()
+    orc.close()
+
+
+@pytest.mark.parametrize("name", ["literal_forced", "runtime_free_exhale250"])
+@pytest.mark.parametrize("water", [1.0 + 1e-9, 1.2, 2.5, -0.1, float("nan")])
+def test_injected_water_level_out_of_range_is_refused(name, water):
+    """`env.water_volume = 1.2` and the like.  The reference would go on (2.5 at exhale_duration 150 gives a 375-step breath,
+    ellipse_b > ellipse_a for one step); the packed breathing word keeps 8 bits of the length and the literal-constant
+    kernels take ellipse_a for the radius, so set_state refuses a level outside [0, 1] instead of diverging."""
+    cfg = make_cfg(WATER_CONFIGS[name][0])
+    dev = SalpLib(cfg, EDGE_N, device_id=0, seed=3)
+    f64, i32 = get_state(dev, cfg)
+    i32[_capi.I_PHASE, 70], i32[_capi.I_TIMER, 70], i32[_capi.I_SHAPE_HOLD, 70] = 1, 60, 0
+    f64[_capi.F_WATER, 70] = water
+    refused(dev, f64, i32, "water")
+    f64[_capi.F_WATER, 70] = 1.0           # the same snapshot with the level in range is taken
+    dev.set_state(f64, i32, 0)
+    assert get_state(dev, cfg)[0][_capi.F_WATER, 70] == 1.0
+    dev.close()
+
+
+def test_breathing_integers_out_of_range_are_refused():
+    """The packed breathing word keeps 2 + 8 + 8 + 3 bits: values beyond them were silently truncated."""
+    cfg = pkg.load_env_config("single_food")
+    dev = SalpLib(cfg, EDGE_N, device_id=0, seed=3)
+    for row, bad in ((_capi.I_EXHALE_DUR, 375), (_capi.I_TIMER, 256), (_capi.I_PHASE, 3), (_capi.I_SHAPE_HOLD, 8), (_capi.I_TIMER, -1)):
+        f64, i32 = get_state(dev, cfg)
+        i32[row, 129] = bad
+        refused(dev, f64, i32, "exhale duration")
+    dev.close()
+
+
+HEADING_CONFIGS = {
+    "literal_F1": (dict(preset="single_food"), (1, 3, 1)),
+    "runtime_F1": (dict(preset="single_food", width=900, height=700, tank_margin=40.0), (1, 3, 0)),
+    "literal_F12": (dict(preset="sac_gail", proximity_reward_weight=1.0), (12, 3, 1)),
+    "runtime_F16": (dict(preset="sac_gail", num_food_items=16, width=900, height=650), (16, 3, 0)),
+    "generic_F9_K5": (dict(preset="sac_gail", num_food_items=9, max_observed_food=5), (12, 8, 0)),
+}
+
+
+@pytest.mark.parametrize("name", list(HEADING_CONFIGS))
+def test_injected_heading_far_outside_the_circle_matches_oracle(name):
+    """`env.robot_angle = 70.0` (eval/collect_navigation_data.py:80 pokes the heading; nothing keeps it in [-pi, pi]), with and
+    without angular velocity.  observe() before any step reports theta / pi unwrapped, as the reference would; the first step
+    wraps it by repeated subtraction (legacy:329-332) — up to 16 turns here, where the kernels used to stop after 9 and
+    leave the heading outside the circle."""
+    spec, kernel = HEADING_CONFIGS[name]
+    cfg = make_cfg(spec)
+    rng = np.random.default_rng(41)
+    lanes = np.nonzero(np.arange(EDGE_N) % 3 == 1)[0]
+    theta = rng.choice([3.5, -3.5, 20.0, -20.0, 57.0, -57.0, 70.0, -70.0, 100.0, -100.0], lanes.size)
+    omega = rng.choice([0.0, 0.0, 0.3, -0.3, 2.0, -7.0], lanes.size)
+
+    def edit(f64, i32):
+        f64[ol.F_THETA, lanes], f64[ol.F_OMEGA, lanes] = theta, omega
+
+    dev, orc = edge_pair(cfg, 5, edit)
+    compare_edge(cfg, dev, orc, make_actions(cfg, 30, EDGE_N, seed=42), f"heading {name}", kernel)
+    f_end, _ = orc.get_state()
+    assert np.abs(f_end[ol.F_THETA]).max() <= np.pi
+    dev.close()
+    orc.close()
+
+
+@pytest.mark.parametrize("row,value", [(_capi.F_THETA, 1e3), (_capi.F_THETA, -1e3), (_capi.F_THETA, 100.001), (_capi.F_OMEGA, -250.0),
+                                       (_capi.F_THETA, float("inf")), (_capi.F_OMEGA, float("nan"))])
+def test_injected_heading_beyond_the_documented_range_is_refused(row, value):
+    """theta = 1e3 is 318.3 in the observation, where fp32 no longer resolves 1e-5, and 159 turns of the wrapping loop: refused
+    (|theta|, |omega| <= SALP_SET_STATE_MAX_ANGLE = 100)."""
+    cfg = pkg.load_env_config("single_food")
+    dev = SalpLib(cfg, EDGE_N, device_id=0, seed=5)
+    f64, i32 = get_state(dev, cfg)
+    f64[row, 200] = value
+    refused(dev, f64, i32, "theta")
+    dev.close()
+
+
+NEAR_FOOD_CONFIGS = {
+    "literal_F12": (dict(preset="sac_gail", proximity_reward_weight=5.0), (12, 3, 1)),
+    "runtime_F12": (dict(preset="sac_gail", proximity_reward_weight=5.0, width=900), (12, 3, 0)),
+    "literal_F8": (dict(preset="sac_gail", num_food_items=8, proximity_reward_weight=5.0), (8, 3, 1)),
+    "literal_F16": (dict(preset="sac_gail", num_food_items=16, proximity_reward_weight=5.0), (16, 3, 1)),
+    "generic_F9_K5": (dict(preset="sac_gail", num_food_items=9, max_observed_food=5, proximity_reward_weight=5.0), (12, 8, 0)),
+    "generic_F14_K5": (dict(preset="sac_gail", num_food_items=14, max_observed_food=5, proximity_reward_weight=5.0), (16, 8, 0)),
+}
+
+
+@pytest.mark.parametrize("name", list(NEAR_FOOD_CONFIGS))
+def test_several_foods_next_to_the_swimmer_keep_every_observed_entry(name):
+    """`env.food_positions[k] = robot_pos + tiny` for three and four slots (the fallback placement of snake:120-131 can do the
+    same to two).  The capture loop takes the lowest slot inside the radius, one per step, so after the first step two (lanes
+    0 mod 3) or three (lanes 1 mod 3) foods within 2 px are alive in the SAME observation: entries 0, 1 and 2 each need offsets
+    from the exact positions — with fp32 positions (roundings of ~3e-5 px) a bearing at 0.45 px is off by up to ~1e-4 rad."""
+    spec, kernel = NEAR_FOOD_CONFIGS[name]
+    cfg = make_cfg(spec)
+    F = cfg.num_food_items
+    rng = np.random.default_rng(51)
+    idx = np.arange(EDGE_N)
+    variants = ((idx % 3 == 0, ((2, 1.8), (5, 0.3), (7, 0.45))),                 # slot 2 goes first: 0.3 and 0.45 px stay
+                (idx % 3 == 1, ((1, 2.0), (2, 0.6), (5, 0.3), (7, 0.45))))      # slot 1 goes first: three stay
+
+    def edit(f64, i32):
+        for mask, foods in variants:
+            m = np.nonzero(mask)[0]
+            f64[ol.F_X, m] += rng.uniform(-30.0, 30.0, m.size)      # off the tank centre, which fp32 holds exactly
+            f64[ol.F_Y, m] += rng.uniform(-30.0, 30.0, m.size)
+            for slot, d in foods:
+                ang = rng.uniform(-np.pi, np.pi, m.size)
+                f64[ol.F_FOOD0 + slot, m] = f64[ol.F_X, m] + d * np.cos(ang)
+                f64[ol.F_FOOD0 + F + slot, m] = f64[ol.F_Y, m] + d * np.sin(ang)
+
+    dev, orc = edge_pair(cfg, 21, edit)
+    act = np.zeros((5, EDGE_N, cfg.act_dim), np.float32)
+    got, ref = compare_edge(cfg, dev, orc, act, f"near foods {name}", kernel)
+    # the state the case is about was reached: after step 0 entries 0 and 1 (and 2) are within 2 px (distance / diagonal)
+    diag = float(np.hypot(cfg.width, cfg.height))
+    two, three = variants[0][0], variants[1][0]
+    assert (ref["obs"][0, two][:, 10 + 4 * 1 + 2] * diag < 2.0).all() and (ref["obs"][0, three][:, 10 + 4 * 2 + 2] * diag < 2.05).all()
+    assert (ref["info"][:3, two | three, pc.INFO_STEPS_SINCE_FOOD] == 0).all()      # a capture on each of the first three steps
+    d = obs_diff(cfg, got["obs"], ref["obs"])
+    for e in range(3):      # entries 0, 1, 2 and the reward, spelled out (compare_edge has asserted the whole row already)
+        assert d[..., 10 + 4 * e: 14 + 4 * e].max() <= OBS_TOL, f"near foods {name}: entry {e} diff {d[..., 10 + 4 * e: 14 + 4 * e].max()}"
+    rd = np.abs(got["reward"] - ref["reward64"]) / np.maximum(1.0, np.abs(ref["reward64"]))
+    assert rd.max() <= REW_TOL, f"near foods {name}: reward diff {rd.max()}"
+    dev.close()
+    orc.close()
+
+
+FEW_FOOD_CONFIGS = {       # (spec, kernel, live foods kept in the injected lanes; None = the config itself has fewer than K)
+    "F2_K3_literal": (dict(preset="sac_gail", num_food_items=2, respawn_food=False), (4, 3, 1), None),
+    "F2_K3_runtime": (dict(preset="sac_gail", num_food_items=2, respawn_food=False, width=900), (4, 3, 0), None),
+    "F5_two_live_literal": (dict(preset="sac_gail", num_food_items=5, respawn_food=False), (8, 3, 1), 2),
+    "F5_two_live_runtime": (dict(preset="sac_gail", num_food_items=5, respawn_food=False, tank_margin=40.0), (8, 3, 0), 2),
+    "F12_one_live_literal": (dict(preset="sac_gail", num_food_items=12, respawn_food=False), (12, 3, 1), 1),
+    "F12_one_live_runtime": (dict(preset="sac_gail", num_food_items=12, respawn_food=False, base_radius=28.0), (12, 3, 0), 1),
+}
+
+
+@pytest.mark.parametrize("name", list(FEW_FOOD_CONFIGS))
+def test_fewer_live_foods_than_observed_entries_from_the_first_step(name):
+    """`env.food_positions[k] = None` (snake:215) for all but one or two slots, nothing respawning: the selection has missing
+    entries (index -1, padded observation) on every one of 400 steps, in lanes next to lanes with a full set."""
+    spec, kernel, keep = FEW_FOOD_CONFIGS[name]
+    cfg = make_cfg(spec)
+    F = cfg.num_food_items
+    lanes = np.nonzero(np.arange(EDGE_N) % 2 == 0)[0]
+
+    def edit(f64, i32):
+        if keep is not None:       # the survivors sit in the LAST slots: every lower slot is empty
+            f64[ol.F_FOOD0: ol.F_FOOD0 + F - keep, lanes] = np.nan
+            f64[ol.F_FOOD0 + F: ol.F_FOOD0 + 2 * F - keep, lanes] = np.nan
+
+    dev, orc = edge_pair(cfg, 61, edit)
+    got, ref = compare_edge(cfg, dev, orc, make_actions(cfg, 400, EDGE_N, seed=62), f"few foods {name}", kernel)
+    short = (ref["obs"][..., 10 + 4 * 2 + 2] == 1.0) & (ref["obs"][..., 10 + 4 * 2] == 0.0)      # third entry padded (snake:412)
+    assert short[:, lanes].mean() > 0.9, short[:, lanes].mean()
+    dev.close()
+    orc.close()
 
 
 def test_out_of_range_and_nan_actions():

@@ -28,7 +28,7 @@ EXPORTS = (
     "salp_vec_num_food", "salp_vec_device", "salp_vec_reset", "salp_vec_step", "salp_vec_rollout",
     "salp_vec_observe", "salp_vec_get_state", "salp_vec_set_state", "salp_vec_get_stats",
     "salp_vec_clear_stats", "salp_vec_global_step", "salp_vec_set_base_num_food", "salp_vec_base_num_food",
-    "salp_vec_reseed", "salp_vec_last_launch", "salp_vec_last_kernel_resources",
+    "salp_vec_reseed", "salp_vec_last_launch", "salp_vec_last_kernel_resources", "salp_vec_last_launch_signatures",
 )
 
 
@@ -90,6 +90,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     L.salp_vec_clear_stats.argtypes = [vp]
     if path is None or hasattr(L, "salp_vec_last_launch"):
         L.salp_vec_last_launch.argtypes = [vp, ctypes.POINTER(ctypes.c_int64)]
+    if path is None or hasattr(L, "salp_vec_last_launch_signatures"):
+        L.salp_vec_last_launch_signatures.argtypes = [vp, ctypes.POINTER(ctypes.c_int64)]
     if path is None or hasattr(L, "salp_vec_last_kernel_resources"):
         L.salp_vec_last_kernel_resources.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
     if path is None or hasattr(L, "salp_vec_reseed"):   # (an explicit path may be an older A/B variant, profiles/ab_bench.py)
@@ -190,12 +192,19 @@ class SalpLib:
 
     def last_launch(self) -> dict:
         """The kernel instantiation of the most recent step / rollout call (salp_vec_last_launch).  `full_signature`: 1 = the four
-        main outputs only, 2 = the four plus final_obs / info, 0 = some main output absent."""
+        main outputs only, 2 = the four plus final_obs / info, 0 = every store tested (some main output absent, the generic
+        instantiation, or a predicated launch asked for final_obs / info) — of the kernel that ran: the unpredicated launch's
+        when there was one, else the predicated launch's.  `signature_unpredicated` / `signature_predicated`: each half's own,
+        -1 for a half that was not launched (salp_vec_last_launch_signatures)."""
         a = (ctypes.c_int64 * 8)()
         check(self.lib, self.lib.salp_vec_last_launch(self._h, a), "salp_vec_last_launch")
         keys = ("food_slots", "observed_capacity", "literal_constants", "forced", "full_signature", "actions_in_kernel",
                 "envs_unpredicated", "envs_predicated")
-        return dict(zip(keys, (int(v) for v in a)))
+        out = dict(zip(keys, (int(v) for v in a)))
+        b = (ctypes.c_int64 * 2)()
+        check(self.lib, self.lib.salp_vec_last_launch_signatures(self._h, b), "salp_vec_last_launch_signatures")
+        out["signature_unpredicated"], out["signature_predicated"] = int(b[0]), int(b[1])
+        return out
 
     def last_kernel_resources(self) -> dict:
         """Registers, LDS, scratch and resident workgroups per CU of the most recent call's kernel (salp_vec_last_kernel_resources)."""

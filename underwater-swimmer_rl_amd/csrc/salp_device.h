@@ -749,8 +749,10 @@ __device__ __forceinline__ double step_head(EnvCore& e, const DevParams& P, uint
   // max(ellipse_a, ellipse_b) is ellipse_a whenever both come from the formulas above with the reference's radii:
   // a - b = R (0.5 - 0.5 p) inhaling, R 0.5 p exhaling, 0.5 R at rest, all >= 0 and exact in fp64 for R = 30 (a and b
   // are multiples of 2^-46 below 64: every product and sum above is exact or rounds both the same way is NOT assumed —
-  // checked for every (phase, timer, duration) of the literal constants by tests/test_source_claims.py).  Other radii
-  // keep the maximum.
+  // checked for every (phase, timer, duration) of the literal constants by tests/test_source_claims.py).  In the release
+  // branch a and b come from the state's water level w itself, whatever put it there: fl(-6 w) >= -6 and fl(9 w) <= 9 for
+  // w in [0, 1] and rounding is monotonic, so a >= 33 >= b — salp_vec_set_state refuses a water level outside [0, 1].
+  // Other radii keep the maximum.
   const double r = STD ? a : pymax(a, b);
 #ifdef SALP_EXP_NO_THRUST      // experiment build (profiles/ab_bench.py): price of the thrust block
   thrust = false;
@@ -764,16 +766,18 @@ __device__ __forceinline__ double step_head(EnvCore& e, const DevParams& P, uint
   e.vx = e.vx * CV(drag); e.vy = e.vy * CV(drag); e.om = e.om * CV(ang_drag);
   e.x = e.x + e.vx; e.y = e.y + e.vy; e.th = e.th + e.om;
   // legacy:329-332 `while theta > pi: theta -= 2 pi` / `while theta < -pi: ...`.  |omega| is far below
-  // 2 pi, so one conditional step each is the common case; the (bounded) loops only run if a lane
-  // is still outside, e.g. after an injected state.
+  // 2 pi, so one conditional step each is the common case; the loops only run if a lane is still outside,
+  // after an injected state.  They subtract as the reference does (same roundings) and are bounded so that no state
+  // can hang a wavefront: salp_vec_set_state admits |theta|, |omega| <= 100 (include/salp_vec.h), so |theta + omega|
+  // <= 200 + pi needs at most 33 turns.
   const double pi = SALP_PI, twopi = SALP_2PI;
   if (e.th > pi) e.th -= twopi;
   if (e.th < -pi) e.th += twopi;
   if (__any(e.th > pi || e.th < -pi)) {
 #pragma unroll 1
-    for (int it = 0; it < 8 && e.th > pi; ++it) e.th -= twopi;
+    for (int it = 0; it < 64 && e.th > pi; ++it) e.th -= twopi;
 #pragma unroll 1
-    for (int it = 0; it < 8 && e.th < -pi; ++it) e.th += twopi;
+    for (int it = 0; it < 64 && e.th < -pi; ++it) e.th += twopi;
   }
   {
     const double m = CV(margin) + r;

@@ -275,7 +275,7 @@ __device__ __forceinline__ void resolve_f32(const MirrorLds& m, int K, float xf,
     q.bx[s] = 0.f; q.by[s] = 0.f; q.bd[s] = 0.f;
     if (s < K) {
       const bool found = ALLFOUND || (q.idx[s] >= 0);
-      const float2 p = m.get(ALLFOUND ? q.idx[s] : (q.idx[s] & 15));
+      const float2 p = m.get(ALLFOUND ? q.idx[s] : (q.idx[s] < 0 ? 0 : q.idx[s]));   // a missing entry (-1) reads slot 0, discarded
       const float bx = p.x - xf, by = p.y - yf;
       const float bd = __builtin_amdgcn_sqrtf(fmaf(by, by, bx * bx));
       q.bx[s] = found ? bx : 0.f;
@@ -294,21 +294,33 @@ __device__ __forceinline__ void resolve_f32(const MirrorLds& m, int K, float xf,
 template <int FMAX, int KMAX>
 __device__ __forceinline__ void refine_near(const Env<FMAX>& e, int K, float tol_c0, FoodScan<KMAX>& q) {
   const float near2 = tol_c0 * 17857.f;            // tol_c0 = 1.4e-7 L^2  ->  (0.05 L)^2
-  // entry 0, the nearest: the one the reward reads; a second food that close as well has not been seen
-  const bool nr = (K > 0) && (q.idx[0] >= 0) && (q.bd[0] * q.bd[0] < near2);
-  if (__any(nr)) {
+  // Entry 0, the nearest, is the one the reward reads; the entries behind it only go to the observation, but two or three
+  // foods can sit that close together (an injected food set, two fallback placements), so every observed entry is looked at.
+#pragma unroll 1
+  for (int s = 0; s < K; ++s) {                    // one copy of the code, s in a scalar register (as exact_order_sqrt_reg)
+    int is = -1;
+    float ds = 0.f;
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j) { is = (j == s) ? q.idx[j] : is; ds = (j == s) ? q.bd[j] : ds; }
+    const bool nr = (is >= 0) && (ds * ds < near2);
+    if (!__any(nr)) break;                          // the entries are sorted by distance: none behind this one is near either
     double dx = 0.0, dy = 0.0;
 #pragma unroll
     for (int k = 0; k < FMAX; ++k) {
-      const bool h = nr && (q.idx[0] == k);
+      const bool h = nr && (is == k);
       double ex = e.x, ey = e.y;
       asm volatile("" : "+v"(ex), "+v"(ey));      // one slot at a time, inside this branch (see exact_order_reg)
       dx = h ? (e.fx[k] - ex) : dx;
       dy = h ? (e.fy[k] - ey) : dy;
     }
-    q.bx[0] = nr ? (float)dx : q.bx[0];
-    q.by[0] = nr ? (float)dy : q.by[0];
-    q.bd[0] = nr ? (float)__builtin_sqrt(dx * dx + dy * dy) : q.bd[0];
+    const float fdx = (float)dx, fdy = (float)dy, fd = __builtin_amdgcn_sqrtf(fmaf(fdy, fdy, fdx * fdx));   // as resolve_f32
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j) {
+      const bool w = nr && (j == s);
+      q.bx[j] = w ? fdx : q.bx[j];
+      q.by[j] = w ? fdy : q.by[j];
+      q.bd[j] = w ? fd : q.bd[j];
+    }
   }
 }
 

@@ -720,6 +720,7 @@ struct salp_vec {
   size_t nf_rows;
   hipStream_t last_stream;   // the stream of the handle's most recent launch: what get_stats / destroy wait for
   int64_t last_launch[8];    // salp_vec_last_launch
+  int64_t last_sigs[2];      // salp_vec_last_launch_signatures
   const void* last_kernel;   // the main (else the predicated) kernel of the most recent launch: salp_vec_last_kernel_resources
 };
 
@@ -892,8 +893,13 @@ int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st) {
   // A small ragged batch (step-per-launch acting loops) is launch-bound: one predicated launch over the whole
   // range instead of two; the predicates only cost when the write stream is the bound.
   if (n_full < h->n && h->n * (int64_t)H <= (int64_t)1 << 22) n_full = 0;
+  // the signature each launch was compiled for (pick_sig): the predicated kernels exist as kSigMain and kSigPartial only
+  const int sig_full = (h->kmax == 3) ? sig : kSigPartial;
+  const int sig_ragged = (h->kmax == 3 && sig == kSigMain) ? kSigMain : kSigPartial;
+  h->last_sigs[0] = (n_full > 0) ? sig_full : -1;
+  h->last_sigs[1] = (n_full < h->n) ? sig_ragged : -1;
   h->last_launch[0] = h->fmax; h->last_launch[1] = h->kmax; h->last_launch[2] = (h->kmax == 3) ? h->std_consts : 0;
-  h->last_launch[3] = h->P.forced; h->last_launch[4] = (h->kmax == 3) ? sig : kSigPartial; h->last_launch[5] = gen;
+  h->last_launch[3] = h->P.forced; h->last_launch[4] = (n_full > 0) ? sig_full : sig_ragged; h->last_launch[5] = gen;
   h->last_launch[6] = n_full; h->last_launch[7] = h->n - n_full;
   if (n_full > 0) {
     const unsigned grid = (unsigned)((n_full + kBlock - 1) / kBlock);
@@ -960,6 +966,7 @@ int salp_vec_create(const salp_config_t* cfg, int64_t n_envs, int device_id, uin
   salp_vec* h = new (std::nothrow) salp_vec();
   if (!h) return fail(SALP_ERR_OOM, "host allocation failed");
   memset(h, 0, sizeof(*h));
+  h->last_sigs[0] = h->last_sigs[1] = -1;
   h->cfg = *cfg; h->device = device_id; h->n = n_envs; h->seed = seed; h->global_step = 0;
   h->F = cfg->num_food_items; h->K = cfg->max_observed_food;
   h->obs_dim = 10 + 4 * h->K + 2; h->act_dim = cfg->forced_breathing ? 1 : 2;
@@ -1048,6 +1055,12 @@ int64_t salp_vec_global_step(const salp_vec_t* h) { return h ? h->global_step : 
 int salp_vec_last_launch(const salp_vec_t* h, int64_t info[8]) {
   if (!h || !info) return fail(SALP_ERR_INVALID, "handle/info is NULL");
   memcpy(info, h->last_launch, sizeof(h->last_launch));
+  return SALP_OK;
+}
+
+int salp_vec_last_launch_signatures(const salp_vec_t* h, int64_t sig[2]) {
+  if (!h || !sig) return fail(SALP_ERR_INVALID, "handle/sig is NULL");
+  sig[0] = h->last_sigs[0]; sig[1] = h->last_sigs[1];
   return SALP_OK;
 }
 
@@ -1238,8 +1251,44 @@ int salp_vec_get_state(salp_vec_t* h, double* f64, int32_t* i32, uint32_t flags,
   return SALP_OK;
 }
 
+// The ranges of include/salp_vec.h ("Ranges accepted by salp_vec_set_state"), on a host snapshot.
+static int check_snapshot(const salp_vec_t* h, const double* f64, const int32_t* i32) {
+  const int64_t n = h->n;
+  char msg[200];
+  if (f64) {
+    for (int64_t i = 0; i < n; ++i) {
+      const double th = f64[SALP_F_THETA * n + i], om = f64[SALP_F_OMEGA * n + i], w = f64[SALP_F_WATER * n + i];
+      if (!(fabs(th) <= SALP_SET_STATE_MAX_ANGLE) || !(fabs(om) <= SALP_SET_STATE_MAX_ANGLE)) {
+        snprintf(msg, sizeof msg, "set_state: env %lld: theta %g / omega %g outside [-%g, %g] (or NaN)", (long long)i, th, om,
+                 SALP_SET_STATE_MAX_ANGLE, SALP_SET_STATE_MAX_ANGLE);
+        return fail(SALP_ERR_INVALID, msg);
+      }
+      if (!(w >= 0.0 && w <= 1.0)) {
+        snprintf(msg, sizeof msg, "set_state: env %lld: water %.17g outside [0, 1] (or NaN)", (long long)i, w);
+        return fail(SALP_ERR_INVALID, msg);
+      }
+    }
+  }
+  if (i32) {
+    for (int64_t i = 0; i < n; ++i) {
+      const int32_t ph = i32[SALP_I_PHASE * n + i], tm = i32[SALP_I_TIMER * n + i], du = i32[SALP_I_EXHALE_DUR * n + i],
+                    ho = i32[SALP_I_SHAPE_HOLD * n + i];
+      if (ph < 0 || ph > 2 || tm < 0 || tm > 255 || du < 0 || du > 255 || ho < 0 || ho > 7) {
+        snprintf(msg, sizeof msg, "set_state: env %lld: phase %d / timer %d / exhale duration %d / shape hold %d outside 0..2 / 0..255 / 0..255 / 0..7",
+                 (long long)i, ph, tm, du, ho);
+        return fail(SALP_ERR_INVALID, msg);
+      }
+    }
+  }
+  return SALP_OK;
+}
+
 int salp_vec_set_state(salp_vec_t* h, const double* f64, const int32_t* i32, uint32_t flags, void* stream) {
   if (!h) return fail(SALP_ERR_INVALID, "handle is NULL");
+  if (!(flags & SALP_DEVICE_PTRS)) {     // nothing is written when any env is out of range
+    const int bad = check_snapshot(h, f64, i32);
+    if (bad != SALP_OK) return bad;
+  }
   DeviceScope dev_scope;
   HIP_TRY(dev_scope.enter(h->device));
   hipStream_t st = (hipStream_t)stream;
