@@ -14,6 +14,9 @@
  *   salp_vec_step           SalpSnakeEnv.step                snake:157-202, legacy:119-156
  *   salp_vec_rollout        the caller's `for t in range(T): env.step(a[t])` loop
  *                           (train.py:110-122, eval/collect_navigation_data.py:97-114)
+ *   salp_vec_step_packed / salp_vec_rollout_packed
+ *                           the same two with the returned tuple (obs, reward, terminated, truncated, info) packed
+ *                           into one record per env and step — no reference counterpart
  *   salp_vec_get/set_state  attribute pokes `env.robot_pos = …`, `env.food_positions = …`
  *                           (eval/collect_navigation_data.py:76-89) and legacy:390-403 (_get_info)
  *   salp_vec_observe        SalpSnakeEnv._get_extended_observation   snake:366-428
@@ -70,6 +73,7 @@ typedef enum salp_status {
 } salp_status;
 
 enum { SALP_DEVICE_PTRS = 1u };
+enum { SALP_REC_FINAL_OBS = 2u };   /* salp_vec_step_packed / salp_vec_rollout_packed: records carry the terminal observation */
 
 /* POD of the reference's parameters.  Units are the reference's (pixels, steps, radians). */
 typedef struct salp_config {
@@ -150,6 +154,20 @@ enum {
  * (pre-autoreset) episode, as in the info dict of snake:195-200. */
 enum { SALP_INFO_FOOD_COLLECTED = 0, SALP_INFO_STEPS_SINCE_FOOD, SALP_INFO_COLLISION, SALP_INFO_COLS };
 
+/* Packed transition record (salp_vec_step_packed / salp_vec_rollout_packed): everything a step returns as ONE row of 32-bit
+ * words per env and step, so that a consumer hands one block on (a collective, a replay buffer) instead of six streams.
+ * With OD = obs_dim:
+ *   words 0 .. OD-1     the observation, float32: what `obs` of salp_vec_step receives (post-autoreset)
+ *   word  OD + SALP_REC_REWARD             reward, float32
+ *   word  OD + SALP_REC_FLAGS              byte 0 terminated (0/1), byte 1 truncated (0/1), byte 2 collision (0/1), byte 3 zero
+ *   word  OD + SALP_REC_FOOD_COLLECTED     int32, SALP_INFO_FOOD_COLLECTED of the step (pre-autoreset episode)
+ *   word  OD + SALP_REC_STEPS_SINCE_FOOD   int32, likewise
+ * and, with the call flag SALP_REC_FINAL_OBS, OD more words: the terminal observation of an env that finished in that
+ * step; in the rows of unfinished envs those words are not written (the final_obs rule of salp_vec_step).  Integer words are
+ * stored as integers, so every field is a typed view of the block (bytes 0 and 1 of the flags word are bool arrays).
+ * A block is [horizon][n_envs][salp_vec_record_width] words, contiguous; a device block must be 16-byte aligned. */
+enum { SALP_REC_REWARD = 0, SALP_REC_FLAGS, SALP_REC_FOOD_COLLECTED, SALP_REC_STEPS_SINCE_FOOD, SALP_REC_EXTRA_COLS };
+
 /* Running totals since create / salp_vec_clear_stats, reduced on the device
  * (wave-shuffle + one atomic per wave; fixed-point so the sum is order-independent). */
 typedef struct salp_stats {
@@ -211,6 +229,19 @@ int salp_vec_rollout(salp_vec_t* h, const float* act, int32_t horizon, float* ob
                      uint8_t* terminated, uint8_t* truncated, float* final_obs, float* act_out,
                      uint32_t flags, void* stream);
 
+/* Words per record: obs_dim + SALP_REC_EXTRA_COLS, or 2 obs_dim + SALP_REC_EXTRA_COLS with SALP_REC_FINAL_OBS in flags. */
+int salp_vec_record_width(const salp_vec_t* h, uint32_t flags);
+
+/* step() / rollout() with the packed record as the only output ("Packed transition record" above): rec is
+ * [n_envs][width] / [horizon][n_envs][width] words.  flags: SALP_DEVICE_PTRS and / or SALP_REC_FINAL_OBS.  act, act_out, the
+ * global step, the statistics and the same-step autoreset are those of salp_vec_step / salp_vec_rollout (act == NULL:
+ * device-generated actions, rollout only).  With device pointers the call only launches kernels on `stream` (capturable
+ * into a hipGraph, like salp_vec_step).  SALP_ERR_INVALID, with nothing launched and the handle unchanged, for a NULL
+ * rec, horizon < 1, a flag bit other than those two, or a device rec that is not 16-byte aligned. */
+int salp_vec_step_packed(salp_vec_t* h, const float* act, float* rec, uint32_t flags, void* stream);
+int salp_vec_rollout_packed(salp_vec_t* h, const float* act, int32_t horizon, float* rec, float* act_out,
+                            uint32_t flags, void* stream);
+
 /* Current observation of every env without stepping. obs float [n_envs][obs_dim]. */
 int salp_vec_observe(salp_vec_t* h, float* obs, uint32_t flags, void* stream);
 
@@ -240,10 +271,11 @@ int64_t salp_vec_global_step(const salp_vec_t* h);
  * reference counterpart): info[0] food slots of the kernel (1, 4, 8, 12, 16), [1] observed-food capacity (3, or 8 = the
  * generic instantiation), [2] 1 = the reference's constants compiled in as literals, [3] forced breathing, [4] the
  * output signature the kernel was compiled for: 1 = obs, reward, terminated, truncated and nothing else, 2 = those four plus
- * final_obs and / or info, 0 = some of the four is NULL (every store tested; always 0 for the generic instantiation), [5] 1 = actions drawn in the kernel,
+ * final_obs and / or info, 0 = some of the four is NULL (every store tested; always 0 for the generic instantiation's unpacked calls),
+ * 3 = the packed record (both halves of a split launch and the generic instantiation too), [5] 1 = actions drawn in the kernel,
  * [6] envs served by the unpredicated launch (whole wavefronts), [7] envs served by the predicated launch.
  * [4] is the signature of the kernel that ran: the unpredicated launch's when there was one, else the predicated launch's
- * (predicated kernels exist for signatures 1 and 0 only: a call with final_obs / info runs them as 0). */
+ * (predicated kernels exist for signatures 1, 3 and 0 only: a call with final_obs / info runs them as 0). */
 int salp_vec_last_launch(const salp_vec_t* h, int64_t info[8]);
 /* The output signature of each half of that call: sig[0] the unpredicated launch, sig[1] the predicated launch, -1 for a
  * half that was not launched (or before any call). */

@@ -2,7 +2,11 @@
 """Interleaved A/B timing of several builds of libsalp_hip.so in ONE process (same device, same
 data), as cdna_hip_programming.md §5.4 rule 24 asks.  usage:
     python profiles/ab_bench.py name1=path1.so name2=path2.so ... [--rounds 6] [--launches 5]
-Prints per-variant median / min kernel ms (HIP events) for the bench workload."""
+Prints per-variant median / min kernel ms (HIP events) for the bench workload.
+Variant-name suffixes pick the entry point: "+gen" / "+gennoout" device-generated actions; "+packed" / "+packedfinal"
+salp_vec_rollout_packed (records of obs_dim + 4 / 2 obs_dim + 4 words); "+step" salp_vec_step with info (and final_obs
+with --final-obs), which needs --chunk 1 — with --chunk 1 "+packed" is salp_vec_step_packed's launch.  --calls N times N
+consecutive calls as one sample (a 10-us step launch is below what one event pair resolves)."""
 import ctypes, json, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -13,6 +17,7 @@ from underwater_swimmer_rl_amd import _capi
 def main():
     variants, rounds, launches, n, H, preset = [], 6, 5, 262144, 250, "single_food_long_horizon"
     want_fin = False
+    calls = 1
     overrides = {}
     it = iter(sys.argv[1:])
     for a in it:
@@ -23,6 +28,7 @@ def main():
         elif a == "--preset": preset = next(it)
         elif a == "--set":                           # --set width=801 (a SalpSnakeEnv keyword on top of the preset)
             k, v = next(it).split("=", 1); overrides[k] = (int(v) if v.lstrip("-").isdigit() else (v == "true") if v in ("true", "false") else float(v))
+        elif a == "--calls": calls = int(next(it))
         elif a == "--final-obs": want_fin = True      # the non-FULL output signature (terminal observations written)
         else:
             k, v = a.split("=", 1); variants.append((k, os.path.abspath(v)))
@@ -36,6 +42,8 @@ def main():
     term = torch.empty((H, n), dtype=torch.uint8, device=dev)
     trunc = torch.empty((H, n), dtype=torch.uint8, device=dev)
     fin = torch.empty((H, n, cfg.obs_dim), device=dev) if want_fin else None
+    info = torch.empty((H, n, _capi.INFO_COLS), dtype=torch.int32, device=dev)
+    rec = torch.empty((H, n, 2 * cfg.obs_dim + _capi.REC_EXTRA_COLS), device=dev)      # either record width
     handles = {}
     for name, path in variants:
         lib = _capi.load_library(path)
@@ -45,6 +53,16 @@ def main():
     def launch(name):
         lib, h, _ = handles[name]
         vp = ctypes.c_void_p
+        st = vp(torch.cuda.current_stream().cuda_stream)
+        if "+packed" in name:
+            flags = _capi.SALP_DEVICE_PTRS | (_capi.REC_FINAL_OBS if name.endswith("+packedfinal") else 0)
+            _capi.check(lib, lib.salp_vec_rollout_packed(h, vp(act.data_ptr()), H, vp(rec.data_ptr()), None, flags, st), "rollout_packed")
+            return
+        if name.endswith("+step"):
+            assert H == 1, "+step needs --chunk 1"
+            _capi.check(lib, lib.salp_vec_step(h, vp(act.data_ptr()), vp(obs.data_ptr()), vp(rew.data_ptr()), vp(term.data_ptr()),
+                        vp(trunc.data_ptr()), vp(fin.data_ptr()) if fin is not None else None, vp(info.data_ptr()), 1, st), "step")
+            return
         a_in = None if "+gen" in name else vp(act.data_ptr())
         a_out = vp(act.data_ptr()) if name.endswith("+gen") else None
         _capi.check(lib, lib.salp_vec_rollout(h, a_in, H, vp(obs.data_ptr()), vp(rew.data_ptr()),
@@ -58,7 +76,9 @@ def main():
         for name, _ in variants:
             for _ in range(launches):
                 s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                s.record(); launch(name); e.record(); e.synchronize()
+                s.record()
+                for _ in range(calls): launch(name)
+                e.record(); e.synchronize()
                 times[name].append(s.elapsed_time(e))
     # every variant simulates the same trajectory (same seed, warm-up and launch count), so launch i of one variant and
     # launch i of another do the same work: the MEAN over all launches, and the mean of the per-launch ratios to the

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """LDS bank-conflict model (MI355X_MICROARCH.md §LDS) of the rollout kernel's observation tile: cycles of the six
-ds_write_b128 (lane = row) and of the six ds_read_b128 of the flush plan, for candidate row layouts, Q = 6."""
+ds_write_b128 (lane = row) and of the six ds_read_b128 of the flush plan, for candidate row layouts, Q = 6 — and of the
+packed-record tile (signature 3: Q + 1 = 7 float4 per row, full height and the two-pass half height)."""
 def rd_groups():
     g = [list(range(0, 4)) + list(range(12, 16)) + list(range(20, 28)),
          list(range(4, 12)) + list(range(16, 20)) + list(range(28, 32))]
@@ -26,7 +27,33 @@ def model(f):
     w = sum(cycles(wr_groups(), lambda l, q=q: f(l, q), 32) for q in range(Q))
     rd = sum(cycles(rd_groups(), lambda l, j=j: f((j * 64 + l) // Q, (j * 64 + l) % Q), 64) for j in range(Q))
     return w, rd
+# Packed-record tile (salp_vec.hip, PACKED): rows of QP = 7 float4 at an unpadded 112-B pitch, no swizzle.  7 is odd, so
+# eight consecutive rows start in eight different 16-B bank groups; the flush reads float4 j*64 + lane of a linear tile.
+QP = 7
+def PACKED(r, c): return r * 16 * QP + 16 * c
+def model_packed(f=PACKED, rows=64):
+    """(LDS cycles of the QP row writes, LDS cycles of the flush reads) of one step: `rows` = 64, one pass of seven
+    64-lane reads; `rows` = 32 (the 8-slot and the literal-constant 16-slot kernels), two passes, each written by one half
+    of the wavefront and flushed by three 64-lane reads and one of 32 lanes."""
+    passes = 64 // rows
+    w = rd = 0
+    for h in range(passes):
+        writers = [[l for l in g if l // rows == h] for g in wr_groups()]
+        w += sum(cycles([g for g in writers if g], lambda l, q=q: f(l % rows, q), 32) for q in range(QP))
+        for j in range((rows * QP + 63) // 64):
+            readers = [[l for l in g if j * 64 + l < rows * QP] for g in rd_groups()]
+            rd += cycles([g for g in readers if g], lambda l, j=j: f((j * 64 + l) // QP, (j * 64 + l) % QP), 64)
+    return w, rd
+def model_stash():
+    """The record's last float4 parked per lane at tile byte 384 + 16 lane between the step and the row writes:
+    (cycles of its one ds_write_b128, cycles of its one ds_read_b128)."""
+    f = lambda l: 384 + 16 * l
+    return cycles(wr_groups(), f, 32), cycles(rd_groups(), f, 64)
 if __name__ == '__main__':
+    print('packed stash (16 B per lane, linear)           write %d cycles (ideal 8)   read %d cycles (ideal 4)' % model_stash())
+    for rows in (64, 32):
+        w, rd = model_packed(rows=rows)
+        print(f'{"packed 112-B pitch, %d-row tile" % rows:46s} writes {w:3d} cycles (ideal {8 * QP})   flush reads {rd:3d} cycles (ideal {4 * QP})')
     for name, f in layouts.items():
         w, rd = model(f)
         print(f'{name:46s} writes {w:3d} cycles (ideal {8 * Q})   flush reads {rd:3d} cycles (ideal {4 * Q})')

@@ -19,6 +19,9 @@ def __getattr__(name):  # lazy: the pieces below need torch / the HIP library
     if name in ("compare_actions_with_states", "robot_params", "params_from_robot", "ROBOT_PARAM_NAMES"):
         from . import robot_compare
         return getattr(robot_compare, name)
+    if name in ("record_width", "unpack_record", "pack_record"):
+        from . import records
+        return getattr(records, name)
     if name in ("SalpLib", "load_library", "SalpError"):
         from . import _capi
         return getattr(_capi, name)

@@ -17,6 +17,9 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libsalp_hip.so")
 
 SALP_DEVICE_PTRS = 1
 INFO_COLS = 3
+# packed transition record (include/salp_vec.h "Packed transition record"; layout helpers: records.py)
+REC_FINAL_OBS = 2           # call flag next to SALP_DEVICE_PTRS
+REC_REWARD, REC_FLAGS, REC_FOOD_COLLECTED, REC_STEPS_SINCE_FOOD, REC_EXTRA_COLS = range(5)
 # snapshot rows (include/salp_vec.h)
 F_X, F_Y, F_VX, F_VY, F_THETA, F_OMEGA, F_NOZZLE, F_WATER, F_ELLIPSE_A, F_ELLIPSE_B, F_FOOD0 = range(11)
 (I_PHASE, I_TIMER, I_EXHALE_DUR, I_SHAPE_HOLD, I_STEPS_SINCE_FOOD, I_FOOD_COLLECTED, I_RNG_COUNTER,
@@ -29,6 +32,7 @@ EXPORTS = (
     "salp_vec_observe", "salp_vec_get_state", "salp_vec_set_state", "salp_vec_get_stats",
     "salp_vec_clear_stats", "salp_vec_global_step", "salp_vec_set_base_num_food", "salp_vec_base_num_food",
     "salp_vec_reseed", "salp_vec_last_launch", "salp_vec_last_kernel_resources", "salp_vec_last_launch_signatures",
+    "salp_vec_record_width", "salp_vec_step_packed", "salp_vec_rollout_packed",
 )
 
 
@@ -96,6 +100,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         L.salp_vec_last_kernel_resources.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
     if path is None or hasattr(L, "salp_vec_reseed"):   # (an explicit path may be an older A/B variant, profiles/ab_bench.py)
         L.salp_vec_reseed.argtypes = [vp, u64, vp, u32, vp]
+    if path is None or hasattr(L, "salp_vec_step_packed"):
+        L.salp_vec_record_width.argtypes = [vp, u32]
+        L.salp_vec_step_packed.argtypes = [vp, vp, vp, u32, vp]
+        L.salp_vec_rollout_packed.argtypes = [vp, vp, i32, vp, vp, u32, vp]
     L.salp_vec_global_step.argtypes = [vp]
     L.salp_vec_global_step.restype = i64
     L.salp_vec_set_base_num_food.argtypes = [vp, i32]
@@ -168,6 +176,21 @@ class SalpLib:
                                                   self._ptr(final_obs), self._ptr(act_out), flags,
                                                   ctypes.c_void_p(stream)), "salp_vec_rollout")
 
+    def record_width(self, with_final: bool) -> int:
+        """Words per packed record of this handle: obs_dim + 4, or 2 obs_dim + 4 with the terminal observation."""
+        return int(self.lib.salp_vec_record_width(self._h, REC_FINAL_OBS if with_final else 0))
+
+    def step_packed(self, act, rec, flags, stream=0):
+        """salp_vec_step_packed: rec float32 [n, width]; flags: SALP_DEVICE_PTRS and / or REC_FINAL_OBS."""
+        check(self.lib, self.lib.salp_vec_step_packed(self._h, self._ptr(act), self._ptr(rec), flags,
+                                                      ctypes.c_void_p(stream)), "salp_vec_step_packed")
+
+    def rollout_packed(self, act, horizon, rec, act_out, flags, stream=0):
+        """salp_vec_rollout_packed: rec float32 [horizon, n, width]; act None = device-generated actions (into act_out)."""
+        check(self.lib, self.lib.salp_vec_rollout_packed(self._h, self._ptr(act), int(horizon), self._ptr(rec),
+                                                         self._ptr(act_out), flags, ctypes.c_void_p(stream)),
+              "salp_vec_rollout_packed")
+
     def reseed(self, seed, obs, flags, stream=0):
         """New draw streams keyed by `seed`, every env reset from draw counter 0; no reallocation (capture-safe)."""
         check(self.lib, self.lib.salp_vec_reseed(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, self._ptr(obs), flags,
@@ -192,8 +215,9 @@ class SalpLib:
 
     def last_launch(self) -> dict:
         """The kernel instantiation of the most recent step / rollout call (salp_vec_last_launch).  `full_signature`: 1 = the four
-        main outputs only, 2 = the four plus final_obs / info, 0 = every store tested (some main output absent, the generic
-        instantiation, or a predicated launch asked for final_obs / info) — of the kernel that ran: the unpredicated launch's
+        main outputs only, 2 = the four plus final_obs / info, 3 = the packed record (step_packed / rollout_packed, every
+        instantiation), 0 = every store tested (some main output absent, the generic instantiation, or a predicated launch
+        asked for final_obs / info) — of the kernel that ran: the unpredicated launch's
         when there was one, else the predicated launch's.  `signature_unpredicated` / `signature_predicated`: each half's own,
         -1 for a half that was not launched (salp_vec_last_launch_signatures)."""
         a = (ctypes.c_int64 * 8)()

@@ -38,7 +38,10 @@ constexpr int kWave = 64;
 //   signatures landed on 129 = three per SIMD, up to 22 % slower (profiles/r03/ab_notes.md sessions 14, 20);  12 slots 3 —
 //   <= 168 VGPRs, 49 KB of LDS (four: a timing build at 128 VGPRs / 36 KB was 13 % slower, session 17);  16 slots 3 for the
 //   literal-constant unpredicated kernels (half-height tile, session 19), else 2;  generic K: 2 (12 slots) / 1 (16 slots).
-constexpr int waves_per_simd(int fmax, int kmax, bool std_consts, bool ragged) {
+//   The packed signature keeps every row (its 8-slot kernel keeps the six-column tile, TAILREG below); its one-wavefront
+//   predicated 8-slot twin has the seven-column tile, 45 KB: 3.
+constexpr int waves_per_simd(int fmax, int kmax, bool std_consts, bool ragged, int sig) {
+  if (sig == 3 && ragged && kmax == 3 && fmax == 8) return 3;
   return fmax <= 1 ? 4 : (kmax != 3 ? (fmax <= 12 ? 2 : 1) : (fmax <= 8 ? 4 : (fmax <= 12 ? 3 : ((std_consts && !ragged) ? 3 : 2))));
 }
 
@@ -94,7 +97,7 @@ struct ColdBlock {
 // all — the per-step 256-B action read costs the write stream ~10 % (HBM read/write turnarounds,
 // profiles/r01/ab_notes.md) — and, if act_out is given, the actions are written out instead.
 template <int FMAX, int KMAX, bool FORCED, bool STD, int SIG, bool RAGGED, bool GEN>
-__global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED)) void salp_rollout_kernel(DevParams P_arg, DevState S, IOPtrs io, int H, int64_t env_begin, int64_t env_end, const ColdBlock* __restrict__ cold) {
+__global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG)) void salp_rollout_kernel(DevParams P_arg, DevState S, IOPtrs io, int H, int64_t env_begin, int64_t env_end, const ColdBlock* __restrict__ cold) {
   // STD = false: where the hot path's constants come from (open_consts, salp_device.h) — the device copy, function by
   // function, for the 4- and 8-slot kernels; the by-value launch parameters for the others
   constexpr bool MEMC = !STD && KMAX == 3 && (FMAX == 4 || FMAX == 8);
@@ -103,15 +106,27 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED)) vo
   const DevParams& P = STD ? P_arg : P_pol;
   constexpr bool FULL = SIG != 0;         // obs, reward, terminated, truncated all present: their stores are unconditional
   constexpr bool EXTRAS = SIG != 1;       // final_obs / info may be present (tested per use; SIG 0: every output is tested)
+  // SIG 3 (kSigPacked): ONE output stream of transition records (include/salp_vec.h "Packed transition record") — the
+  // observation row plus one float4 (reward, flags word, food_collected, steps_since_food) — through the tile; io.obs is
+  // the record block, io.final_obs non-NULL says that the rows carry a terminal-observation tail
+  constexpr bool PACKED = SIG == 3;
+  // TAILREG: the unpredicated 8-slot packed kernel stores that last float4 straight from registers (one 16-B store per
+  // lane where the other signatures issue their reward / flag / info stores) and keeps the tile of the unpacked
+  // signatures: 40960 B of LDS per workgroup is exactly four workgroups per CU, a seven-column tile (45056 B) is three.
+  constexpr bool TAILREG = PACKED && !RAGGED && KMAX == 3 && FMAX == 8;
   constexpr int QMAX = 3 + KMAX;          // float4 per observation row
+  constexpr int QPMAX = QMAX + ((PACKED && !TAILREG) ? 1 : 0);   // float4 columns of a tile row
   // LDS tile of the wavefront's 64 observation rows.  Banking (MI355X_MICROARCH.md §LDS): ds_write_b128 goes
   // in 8 groups of 8 lanes over banks (a/4) mod 32, ds_read_b128 in 4 groups of 16 lanes ({0-3,12-15,20-27},
   // ...) over banks (a/4) mod 64.  K = 3 (Q = 6 float4 per row): unpadded 96-B rows with the float4 column
   // XOR-ed by bit 2 of the row — conflict-free for the row writes AND for the flush reads (profiles/isa_lds_model.py;
   // the 112-B padded pitch of round 1 was conflict-free for the writes only: 2-way on the reads).
   // Other K (generic instantiation, Q possibly odd): the padded pitch.
-  constexpr bool SWZ = (KMAX == 3);
-  constexpr int PITCH = SWZ ? 4 * QMAX : 4 * QMAX + 4;     // LDS row pitch in floats
+  // PACKED: unpadded rows of Q + 1 float4 with no swizzle.  K = 3: 7 float4 = 112 B, an ODD number of float4, so eight
+  // consecutive rows start in eight different 16-B bank groups (writes conflict-free) and the flush reads float4 j*64 + lane
+  // of a linear tile (reads conflict-free): profiles/isa_lds_model.py PACKED.  Generic K: rows of QPMAX float4, not modelled.
+  constexpr bool SWZ = (KMAX == 3) && (!PACKED || TAILREG);
+  constexpr int PITCH = (PACKED && !TAILREG) ? 4 * QPMAX : (SWZ ? 4 * QMAX : 4 * QMAX + 4);     // LDS row pitch in floats
   // Where the food positions of a multi-food env live: up to 12 slots in VGPRs with an fp32 mirror in LDS
   // (salp_food_reg.h), above that in LDS (salp_food_lds.h); one food is plain registers.
   constexpr bool REGF = FMAX > 1 && (FMAX <= 12 || KMAX == 3);   // K = 3: every slot count; generic K: up to 12 slots
@@ -178,9 +193,35 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED)) vo
 #pragma unroll
   for (int j = 0; j < QMAX; ++j) {
     int i = wave * WAVE_FLOATS + (lds_off[j] >= 0 ? lds_off[j] : 0);
-    asm volatile("" : "+v"(i));
+    if constexpr (!PACKED || TAILREG) asm volatile("" : "+v"(i));
     flush_src[j] = reinterpret_cast<const v4f*>(lds + i);
   }
+  // PACKED flush plan: float4 f = j*64 + lane of a tile pass (TILE_ROWS rows of TQ float4: Q + 1, TAILREG Q) lives at tile
+  // row r = f / TQ, column c = f % TQ and goes to float4 r * RW4 + c of the pass's first record; RW4 = the record width in
+  // float4 (Q + 1, or 2 Q + 1 with the terminal observation, which the flush skips).  Without the terminal observation the
+  // wavefront's 64 records are one contiguous run and every store is a whole 1-KB line group, as in the other signatures.
+  // The plan is kept as ONE byte per store — the row r, 0xFF: nothing to move (past the pass's last float4; RAGGED: a row
+  // past the range) — four to a register, and both offsets are rebuilt from it at every flush (f + r * (pitch - TQ) in
+  // the tile, f + r * (RW4 - TQ) in the block: a bit-field extract and a multiply-add per store).  An offset register per
+  // store put the 8-, 12- and 16-slot kernels, which sit at their register limits, into scratch.
+  constexpr int PJ = PACKED ? (TILE_ROWS * QPMAX + kWave - 1) / kWave : 1;
+  const int NQ = Q + 1;
+  const int TQ = TAILREG ? Q : NQ;
+  const int RW4 = NQ + ((PACKED && io.final_obs) ? Q : 0);
+  uint32_t rec_rows[(PJ + 3) / 4];
+#pragma unroll
+  for (int i = 0; i < (PJ + 3) / 4; ++i) rec_rows[i] = 0u;
+#pragma unroll
+  for (int j = 0; j < PJ; ++j) {
+    const int f = j * kWave + lane;
+    const int r = f / TQ;
+    rec_rows[j >> 2] |= (uint32_t)((f < TILE_ROWS * TQ && (!RAGGED || r < rows)) ? r : 0xFF) << (8 * (j & 3));
+  }
+  // The record's last float4 waits in LDS from the step's end to the row writes (its values are those of BEFORE the
+  // autoreset): 16 B per lane at tile bytes 384 .. 1407, which the rare paths leave alone (placement scratch 0 .. 255,
+  // wave_stats 256 .. 383) and every tile covers (>= 3584 B) — not four registers across the rare region and observe().
+  // (Not TAILREG: stored at once.)
+  float4* const rec_stash = reinterpret_cast<float4*>(tile + 96) + lane;
   // Event statistics (episodes, terminations, food, ...) change on rare steps only: they are accumulated with LDS integer
   // atomics inside the rare-event branch — in 128 bytes of the wavefront's own tile, idle there — and leave with ONE
   // global atomic instruction per wavefront and event step, into one of 64 line-sized replicas.  (Rounds 1-2 kept a
@@ -295,7 +336,14 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED)) vo
     double rmax = o.rmax;
     bool have_rel = o.rel_valid;
 
-    if (active) {
+    // PACKED: the record's last float4, taken here (the values of the step's own episode, before the autoreset below)
+    if constexpr (PACKED) {
+      const uint32_t fl = (o.terminated ? 1u : 0u) | (o.truncated ? 0x100u : 0u) | (o.collision ? 0x10000u : 0u);
+      const float4 last = make_float4(o.reward, __uint_as_float(fl), __uint_as_float((uint32_t)e.fc), __uint_as_float((uint32_t)e.ssf));
+      if constexpr (TAILREG) reinterpret_cast<float4*>(io.obs)[(rowbase + env) * RW4 + Q] = last;
+      else *rec_stash = last;
+    }
+    if (!PACKED && active) {
       // reward: one dword per lane (256 B per wavefront); flags: one byte per lane.  (Rebuilding the
       // 64 flag bytes from a ballot and storing 16 dwords was measured: no faster in the memory
       // pipeline and slower overall, profiles/r01/ab_notes.md.)
@@ -368,7 +416,8 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED)) vo
             } else {
               observe<FMAX, KMAX, STD>(e, C, rmax, have_rel, o.rel, fo);
             }
-            float4* dst = reinterpret_cast<float4*>(io.final_obs + (rowbase + env) * OD);
+            float4* dst = PACKED ? reinterpret_cast<float4*>(io.obs) + (rowbase + env) * RW4 + NQ     // the record's own tail
+                                 : reinterpret_cast<float4*>(io.final_obs + (rowbase + env) * OD);
 #pragma unroll
             for (int q = 0; q < QMAX; ++q)
               if (q < Q) dst[q] = make_float4(fo[4 * q], fo[4 * q + 1], fo[4 * q + 2], fo[4 * q + 3]);
@@ -426,7 +475,52 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED)) vo
       SALP_STAMP(8);
       // (per-lane 96-B rows stored straight from registers, without the LDS transpose: 2.1x slower, r01 ab_notes)
       v4f* gout = reinterpret_cast<v4f*>(io.obs + (rowbase + env0) * OD) + lane;
-      if constexpr (HALF) {
+      if constexpr (PACKED) {
+        // the record rows through the tile, in one pass or (HALF) two of 32 rows; each pass is PJ 16-B-per-lane stores
+        v4f* const rec0 = reinterpret_cast<v4f*>(io.obs) + (rowbase + env0) * RW4;
+        const v4f* const tile4 = reinterpret_cast<const v4f*>(tile);
+        const int skip4 = RW4 - TQ;                 // float4 the flush skips behind every tile row (wave-uniform)
+#pragma unroll
+        for (int i = 0; i < (PJ + 3) / 4; ++i) asm volatile("" : "+v"(rec_rows[i]));     // unpacked here, at every flush (see the plan)
+        auto row_of = [&](int j) { return (int)((rec_rows[j >> 2] >> (8 * (j & 3))) & 0xFFu); };
+        // whole store instructions of an unpredicated K = 3 launch carry no test at all
+        auto moves = [&](int j) { return (!RAGGED && KMAX == 3 && (j + 1) * kWave <= TILE_ROWS * QPMAX) ? true : row_of(j) != 0xFF; };
+        float4 tail = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (!TAILREG) {
+          // every lane's, before ANY lane writes a row over the stash: the rows of other lanes cover it, which the compiler,
+          // reasoning about one lane, cannot see — without the barrier it sank this read below the row writes
+          tail = *rec_stash;
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+#pragma unroll
+        for (int h = 0; h < (HALF ? 2 : 1); ++h) {
+          if (!HALF || (lane >> 5) == h) {
+#pragma unroll
+            for (int q = 0; q < QMAX; ++q)
+              if (q < Q) ((q & 1) ? myrow_odd : myrow_even)[q] = make_float4(ob[4 * q], ob[4 * q + 1], ob[4 * q + 2], ob[4 * q + 3]);
+            if constexpr (!TAILREG) myrow4[Q] = tail;
+          }
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          v4f tv[PJ];
+#pragma unroll
+          for (int j = 0; j < PJ; ++j)
+            if (moves(j)) {
+              if constexpr (TAILREG) tv[j] = *flush_src[j];        // the swizzled six-column tile of the unpacked signatures
+              else tv[j] = tile4[j * kWave + lane + row_of(j) * (PITCH / 4 - TQ)];
+            }
+          v4f* const pass0 = rec0 + h * TILE_ROWS * RW4;
+#pragma unroll
+          for (int j = 0; j < PJ; ++j)
+            if (moves(j)) __builtin_nontemporal_store(tv[j], &pass0[j * kWave + lane + row_of(j) * skip4]);
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // this pass's reads before the next writes of the tile
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+      } else if constexpr (HALF) {
         // float4 f = j*64 + lane (j = 0..2) of a half lives at tile row f / 6, column f % 6 (flush_src[0..2]) and goes to global
         // float4 (3 h + j) * 64 + lane of the wavefront's 64-row block: the same 1-KB stores as the full plan, three per half
 #pragma unroll
@@ -792,12 +886,15 @@ typedef void (*reset_fn)(DevParams, DevState, const uint8_t*, float*, int);
 // written in the rare-event region, the three info words per step); kSigPartial = some main output is NULL: every
 // store is tested, the step ends in a full drain (a 12-food rollout with final_obs ran 22 % slower in that form,
 // profiles/r03/ab_notes.md session 15).  The one-wavefront predicated launches exist as kSigMain and kSigPartial only.
-enum { kSigPartial = 0, kSigMain = 1, kSigExtras = 2 };
+// kSigPacked = ONE stream of transition records (salp_vec_step_packed / salp_vec_rollout_packed): no per-lane reward / flag /
+// info stores at all; unpredicated and predicated, K = 3 and generic K; no in-kernel action generation.
+enum { kSigPartial = 0, kSigMain = 1, kSigExtras = 2, kSigPacked = 3 };
 template <int FMAX, int KMAX, bool FORCED, bool STD, bool RAGGED, bool GEN>
 rollout_fn pick_sig(int sig) {
   if constexpr (GEN) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, true>;
   else {
     if (sig == kSigMain) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, false>;
+    if (sig == kSigPacked) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigPacked, RAGGED, false>;
     if constexpr (!RAGGED)
       if (sig == kSigExtras) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigExtras, false, false>;
     return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigPartial, RAGGED, false>;
@@ -829,6 +926,13 @@ rollout_fn rollout_kernel_for(const salp_vec* h, int sig, bool gen) {
   const bool forced = h->P.forced != 0;
   if (h->kmax == 3)
     return h->std_consts ? rollout_kernel_k3<true, RAGGED>(h, forced, sig, gen) : rollout_kernel_k3<false, RAGGED>(h, forced, sig, gen);
+  if (sig == kSigPacked) {
+    if (h->fmax <= 12)
+      return forced ? (rollout_fn)salp_rollout_kernel<12, 8, true, false, kSigPacked, RAGGED, false>
+                    : (rollout_fn)salp_rollout_kernel<12, 8, false, false, kSigPacked, RAGGED, false>;
+    return forced ? (rollout_fn)salp_rollout_kernel<16, 8, true, false, kSigPacked, RAGGED, false>
+                  : (rollout_fn)salp_rollout_kernel<16, 8, false, false, kSigPacked, RAGGED, false>;
+  }
   if (h->fmax <= 12)   // K != 3 with up to 12 foods: the register-food form of the generic instantiation (2 wavefronts per SIMD, not 1)
     return forced ? (rollout_fn)salp_rollout_kernel<12, 8, true, false, kSigPartial, RAGGED, false>
                   : (rollout_fn)salp_rollout_kernel<12, 8, false, false, kSigPartial, RAGGED, false>;
@@ -884,9 +988,10 @@ struct Bump {  // carve sub-buffers out of the staging allocation
   }
 };
 
-int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st) {
+// packed: io.obs is a record block (kSigPacked), io.final_obs non-NULL asks for the terminal-observation tail
+int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, bool packed = false) {
   const bool main_outputs = io.obs && io.reward && io.terminated && io.truncated;
-  const int sig = !main_outputs ? kSigPartial : ((io.final_obs || io.info) ? kSigExtras : kSigMain);
+  const int sig = packed ? kSigPacked : (!main_outputs ? kSigPartial : ((io.final_obs || io.info) ? kSigExtras : kSigMain));
   const bool gen = io.act == nullptr;               // only reached when can_generate_in_kernel()
   // envs in full wavefronts: unpredicated kernel
   int64_t n_full = h->n / kWave * kWave;
@@ -894,8 +999,9 @@ int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st) {
   // range instead of two; the predicates only cost when the write stream is the bound.
   if (n_full < h->n && h->n * (int64_t)H <= (int64_t)1 << 22) n_full = 0;
   // the signature each launch was compiled for (pick_sig): the predicated kernels exist as kSigMain and kSigPartial only
-  const int sig_full = (h->kmax == 3) ? sig : kSigPartial;
-  const int sig_ragged = (h->kmax == 3 && sig == kSigMain) ? kSigMain : kSigPartial;
+  // (kSigPacked exists in every form)
+  const int sig_full = (h->kmax == 3 || packed) ? sig : kSigPartial;
+  const int sig_ragged = packed ? kSigPacked : ((h->kmax == 3 && sig == kSigMain) ? kSigMain : kSigPartial);
   h->last_sigs[0] = (n_full > 0) ? sig_full : -1;
   h->last_sigs[1] = (n_full < h->n) ? sig_ragged : -1;
   h->last_launch[0] = h->fmax; h->last_launch[1] = h->kmax; h->last_launch[2] = (h->kmax == 3) ? h->std_consts : 0;
@@ -1136,6 +1242,25 @@ int salp_vec_observe(salp_vec_t* h, float* obs, uint32_t flags, void* stream) {
   return SALP_OK;
 }
 
+// Device-generated actions of the next H steps into act_out when given, else into the handle's own buffer (grown on demand).
+static int generate_actions(salp_vec_t* h, int32_t H, float* act_out, hipStream_t st, const float** act) {
+  float* dst = act_out;
+  if (!dst) {
+    const size_t need_a = (size_t)H * (size_t)h->n * h->act_dim * sizeof(float);
+    if (need_a > h->act_bytes) {
+      if (h->act_buf) { (void)hipFree(h->act_buf); h->act_buf = nullptr; h->act_bytes = 0; }
+      HIP_TRY(hipMalloc((void**)&h->act_buf, need_a));
+      h->act_bytes = need_a;
+    }
+    dst = h->act_buf;
+  }
+  const unsigned agrid = (unsigned)((h->n + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(salp_gen_actions_kernel, dim3(agrid), dim3(kBlock), 0, st, h->P, dst, (int)H, h->act_dim, (int64_t)h->global_step);
+  HIP_TRY(hipGetLastError());
+  *act = dst;
+  return SALP_OK;
+}
+
 static int rollout_impl(salp_vec_t* h, const float* act, int32_t H, float* obs, float* reward,
                         uint8_t* terminated, uint8_t* truncated, float* final_obs, int32_t* info,
                         float* act_out, uint32_t flags, void* stream) {
@@ -1155,20 +1280,9 @@ static int rollout_impl(salp_vec_t* h, const float* act, int32_t H, float* obs, 
     io.act = act; io.obs = obs; io.reward = reward; io.terminated = terminated; io.truncated = truncated;
     io.final_obs = final_obs; io.info = info; io.act_out = act_out;
     const bool full_sig = obs && reward && terminated && truncated && !final_obs && !info;
-    if (!act && !can_generate_in_kernel(h, full_sig)) {  // generate into act_out when given, else into the handle's buffer
-      float* dst = act_out;
-      if (!dst) {
-        const size_t need_a = HN * h->act_dim * sizeof(float);
-        if (need_a > h->act_bytes) {
-          if (h->act_buf) { (void)hipFree(h->act_buf); h->act_buf = nullptr; h->act_bytes = 0; }
-          HIP_TRY(hipMalloc((void**)&h->act_buf, need_a));
-          h->act_bytes = need_a;
-        }
-        dst = h->act_buf;
-      }
-      hipLaunchKernelGGL(salp_gen_actions_kernel, dim3(agrid), dim3(kBlock), 0, st, h->P, dst, (int)H, h->act_dim, (int64_t)h->global_step);
-      HIP_TRY(hipGetLastError());
-      io.act = dst;
+    if (!act && !can_generate_in_kernel(h, full_sig)) {
+      int rc = generate_actions(h, H, act_out, st, &io.act);
+      if (rc != SALP_OK) return rc;
     }
     int rc = launch_rollout(h, io, H, st);
     if (rc == SALP_OK) h->global_step += H;
@@ -1222,6 +1336,75 @@ int salp_vec_rollout(salp_vec_t* h, const float* act, int32_t horizon, float* ob
                      uint8_t* terminated, uint8_t* truncated, float* final_obs, float* act_out,
                      uint32_t flags, void* stream) {
   return rollout_impl(h, act, horizon, obs, reward, terminated, truncated, final_obs, nullptr, act_out, flags, stream);
+}
+
+int salp_vec_record_width(const salp_vec_t* h, uint32_t flags) {
+  if (!h) return 0;
+  return h->obs_dim + SALP_REC_EXTRA_COLS + ((flags & SALP_REC_FINAL_OBS) ? h->obs_dim : 0);
+}
+
+// salp_vec_step_packed / salp_vec_rollout_packed: the kSigPacked kernels.  Everything is checked before anything is launched.
+static int packed_impl(salp_vec_t* h, const float* act, int32_t H, float* rec, float* act_out, uint32_t flags, void* stream) {
+  if (!h) return fail(SALP_ERR_INVALID, "handle is NULL");
+  if (!rec) return fail(SALP_ERR_INVALID, "rec is NULL");
+  if (H <= 0) return fail(SALP_ERR_INVALID, "horizon must be >= 1");
+  if (flags & ~(uint32_t)(SALP_DEVICE_PTRS | SALP_REC_FINAL_OBS))
+    return fail(SALP_ERR_INVALID, "unknown flag bits (SALP_DEVICE_PTRS and SALP_REC_FINAL_OBS are defined)");
+  if ((flags & SALP_DEVICE_PTRS) && ((uintptr_t)rec & 15u))
+    return fail(SALP_ERR_INVALID, "rec must be 16-byte aligned (the records are written as float4)");
+  DeviceScope dev_scope;
+  HIP_TRY(dev_scope.enter(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  h->last_stream = st;
+  const bool with_final = (flags & SALP_REC_FINAL_OBS) != 0;
+  const int W = h->obs_dim + SALP_REC_EXTRA_COLS;
+  const size_t RW = (size_t)salp_vec_record_width(h, flags);
+  IOPtrs io;
+  memset(&io, 0, sizeof(io));
+  io.stats = h->stats_enabled ? h->stats : nullptr;
+  io.global_step = h->global_step;
+  const size_t HN = (size_t)H * (size_t)h->n;
+  if (flags & SALP_DEVICE_PTRS) {
+    io.act = act; io.obs = rec; io.final_obs = with_final ? rec + W : nullptr;
+    if (!act) {
+      int rc = generate_actions(h, H, act_out, st, &io.act);
+      if (rc != SALP_OK) return rc;
+    }
+    int rc = launch_rollout(h, io, H, st, true);
+    if (rc == SALP_OK) h->global_step += H;
+    return rc;
+  }
+  // host pointers: stage through device memory, synchronous
+  const size_t act_b = HN * h->act_dim * sizeof(float), rec_b = HN * RW * sizeof(float);
+  int rc = ensure_stage(h, align_up(act_b, 256) + align_up(rec_b, 256) + 1024);
+  if (rc != SALP_OK) return rc;
+  Bump b{(char*)h->stage, 0};
+  float* d_act = b.take<float>(HN * h->act_dim);
+  float* d_rec = b.take<float>(HN * RW);
+  if (act) HIP_TRY(hipMemcpyAsync(d_act, act, act_b, hipMemcpyHostToDevice, st));
+  else {
+    rc = generate_actions(h, H, d_act, st, &io.act);
+    if (rc != SALP_OK) return rc;
+  }
+  if (with_final) HIP_TRY(hipMemcpyAsync(d_rec, rec, rec_b, hipMemcpyHostToDevice, st));   // the tails of unfinished rows stay as they are
+  io.act = d_act; io.obs = d_rec; io.final_obs = with_final ? d_rec + W : nullptr;
+  rc = launch_rollout(h, io, H, st, true);
+  if (rc != SALP_OK) return rc;
+  h->global_step += H;
+  HIP_TRY(hipMemcpyAsync(rec, d_rec, rec_b, hipMemcpyDeviceToHost, st));
+  if (!act && act_out) HIP_TRY(hipMemcpyAsync(act_out, d_act, act_b, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return SALP_OK;
+}
+
+int salp_vec_step_packed(salp_vec_t* h, const float* act, float* rec, uint32_t flags, void* stream) {
+  if (!act) return fail(SALP_ERR_INVALID, "act is NULL");
+  return packed_impl(h, act, 1, rec, nullptr, flags, stream);
+}
+
+int salp_vec_rollout_packed(salp_vec_t* h, const float* act, int32_t horizon, float* rec, float* act_out,
+                            uint32_t flags, void* stream) {
+  return packed_impl(h, act, horizon, rec, act_out, flags, stream);
 }
 
 int salp_vec_get_state(salp_vec_t* h, double* f64, int32_t* i32, uint32_t flags, void* stream) {

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .records import unpack_record
 from .vector_env import SalpVectorEnv, _as_config
 
 
@@ -124,8 +125,11 @@ class ShardedSalpVectorEnv:
         obs)`) bootstraps from the true terminal observation of every shard.  One collective per step: all of
         it travels as one [N/G, W] float32 block, W = obs_dim + 5 (+ obs_dim with terminal observations) — a
         ring all-gather over xGMI is latency-bound at this size, separate collectives cost one launch each.
-        (The three info columns are small non-negative integers: exact in float32.)"""
+        (The three info columns are small non-negative integers: exact in float32.)
+        An engine that offers `step_packed` (the HIP engine) writes that block itself: see `_step_packed`."""
         a = self._shard(actions, 0)
+        if hasattr(self.engine, "step_packed"):
+            return self._step_packed(a)
         obs, rew, term, trunc, info = self.engine.step(a)
         D = self.obs_dim
         obs, rew = _to_tensor(obs, self.device), _to_tensor(rew, self.device)
@@ -152,6 +156,23 @@ class ShardedSalpVectorEnv:
             ginfo["final_observation"] = g[:, D + 5:]
             ginfo["_final_observation"] = g_term | g_trunc
         return g[:, :D], g[:, D], g_term, g_trunc, ginfo
+
+    def _step_packed(self, a):
+        """`step` for an engine with `step_packed`: the kernel's packed transition records (records.py) ARE the block of
+        the one collective — nothing is packed before it, and the returned fields are typed views of the gathered block
+        (plus one widening of the collision byte to int32 and one OR for the mask).  `info["local"]` is this rank's
+        slice of the same tensors."""
+        D = self.obs_dim
+        rec = _to_tensor(self.engine.step_packed(a, want_final_observation=self.gather_final_observation), self.device)
+        u = unpack_record(self.all_gather("step_rec", rec), D)
+        ginfo = {"food_collected": u["food_collected"], "steps_since_food": u["steps_since_food"],
+                 "collision": u["collision"].to(torch.int32)}
+        if u["final_observation"] is not None:
+            ginfo["final_observation"] = u["final_observation"]
+            ginfo["_final_observation"] = u["terminated"] | u["truncated"]
+        n = rec.shape[0]
+        ginfo["local"] = {k: v[self.rank * n:(self.rank + 1) * n] for k, v in ginfo.items()}
+        return u["obs"], u["reward"], u["terminated"], u["truncated"], ginfo
 
     def rollout(self, actions=None, horizon=None, gather: str = "final", async_gather: bool = False):
         """Local fused rollout of `horizon` steps, then the exchange:

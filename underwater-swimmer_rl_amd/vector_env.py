@@ -191,6 +191,63 @@ class SalpVectorEnv:
                 np.logical_or(c["term"], c["trunc"], out=c["done"])
         return c["obs"], c["rew"], c["term"], c["trunc"], c["info"]
 
+    def _prepare_step_packed(self, with_final: bool):
+        import ctypes
+        rec = self._buf("rec_final" if with_final else "rec", (self.num_envs, self._lib.record_width(with_final)), np.float32)
+        p_rec = ctypes.c_void_p(rec.data_ptr()) if self._torch is not None else rec.ctypes.data_as(ctypes.c_void_p)
+        c = dict(rec=rec, p_rec=p_rec, fn=self._lib.lib.salp_vec_step_packed, h=self._lib._h, vp=ctypes.c_void_p,
+                 flags=self._flags | (_capi.REC_FINAL_OBS if with_final else 0))
+        self._packed_cache = getattr(self, "_packed_cache", None) or {}
+        self._packed_cache[with_final] = c
+        return c
+
+    def step_packed(self, actions, want_final_observation: bool = True):
+        """One step of every env, returned as ONE block: the packed transition records [N, width] (records.py;
+        `unpack_record(rec, obs_dim)` gives the step tuple's fields as zero-copy views).  width = obs_dim + 4, or
+        2 obs_dim + 4 with terminal observations (the tail of an unfinished env's row is not written).  The block is the
+        env's own buffer, overwritten by the next call; the per-call cost is one ctypes call, as in `step`."""
+        with_final = bool(want_final_observation)
+        c = (getattr(self, "_packed_cache", None) or {}).get(with_final) or self._prepare_step_packed(with_final)
+        t = self._torch
+        if t is not None and isinstance(actions, t.Tensor) and actions.is_cuda and actions.device == self.device \
+                and actions.dtype == t.float32 and actions.is_contiguous() \
+                and actions.numel() == self.num_envs * self.act_dim:
+            a = actions
+            p_act = c["vp"](a.data_ptr())
+            stream = c["vp"](t.cuda.current_stream(self.device).cuda_stream)
+        else:
+            a = self._actions_in(actions, (self.num_envs,))
+            p_act = self._lib._ptr(a)
+            stream = c["vp"](self._stream)
+        rc = c["fn"](c["h"], p_act, c["p_rec"], c["flags"], stream)
+        if rc != 0:
+            _capi.check(self._lib.lib, rc, "salp_vec_step_packed")
+        return c["rec"]
+
+    def rollout_packed(self, actions=None, horizon: Optional[int] = None, want_final_observation: bool = False,
+                       out=None) -> dict:
+        """`horizon` steps in one kernel launch with the packed records as the only output: dict(record=[H, N, width],
+        actions=...).  actions: [H, N, act_dim] or None (device-generated).  `out`: a float32 [H, N, width] block to write
+        into (its width must match `want_final_observation`); default an env-owned buffer."""
+        n = self.num_envs
+        if actions is not None:
+            horizon = int(actions.shape[0]) if hasattr(actions, "shape") else len(actions)
+            a = self._actions_in(actions, (horizon, n))
+            aout = None
+        else:
+            if horizon is None:
+                raise ValueError("horizon is required when actions is None")
+            a = None
+            aout = self._buf("r_act", (horizon, n, self.act_dim), np.float32)
+        H = int(horizon)
+        with_final = bool(want_final_observation)
+        shape = (H, n, self._lib.record_width(with_final))
+        rec = out if out is not None else self._buf("r_rec_final" if with_final else "r_rec", shape, np.float32)
+        if tuple(rec.shape) != shape:
+            raise ValueError(f"out has shape {tuple(rec.shape)}; expected {shape}")
+        self._lib.rollout_packed(a, H, rec, aout, self._flags | (_capi.REC_FINAL_OBS if with_final else 0), self._stream)
+        return dict(record=rec, actions=a if a is not None else aout)
+
     def capture_policy_steps(self, policy, n_steps: int = 1, record=None, want_final_observation: bool = True):
         """Captures `n_steps` x (`policy(obs) -> actions`, `step(actions)`) into one hipGraph and returns the
         `torch.cuda.CUDAGraph`; every `replay()` advances all envs by `n_steps`.  For small batches the
@@ -271,6 +328,7 @@ class SalpVectorEnv:
         self._lib.close()
         self._bufs.clear()
         self._step_cache = None
+        self._packed_cache = None
 
     # ------------------------------------------------------------------ state access
     def get_state(self):
