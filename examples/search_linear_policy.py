@@ -1,0 +1,77 @@
+#!/usr/bin/env python3
+"""Cross-entropy search over LINEAR swimmer policies on the navigation configuration, the whole population inside the
+rollout kernel: 1024 policies x 64 envs per launch (`SalpVectorEnv.rollout_policy` with a stacked `MLPPolicy`), one launch
+per round, the weights refreshed in place between rounds (`handle.update`, no re-allocation).  A policy is
+a = clip(W obs + b, -1, 1) with 25 parameters; its score is the mean return of its 64 envs over `--steps` steps (food reward
+plus time penalty: reaching the food early scores high).  No pass threshold: it prints the best score per round and the
+scripted pursuit rule's score on the same envs for comparison.
+    python examples/search_linear_policy.py [--policies P] [--envs-per-policy E] [--rounds R] [--steps T]"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from underwater_swimmer_rl_amd import SalpVectorEnv  # noqa: E402
+from underwater_swimmer_rl_amd._capi import SALP_DEVICE_PTRS  # noqa: E402
+from underwater_swimmer_rl_amd.navigation_eval import navigation_config  # noqa: E402
+from underwater_swimmer_rl_amd.policy import MLPPolicy, pursuit_policy  # noqa: E402
+
+
+def population(theta):
+    """theta float32 [P, obs_dim + 1] -> P linear policies (W = theta[:, :-1], b = theta[:, -1])."""
+    P = theta.shape[0]
+    return MLPPolicy([(theta[:, None, :-1], theta[:, -1:])], np.ones((P, 1), np.float32), np.zeros((P, 1), np.float32), "clip")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--policies", type=int, default=1024)
+    ap.add_argument("--envs-per-policy", type=int, default=64)
+    ap.add_argument("--rounds", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=1500)
+    ap.add_argument("--elite", type=float, default=0.05)
+    args = ap.parse_args()
+    P, E, T = args.policies, args.envs_per_policy, args.steps
+    cfg = navigation_config()
+    env = SalpVectorEnv(cfg, num_envs=P * E, seed=0)
+    D = env.obs_dim + 1
+    rng = np.random.default_rng(0)
+    center, spread = np.zeros(D), np.full(D, 1.0)
+    theta = (center + spread * rng.standard_normal((P, D))).astype(np.float32)
+    handle = env.make_policy(population(theta))
+    stream = int(torch.cuda.current_stream(env.device).cuda_stream)
+
+    def scores():
+        env.reset(seed=1)                 # every round (and the baseline) sees the same episodes
+        out = env.rollout_policy(handle, T, want_actions=False)
+        return out["reward"].sum(0).reshape(P, E).mean(1)
+
+    n_elite = max(4, int(args.elite * P))
+    t0 = time.perf_counter()
+    for r in range(args.rounds):
+        if r:
+            theta = (center + spread * rng.standard_normal((P, D))).astype(np.float32)
+            handle.update(torch.as_tensor(population(theta).pack(), device=env.device), SALP_DEVICE_PTRS, stream)
+        s = scores()
+        elite = torch.topk(s, n_elite).indices.cpu().numpy()
+        center, spread = theta[elite].mean(0), np.maximum(theta[elite].std(0), 1e-3)
+        print(f"round {r}: best {float(s.max()):9.2f}  elite mean {float(s[elite].mean()):9.2f}  population mean {float(s.mean()):9.2f}", flush=True)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    # the scripted rule on the same envs, every policy slot holding it
+    base = pursuit_policy(3.0, env.obs_dim)
+    handle.update(np.repeat(base.pack(), P, axis=0))
+    print(f"pursuit baseline: {float(scores().mean()):9.2f}")
+    print(f"{args.rounds} rounds x {P} policies x {E} envs x {T} steps in {dt:.2f} s ({args.rounds * P * E * T / dt:.3g} env-steps/s, "
+          f"one launch per round)")
+    best = theta[elite[0]]
+    print("best weights (obs column: weight):", {i: round(float(v), 3) for i, v in enumerate(best[:-1]) if abs(v) > 0.5}, "bias", round(float(best[-1]), 3))
+    env.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -242,6 +242,56 @@ int salp_vec_step_packed(salp_vec_t* h, const float* act, float* rec, uint32_t f
 int salp_vec_rollout_packed(salp_vec_t* h, const float* act, int32_t horizon, float* rec, float* act_out,
                             uint32_t flags, void* stream);
 
+/* Policy: a small MLP evaluated INSIDE the rollout kernel, so that a closed-loop rollout (every action a function of the
+ * previous observation) is one launch — no reference counterpart; it replaces the caller's
+ * `for t: a = actor(obs); obs = env.step(a)` loop (train.py:110-122 with the actor of the SAC trainer).
+ * The function, for an observation row x (obs_dim floats):
+ *   h = relu(W x + b) for each hidden layer;  u = W_last h + b_last;  a = act(u) * scale + shift,
+ *   act = tanhf (SALP_POLICY_OUT_TANH) or a clamp to [-1, 1] (SALP_POLICY_OUT_CLIP).
+ * Weights of ONE policy, float32, `salp_policy_words` words — the layout of torch's nn.Linear: for each layer in order
+ * W[out][in] row-major, then b[out] (the last layer has out = act_dim); then scale[act_dim], shift[act_dim].
+ * A block of P policies is [P][words].  The library re-lays the block into a buffer of its own at create / update.
+ * Arithmetic: fp32 throughout, in one fixed order in every kernel: each unit starts from its bias and adds its inputs in
+ * index order with one fused multiply-add each (fmaf(w, x, acc)); relu = fmaxf(acc, 0); then tanhf or the clamp; then one
+ * multiply by scale and one add of shift (two roundings).  An action is a deterministic function of (weights, observation).
+ * Policy assignment: P == 1: every env runs the one policy, for any n_envs.  P > 1: env i runs policy i / (n_envs / P);
+ * n_envs % P == 0 and (n_envs / P) % 64 == 0 are required (a wavefront never mixes policies). */
+enum { SALP_POLICY_OUT_TANH = 0, SALP_POLICY_OUT_CLIP = 1 };
+typedef struct salp_policy_desc {
+  uint32_t struct_size;     /* = sizeof(salp_policy_desc_t) */
+  int32_t  n_hidden;        /* 0, 1 or 2 hidden layers (0 = linear policy) */
+  int32_t  hidden[2];       /* each a multiple of 16 in [16, 64]; unused entries 0 */
+  int32_t  out_activation;  /* SALP_POLICY_OUT_TANH or SALP_POLICY_OUT_CLIP */
+  int32_t  n_policies;      /* P >= 1 */
+} salp_policy_desc_t;
+typedef struct salp_policy salp_policy_t;
+
+/* float32 words of ONE policy of this shape on this handle, or a negative salp_status (descriptor out of range). */
+int salp_policy_words(const salp_vec_t* h, const salp_policy_desc_t* desc);
+/* A policy bound to the handle's device, obs_dim, act_dim and n_envs (handles with max_observed_food == 3 only).
+ * weights: [P][words], host pointers, or device pointers with SALP_DEVICE_PTRS (then asynchronous on `stream`).
+ * SALP_ERR_INVALID for a descriptor outside the ranges above or a P that n_envs does not allow.  Destroy the policy before
+ * its handle. */
+int salp_policy_create(salp_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags, void* stream,
+                       salp_policy_t** out);
+/* New weights of the same shape.  With SALP_DEVICE_PTRS the call is stream-ordered and allocates nothing: it may sit between
+ * two replays of a captured graph that holds salp_vec_rollout_policy calls, which then run the new weights. */
+int salp_policy_update(salp_policy_t* pol, const float* weights, uint32_t flags, void* stream);
+void salp_policy_destroy(salp_policy_t* pol);
+
+/* rollout() with the actions computed in the kernel: the action of step 0 is the policy applied to the env's current
+ * observation (what salp_vec_observe returns); the action of step t + 1 is the policy applied to the row written to obs[t]
+ * (after a same-step autoreset the first observation of the new episode; with no_autoreset the row as returned).
+ * When the state was left by a step, the observation of step 0 is formed with the bits of that step's row, so a rollout
+ * cut into several calls takes the same actions, bit for bit, as one call.
+ * obs, reward, terminated, truncated as in salp_vec_rollout, all four required; act_out (may be NULL) receives the actions
+ * taken, float [horizon][n_envs][act_dim].  Global step, statistics, state write-back and autoreset are those of
+ * salp_vec_rollout.  With device pointers the call only launches kernels on `stream` (capturable).
+ * SALP_ERR_INVALID, with nothing launched and the handle unchanged, for a policy of another handle or other dimensions,
+ * horizon < 1, a NULL main output, or a P that n_envs does not allow. */
+int salp_vec_rollout_policy(salp_vec_t* h, const salp_policy_t* pol, int32_t horizon, float* obs, float* reward,
+                            uint8_t* terminated, uint8_t* truncated, float* act_out, uint32_t flags, void* stream);
+
 /* Current observation of every env without stepping. obs float [n_envs][obs_dim]. */
 int salp_vec_observe(salp_vec_t* h, float* obs, uint32_t flags, void* stream);
 
@@ -273,6 +323,7 @@ int64_t salp_vec_global_step(const salp_vec_t* h);
  * output signature the kernel was compiled for: 1 = obs, reward, terminated, truncated and nothing else, 2 = those four plus
  * final_obs and / or info, 0 = some of the four is NULL (every store tested; always 0 for the generic instantiation's unpacked calls),
  * 3 = the packed record (both halves of a split launch and the generic instantiation too), [5] 1 = actions drawn in the kernel,
+ * 2 = actions computed by a policy in the kernel (salp_vec_rollout_policy),
  * [6] envs served by the unpredicated launch (whole wavefronts), [7] envs served by the predicated launch.
  * [4] is the signature of the kernel that ran: the unpredicated launch's when there was one, else the predicated launch's
  * (predicated kernels exist for signatures 1, 3 and 0 only: a call with final_obs / info runs them as 0). */

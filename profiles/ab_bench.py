@@ -6,7 +6,12 @@ Prints per-variant median / min kernel ms (HIP events) for the bench workload.
 Variant-name suffixes pick the entry point: "+gen" / "+gennoout" device-generated actions; "+packed" / "+packedfinal"
 salp_vec_rollout_packed (records of obs_dim + 4 / 2 obs_dim + 4 words); "+step" salp_vec_step with info (and final_obs
 with --final-obs), which needs --chunk 1 — with --chunk 1 "+packed" is salp_vec_step_packed's launch.  --calls N times N
-consecutive calls as one sample (a 10-us step launch is below what one event pair resolves)."""
+consecutive calls as one sample (a 10-us step launch is below what one event pair resolves).
+"+policy": salp_vec_rollout_policy with the 24 -> 32 -> 32 -> A actor (sac.Actor, seed 0) evaluated in the kernel; it writes
+the actions it takes into the shared action block, so with --launches 1 and the "+policy" variant listed FIRST a plain
+variant behind it replays exactly those actions from the same state (the price of the policy block alone).
+"+actorgraph": the same actor in torch around salp_vec_step, `SalpVectorEnv.capture_policy_steps(n_steps = chunk)` replayed
+— the best closed-loop path without the in-kernel policy (runs the installed library whatever path is given)."""
 import ctypes, json, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -50,10 +55,39 @@ def main():
         c = cfg.to_c(); h = ctypes.c_void_p()
         _capi.check(lib, lib.salp_vec_create(ctypes.byref(c), n, 0, 0, 0, ctypes.byref(h)), "create")
         handles[name] = (lib, h, c)
+    policies, graphs, envs = {}, {}, []
+    if any("+policy" in name or "+actorgraph" in name for name, _ in variants):
+        from underwater_swimmer_rl_amd.policy import MLPPolicy
+        from underwater_swimmer_rl_amd.sac import Actor
+        torch.manual_seed(0)
+        low, high = (None, None) if cfg.forced_breathing else ([0.0, -1.0], [1.0, 1.0])
+        actor = Actor(cfg.obs_dim, cfg.act_dim, hidden=(32, 32), act_low=low, act_high=high).to(dev)
+        mlp = MLPPolicy.from_actor(actor)
+        w = mlp.pack()
+        for name, _ in variants:
+            if "+policy" in name:
+                lib, h, _ = handles[name]
+                d, ph = mlp.desc(), ctypes.c_void_p()
+                _capi.check(lib, lib.salp_policy_create(h, ctypes.byref(d), w.ctypes.data_as(ctypes.c_void_p), 0, None, ctypes.byref(ph)), "policy_create")
+                policies[name] = ph
+            if "+actorgraph" in name:
+                env = pkg.SalpVectorEnv(cfg, num_envs=n, seed=0)
+                env.reset()
+                with torch.no_grad():
+                    graphs[name] = env.capture_policy_steps(lambda o: actor(o, deterministic=True, with_logprob=False)[0], n_steps=H,
+                                                            want_final_observation=False)
+                envs.append(env)
     def launch(name):
         lib, h, _ = handles[name]
         vp = ctypes.c_void_p
         st = vp(torch.cuda.current_stream().cuda_stream)
+        if "+actorgraph" in name:
+            graphs[name].replay()
+            return
+        if "+policy" in name:
+            _capi.check(lib, lib.salp_vec_rollout_policy(h, policies[name], H, vp(obs.data_ptr()), vp(rew.data_ptr()), vp(term.data_ptr()),
+                        vp(trunc.data_ptr()), vp(act.data_ptr()), _capi.SALP_DEVICE_PTRS, st), "rollout_policy")
+            return
         if "+packed" in name:
             flags = _capi.SALP_DEVICE_PTRS | (_capi.REC_FINAL_OBS if name.endswith("+packedfinal") else 0)
             _capi.check(lib, lib.salp_vec_rollout_packed(h, vp(act.data_ptr()), H, vp(rec.data_ptr()), None, flags, st), "rollout_packed")

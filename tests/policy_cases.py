@@ -1,0 +1,107 @@
+"""The closed-loop (in-kernel policy) case table shared by tests/test_gpu_policy_rollout.py and its CPU guard
+tests/test_policy_rollout.py: which parity case (tests/parity_cases.py: configuration and injected start state), how many
+envs, which policy.  Needs numpy, the package's configuration, `policy.MLPPolicy` and the oracle binding — no GPU library.
+
+The weights are seeded sparse normal draws (four non-zero weights per unit, `gain / 2` each) with a larger gain on the
+output layer so that the tanh / clip output is driven over most of its range; the seeds and gains below were picked on
+the oracle until every case ends episodes by wall and by truncation in mixed wavefronts under its own policy, spreads its
+actions beyond +-0.9 and keeps `error_bound` below 1e-4 (tests/test_policy_rollout.py asserts all of it).
+"""
+import functools
+
+import numpy as np
+
+import parity_cases as pc
+from underwater_swimmer_rl_amd.policy import MLPPolicy
+
+H = pc.HORIZON
+WAVE = pc.WAVE
+
+# name -> parity case, envs, hidden widths, output activation, weight seed, hidden gain, output gain,
+#         the kernel that must run: (food slots, literal constants), and whether the whole batch runs predicated
+CASES = {
+    "one_food_mlp32": dict(case="single_food", n=256, hidden=(32, 32), out="tanh", seed=123, gain=1.5, out_gain=6.0,
+                           kernel=(1, 1), predicated=False),
+    "one_food_mlp32_ragged": dict(case="single_food", n=293, hidden=(32, 32), out="tanh", seed=123, gain=1.5, out_gain=6.0,
+                                  kernel=(1, 1), predicated=True),
+    "sac_gail_mlp64": dict(case="sac_gail_F12", n=256, hidden=(64, 64), out="tanh", seed=125, gain=1.5, out_gain=6.0,
+                           kernel=(12, 1), predicated=False),
+    "four_slots_other_tank_mlp16": dict(case="F3_other_tank", n=256, hidden=(16,), out="tanh", seed=102, gain=1.5, out_gain=4.0,
+                                        kernel=(4, 0), predicated=False),
+    "free_breathing_mlp32": dict(case="free_breathing", n=256, hidden=(32, 32), out="tanh", seed=142, gain=1.5, out_gain=6.0,
+                                 kernel=(1, 1), predicated=False),
+    "sixteen_slots_linear_clip": dict(case="F16_sixteen_slots", n=256, hidden=(), out="clip", seed=100, gain=1.5, out_gain=4.0,
+                                      kernel=(16, 1), predicated=False),
+}
+ACTION_SPREAD = 0.9          # the squashed output (before scale / shift) must reach below -0.9 and above +0.9
+BOUND_CEILING = 1e-4         # error_bound stays below this on every visited observation: the GPU check is not vacuous
+
+
+def random_policy(obs_dim, act_dim, hidden, out, seed, gain, out_gain, free_breathing=False, fan=4):
+    rng = np.random.default_rng(seed)
+    layers, d = [], obs_dim
+    for h in tuple(hidden) + (act_dim,):
+        g = out_gain if len(layers) == len(hidden) else gain
+        # `fan` non-zero weights per unit: the error bound grows with sum |w|, the signal with sqrt(sum w^2) — sparse rows reach
+        # the whole output range with a bound that stays small
+        W = np.zeros((h, d), np.float32)
+        for r in range(h):
+            cols = rng.choice(d, size=min(fan, d), replace=False)
+            W[r, cols] = (rng.standard_normal(cols.size) * g / np.sqrt(cols.size)).astype(np.float32)
+        b = (rng.standard_normal(h) * 0.1).astype(np.float32)
+        layers.append((W, b))
+        d = h
+    # free breathing: the Box is [0, 1] x [-1, 1] (sac.Actor's scale / shift)
+    scale = np.array([0.5, 1.0], np.float32) if free_breathing else None
+    shift = np.array([0.5, 0.0], np.float32) if free_breathing else None
+    return MLPPolicy.from_layers(layers, scale, shift, out)
+
+
+def case_cfg(name):
+    return pc.case_cfg(CASES[name]["case"])
+
+
+def case_policy(name):
+    c, cfg = CASES[name], case_cfg(name)
+    return random_policy(cfg.obs_dim, cfg.act_dim, c["hidden"], c["out"], c["seed"], c["gain"], c["out_gain"],
+                         free_breathing=not cfg.forced_breathing)
+
+
+def squashed(policy, actions):
+    """The output activation's value behind `actions` (scale / shift undone): in [-1, 1]."""
+    return (np.asarray(actions, np.float64) - policy.shift.astype(np.float64)[0]) / policy.scale.astype(np.float64)[0]
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_closed_loop(name):
+    """The oracle stepped closed-loop under `reference()` (rounded to float32) from the injected start state: computed
+    once, shared, read-only.  Returns cfg, policy, start snapshot, and the run: obs_in [H, n, OD] (what each action saw),
+    actions, and the oracle's outputs with `info`."""
+    c, cfg, policy = CASES[name], case_cfg(name), case_policy(name)
+    n = c["n"]
+    orc, f64, i32 = pc.start_oracle(cfg, n, pc.ENV_SEED)
+    obs_in = np.empty((H, n, cfg.obs_dim), np.float32)
+    actions = np.empty((H, n, cfg.act_dim), np.float32)
+    outs = dict(obs=np.empty((H, n, cfg.obs_dim), np.float32), terminated=np.empty((H, n), np.uint8),
+                truncated=np.empty((H, n), np.uint8), info=np.empty((H, n, 3), np.int32))
+    o = orc.observe()
+    for t in range(H):
+        obs_in[t] = o
+        actions[t] = policy.reference(o).astype(np.float32)
+        s = orc.step(actions[t])
+        for k in outs:
+            outs[k][t] = s[k]
+        o = s["obs"]
+    orc.close()
+    for a in (f64, i32, obs_in, actions, *outs.values()):
+        a.setflags(write=False)
+    return cfg, policy, f64, i32, obs_in, actions, outs
+
+
+def assert_closed_loop_events(name, ev, policy, actions):
+    """What a closed-loop case must show on the oracle: a wall termination, a truncation, a wavefront-step in which finished
+    and unfinished lanes mix, and actions over most of the output range."""
+    assert ev["wall"] >= 1 and ev["truncated"] >= 1 and ev["mixed_wave_steps"] >= 1, f"{name}: {ev}"
+    s = squashed(policy, actions)
+    nozzle = s[..., -1]                      # the nozzle component (the only one with forced breathing)
+    assert nozzle.min() <= -ACTION_SPREAD and nozzle.max() >= ACTION_SPREAD, f"{name}: actions span [{nozzle.min()}, {nozzle.max()}]"

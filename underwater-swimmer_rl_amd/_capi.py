@@ -33,6 +33,7 @@ EXPORTS = (
     "salp_vec_clear_stats", "salp_vec_global_step", "salp_vec_set_base_num_food", "salp_vec_base_num_food",
     "salp_vec_reseed", "salp_vec_last_launch", "salp_vec_last_kernel_resources", "salp_vec_last_launch_signatures",
     "salp_vec_record_width", "salp_vec_step_packed", "salp_vec_rollout_packed",
+    "salp_policy_words", "salp_policy_create", "salp_policy_update", "salp_policy_destroy", "salp_vec_rollout_policy",
 )
 
 
@@ -104,6 +105,14 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         L.salp_vec_record_width.argtypes = [vp, u32]
         L.salp_vec_step_packed.argtypes = [vp, vp, vp, u32, vp]
         L.salp_vec_rollout_packed.argtypes = [vp, vp, i32, vp, vp, u32, vp]
+    if path is None or hasattr(L, "salp_vec_rollout_policy"):
+        from .policy import CPolicyDesc
+        L.salp_policy_words.argtypes = [vp, ctypes.POINTER(CPolicyDesc)]
+        L.salp_policy_create.argtypes = [vp, ctypes.POINTER(CPolicyDesc), vp, u32, vp, ctypes.POINTER(vp)]
+        L.salp_policy_update.argtypes = [vp, vp, u32, vp]
+        L.salp_policy_destroy.argtypes = [vp]
+        L.salp_policy_destroy.restype = None
+        L.salp_vec_rollout_policy.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, u32, vp]
     L.salp_vec_global_step.argtypes = [vp]
     L.salp_vec_global_step.restype = i64
     L.salp_vec_set_base_num_food.argtypes = [vp, i32]
@@ -141,6 +150,8 @@ class SalpLib:
 
     def close(self):
         if getattr(self, "_h", None):
+            for p in list(getattr(self, "_policies", ())):     # a policy goes before its handle
+                p.close()
             self.lib.salp_vec_destroy(self._h)
             self._h = ctypes.c_void_p()
 
@@ -190,6 +201,39 @@ class SalpLib:
         check(self.lib, self.lib.salp_vec_rollout_packed(self._h, self._ptr(act), int(horizon), self._ptr(rec),
                                                          self._ptr(act_out), flags, ctypes.c_void_p(stream)),
               "salp_vec_rollout_packed")
+
+    def policy_words(self, policy) -> int:
+        """salp_policy_words: float32 words of one policy of this shape on this handle (raises for a shape out of range)."""
+        d = policy.desc()
+        rc = self.lib.salp_policy_words(self._h, ctypes.byref(d))
+        if rc < 0:
+            check(self.lib, rc, "salp_policy_words")
+        return int(rc)
+
+    def policy_create(self, policy, weights=None, flags=0, stream=0) -> "PolicyHandle":
+        """salp_policy_create for an `MLPPolicy` (shape and, unless `weights` is given, its packed float32 weights; `weights`
+        with SALP_DEVICE_PTRS: a device block in the public layout [P, words])."""
+        d = policy.desc()
+        w = policy.pack() if weights is None else weights
+        h = ctypes.c_void_p()
+        check(self.lib, self.lib.salp_policy_create(self._h, ctypes.byref(d), self._ptr(w), flags, ctypes.c_void_p(stream),
+                                                    ctypes.byref(h)), "salp_policy_create")
+        ph = PolicyHandle(self, h, policy.n_policies, int(policy.words))
+        if not hasattr(self, "_policies"):
+            self._policies = []
+        self._policies.append(ph)
+        return ph
+
+    def policy_update(self, handle: "PolicyHandle", weights, flags=0, stream=0):
+        """salp_policy_update: float32 [P, words] in the public layout; with SALP_DEVICE_PTRS stream-ordered, no allocation."""
+        check(self.lib, self.lib.salp_policy_update(handle._p, self._ptr(weights), flags, ctypes.c_void_p(stream)),
+              "salp_policy_update")
+
+    def rollout_policy(self, handle: "PolicyHandle", horizon, obs, reward, term, trunc, act_out, flags, stream=0):
+        """salp_vec_rollout_policy: the four main outputs are required, act_out may be None."""
+        check(self.lib, self.lib.salp_vec_rollout_policy(self._h, handle._p, int(horizon), self._ptr(obs), self._ptr(reward),
+                                                         self._ptr(term), self._ptr(trunc), self._ptr(act_out), flags,
+                                                         ctypes.c_void_p(stream)), "salp_vec_rollout_policy")
 
     def reseed(self, seed, obs, flags, stream=0):
         """New draw streams keyed by `seed`, every env reset from draw counter 0; no reallocation (capture-safe)."""
@@ -249,3 +293,26 @@ class SalpLib:
     @property
     def global_step(self) -> int:
         return int(self.lib.salp_vec_global_step(self._h))
+
+
+class PolicyHandle:
+    """One salp_policy_t: a policy block on a handle's device (SalpLib.policy_create)."""
+
+    def __init__(self, owner: SalpLib, p, n_policies: int, words: int):
+        self.owner, self._p, self.n_policies, self.words = owner, p, int(n_policies), int(words)
+
+    def update(self, weights, flags=0, stream=0):
+        self.owner.policy_update(self, weights, flags, stream)
+
+    def close(self):
+        if getattr(self, "_p", None):
+            self.owner.lib.salp_policy_destroy(self._p)
+            self._p = ctypes.c_void_p()
+            if self in getattr(self.owner, "_policies", ()):
+                self.owner._policies.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1,0 +1,155 @@
+// salp_policy.h — the in-kernel MLP policy of salp_vec_rollout_policy (include/salp_vec.h "Policy"): the device block's
+// layout, shared by the host (which builds it) and the rollout kernel (which evaluates it once per env-step).
+//
+// Device block, 32-bit words:  [PH_WORDS header][policy 0][policy 1]...  each policy `stride` words, a multiple of 16, so
+// that every 16-word group below starts on a 64-byte boundary.  One policy (IN = obs_dim for the first layer, else the
+// width of the layer before):
+//   per hidden layer, per chunk c of 16 output units:   b[16 c .. 16 c + 15], then for i = 0 .. IN-1 the 16 weights
+//                                                        W[16 c + j][i], j = 0 .. 15        (16 (IN + 1) words per chunk)
+//   tail (16 words):                                     b_last[A], scale[A], shift[A], zero padding
+//   last layer, per action a:                            W_last[a][0 .. IN-1], zero-padded to a multiple of 16 words
+// The weights are wave-uniform (a wavefront never mixes policies), so everything is read through the constant address
+// space with scalar loads (s_load_dwordx16: one load feeds 16 v_fmac with a scalar operand each); the base is made opaque
+// inside policy_eval so that the loads stay in the function instead of being hoisted across the step loop.
+//
+// Arithmetic (fixed, the same in every instantiation): fp32; every unit starts from its bias and adds its inputs in index
+// order with one fmaf each; relu = fmaxf(., 0); tanhf or a clamp to [-1, 1]; then one multiply by scale and one add of
+// shift (two roundings).  The last layer is fused into the chunk loop of the layer before it — chunks and their units
+// are visited in index order, so its sum keeps the same order — and the only activations that are stored are those of
+// the FIRST of two hidden layers: at most 64 VGPRs (indexed at compile time; the widths are run-time values tested per
+// group of 16, wave-uniform).
+#pragma once
+#include <stdint.h>
+
+namespace salp {
+
+enum { PH_NHIDDEN = 0, PH_H0, PH_H1, PH_OUT, PH_STRIDE, PH_GROUP, PH_COUNT, PH_WORDS = 16 };
+enum { POLICY_CHUNK = 16, POLICY_MAX_HIDDEN = 64, POLICY_TAIL_WORDS = 16 };
+
+#ifdef __HIPCC__
+typedef const float __attribute__((address_space(4))) pol_float;
+typedef const int32_t __attribute__((address_space(4))) pol_int;
+typedef float pol_v16 __attribute__((ext_vector_type(16)));
+typedef float pol_v8 __attribute__((ext_vector_type(8)));
+typedef const pol_v16 __attribute__((address_space(4))) pol_v16c;
+typedef const pol_v8 __attribute__((address_space(4))) pol_v8c;
+
+__device__ __forceinline__ pol_v16 pol_load16(pol_float* p) { return *reinterpret_cast<pol_v16c*>(p); }
+__device__ __forceinline__ pol_v8 pol_load8(pol_float* p) { return *reinterpret_cast<pol_v8c*>(p); }
+
+// acc[j] = b[j] + sum_i W[j][i] x[i] over the NIN register inputs, for the chunk whose block starts at `wc`
+template <int NIN>
+__device__ __forceinline__ void policy_chunk_regs(pol_float* wc, const float (&x)[NIN], float (&acc)[POLICY_CHUNK]) {
+  const pol_v16 b = pol_load16(wc);
+#pragma unroll
+  for (int j = 0; j < POLICY_CHUNK; ++j) acc[j] = b[j];
+#pragma unroll
+  for (int i = 0; i < NIN; ++i) {
+    const pol_v16 w = pol_load16(wc + POLICY_CHUNK * (1 + i));
+#pragma unroll
+    for (int j = 0; j < POLICY_CHUNK; ++j) acc[j] = __builtin_fmaf(w[j], x[i], acc[j]);
+  }
+}
+
+// u[a] += sum_j W_last[a][16 c + j] relu'd[j]: the last layer's share of one chunk of its input
+template <int AD>
+__device__ __forceinline__ void policy_last_chunk(pol_float* wl, int row_stride, int c, const float (&v)[POLICY_CHUNK], float (&u)[2]) {
+#pragma unroll
+  for (int a = 0; a < AD; ++a) {
+    const pol_v16 w = pol_load16(wl + a * row_stride + POLICY_CHUNK * c);
+#pragma unroll
+    for (int j = 0; j < POLICY_CHUNK; ++j) u[a] = __builtin_fmaf(w[j], v[j], u[a]);
+  }
+}
+
+// The action of one env from its observation row `x` (OD = 24 floats in registers).  `blk`: the device block;
+// `pol_off`: word offset of this wavefront's policy behind the header (wave-uniform).
+template <int OD, int AD>
+__device__ __forceinline__ void policy_eval(const float* blk, uint32_t pol_off, const float (&x)[OD], float& c0, float& c1) {
+  static_assert(OD == 24, "the policy kernels exist for max_observed_food == 3");
+  const uint64_t adr = (uint64_t)(uintptr_t)blk;
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)adr);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(adr >> 32));
+  pol_int* hd = (pol_int*)(uintptr_t)(((uint64_t)hi << 32) | lo);
+  asm volatile("" : "+s"(hd));
+  const int nh = hd[PH_NHIDDEN], h0 = hd[PH_H0], h1 = hd[PH_H1], out_act = hd[PH_OUT];
+  pol_float* w = (pol_float*)hd + PH_WORDS + (uint32_t)__builtin_amdgcn_readfirstlane((int)pol_off);
+
+  const int c0n = h0 / POLICY_CHUNK, c1n = h1 / POLICY_CHUNK;
+  const int l0_words = c0n * POLICY_CHUNK * (OD + 1);
+  const int l1_words = c1n * POLICY_CHUNK * (h0 + 1);
+  pol_float* tail = w + (nh >= 1 ? l0_words : 0) + (nh >= 2 ? l1_words : 0);
+  pol_float* wl = tail + POLICY_TAIL_WORDS;
+  const pol_v8 tl = pol_load8(tail);      // b_last[AD], scale[AD], shift[AD]
+  float u[2] = {tl[0], AD == 2 ? tl[1] : 0.f};
+
+  if (nh == 0) {
+#pragma unroll
+    for (int a = 0; a < AD; ++a) {
+      const pol_v16 wa = pol_load16(wl + a * 32);
+      const pol_v8 wb = pol_load8(wl + a * 32 + 16);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) u[a] = __builtin_fmaf(wa[i], x[i], u[a]);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) u[a] = __builtin_fmaf(wb[i], x[16 + i], u[a]);
+    }
+  } else if (nh == 1) {
+#pragma unroll 1
+    for (int c = 0; c < c0n; ++c) {
+      float acc[POLICY_CHUNK];
+      policy_chunk_regs<OD>(w + c * (POLICY_CHUNK * (OD + 1)), x, acc);
+#pragma unroll
+      for (int j = 0; j < POLICY_CHUNK; ++j) acc[j] = fmaxf(acc[j], 0.f);
+      policy_last_chunk<AD>(wl, h0, c, acc, u);
+    }
+  } else {
+    float h[POLICY_MAX_HIDDEN];
+#pragma unroll
+    for (int g = 0; g < POLICY_MAX_HIDDEN / POLICY_CHUNK; ++g) {
+      if (g < c0n) {
+        float acc[POLICY_CHUNK];
+        policy_chunk_regs<OD>(w + g * (POLICY_CHUNK * (OD + 1)), x, acc);
+#pragma unroll
+        for (int j = 0; j < POLICY_CHUNK; ++j) h[POLICY_CHUNK * g + j] = fmaxf(acc[j], 0.f);
+      } else {
+#pragma unroll
+        for (int j = 0; j < POLICY_CHUNK; ++j) h[POLICY_CHUNK * g + j] = 0.f;
+      }
+    }
+    pol_float* w1 = w + l0_words;
+    const int chunk_words = POLICY_CHUNK * (h0 + 1);
+#pragma unroll 1
+    for (int c = 0; c < c1n; ++c) {
+      pol_float* wc = w1 + c * chunk_words;
+      float acc[POLICY_CHUNK];
+      const pol_v16 b = pol_load16(wc);
+#pragma unroll
+      for (int j = 0; j < POLICY_CHUNK; ++j) acc[j] = b[j];
+#pragma unroll
+      for (int g = 0; g < POLICY_MAX_HIDDEN / POLICY_CHUNK; ++g) {
+        if (g < c0n) {
+#pragma unroll
+          for (int ii = 0; ii < POLICY_CHUNK; ++ii) {
+            const int i = POLICY_CHUNK * g + ii;
+            const pol_v16 wv = pol_load16(wc + POLICY_CHUNK * (1 + i));
+#pragma unroll
+            for (int j = 0; j < POLICY_CHUNK; ++j) acc[j] = __builtin_fmaf(wv[j], h[i], acc[j]);
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < POLICY_CHUNK; ++j) acc[j] = fmaxf(acc[j], 0.f);
+      policy_last_chunk<AD>(wl, h1, c, acc, u);
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < AD; ++a) {
+    const float v = out_act ? fminf(fmaxf(u[a], -1.0f), 1.0f) : tanhf(u[a]);
+    u[a] = v * tl[AD + a] + tl[2 * AD + a];
+  }
+  c0 = u[0];
+  if (AD == 2) c1 = u[1];
+}
+#endif  // __HIPCC__
+
+}  // namespace salp

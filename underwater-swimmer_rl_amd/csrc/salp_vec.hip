@@ -25,6 +25,7 @@
 #include "salp_device.h"
 #include "salp_food_lds.h"
 #include "salp_food_reg.h"
+#include "salp_policy.h"
 
 using namespace salp;
 
@@ -40,7 +41,12 @@ constexpr int kWave = 64;
 //   literal-constant unpredicated kernels (half-height tile, session 19), else 2;  generic K: 2 (12 slots) / 1 (16 slots).
 //   The packed signature keeps every row (its 8-slot kernel keeps the six-column tile, TAILREG below); its one-wavefront
 //   predicated 8-slot twin has the seven-column tile, 45 KB: 3.
-constexpr int waves_per_simd(int fmax, int kmax, bool std_consts, bool ragged, int sig) {
+//   The policy kernels (ACT_POLICY): the first hidden layer's activations are up to 64 VGPRs on top of the step's own.  One food
+//   and 4 slots: 2 (256 registers, no scratch).  8 slots and more, and every predicated launch: 1 — at 2 they spilled 50-580 B
+//   per lane to scratch inside the step loop; at 1 the wavefront owns the SIMD's 512 registers and what does not fit in the
+//   256 VGPRs is parked in AGPRs (v_accvgpr_write / _read), not in memory (profiles/r05/policy_kernel_resources.txt).
+constexpr int waves_per_simd(int fmax, int kmax, bool std_consts, bool ragged, int sig, bool policy = false) {
+  if (policy) return (ragged || fmax >= 8) ? 1 : 2;
   if (sig == 3 && ragged && kmax == 3 && fmax == 8) return 3;
   return fmax <= 1 ? 4 : (kmax != 3 ? (fmax <= 12 ? 2 : 1) : (fmax <= 8 ? 4 : (fmax <= 12 ? 3 : ((std_consts && !ragged) ? 3 : 2))));
 }
@@ -57,7 +63,7 @@ __device__ __forceinline__ int wave_sum(int v) {
 }
 
 struct IOPtrs {
-  const float* act;       // [H][n][act_dim] or null (device-generated)
+  const float* act;       // [H][n][act_dim] or null (device-generated); ACT_POLICY: the policy's device block (salp_policy.h)
   float* obs;             // [H][n][obs_dim]
   float* reward;          // [H][n]
   uint8_t* terminated;    // [H][n]
@@ -96,10 +102,18 @@ struct ColdBlock {
 // GEN = actions are generated in the kernel (salp_vec_rollout with act == NULL): no read stream at
 // all — the per-step 256-B action read costs the write stream ~10 % (HBM read/write turnarounds,
 // profiles/r01/ab_notes.md) — and, if act_out is given, the actions are written out instead.
-template <int FMAX, int KMAX, bool FORCED, bool STD, int SIG, bool RAGGED, bool GEN>
-__global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG)) void salp_rollout_kernel(DevParams P_arg, DevState S, IOPtrs io, int H, int64_t env_begin, int64_t env_end, const ColdBlock* __restrict__ cold) {
+// ACT = ACT_POLICY: the actions are a function of the observations (salp_vec_rollout_policy): the action of step 0 is the
+// policy (salp_policy.h) applied to the env's current observation, computed in the prologue with the step's own
+// functions; the action of step t + 1 is the policy applied to the row just written to obs[t], evaluated from the
+// registers behind the tile flush, while the row stores drain.  No read stream; act_out as with ACT_GEN.
+enum { ACT_READ = 0, ACT_GEN = 1, ACT_POLICY = 2 };
+template <int FMAX, int KMAX, bool FORCED, bool STD, int SIG, bool RAGGED, int ACT>
+__global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG, ACT == ACT_POLICY)) void salp_rollout_kernel(DevParams P_arg, DevState S, IOPtrs io, int H, int64_t env_begin, int64_t env_end, const ColdBlock* __restrict__ cold) {
   // STD = false: where the hot path's constants come from (open_consts, salp_device.h) — the device copy, function by
   // function, for the 4- and 8-slot kernels; the by-value launch parameters for the others
+  constexpr bool GEN = ACT == ACT_GEN;
+  constexpr bool POLICY = ACT == ACT_POLICY;
+  static_assert(!POLICY || (SIG == 1 && KMAX == 3), "policy kernels: the main-only signature, K = 3");
   constexpr bool MEMC = !STD && KMAX == 3 && (FMAX == 4 || FMAX == 8);
   DevParams P_pol = P_arg;
   P_pol.use_mem = MEMC ? 1 : 0;
@@ -262,9 +276,54 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
 
   float a0 = 0.f, a1 = 0.f;
   U4 aw0 = {0u, 0u, 0u, 0u}, aw1 = {0u, 0u, 0u, 0u};   // GEN: the current Philox block of each action component
-  if (!GEN) {
+  if (ACT == ACT_READ) {
     a0 = io.act[envc * AD];
     a1 = FORCED ? 0.f : io.act[envc * AD + 1];
+  }
+  uint32_t pol_off = 0u;    // POLICY: word offset of this wavefront's policy in the block (wave-uniform)
+  if constexpr (POLICY) {
+    if (rows > 0) {
+      pol_int* const hd = (pol_int*)(uintptr_t)io.act;
+      const uint32_t group = (uint32_t)hd[PH_GROUP], npol = (uint32_t)hd[PH_COUNT];
+      uint32_t pi = (uint32_t)env0 / group;          // env i runs policy i / (n_envs / P)
+      pi = pi < npol ? pi : npol - 1u;
+      pol_off = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pi * (uint32_t)hd[PH_STRIDE]));
+      // the env's current observation, as the end of a step forms it (below), from the loaded state: the SAME bits as the
+      // row of the step that left this state, so that a rollout cut into several calls takes the actions of one call.
+      // The one thing in a row that the state does not spell out is which bearing polynomial its nearest food went
+      // through: the step hands the reward's own (PRECISE) bearing to the row (`have_rel`) unless the food set or the
+      // episode changed behind it — per lane in the one-food kernels (a capture or an autoreset: both leave
+      // steps_since_food == 0, which no other step does), for the whole wavefront in the register-food kernels (any lane
+      // that captured or finished sends the wavefront through the rare region, which selects again for every lane;
+      // `finished` is the step's own test on the state it left).  A state that no step left (reset, set_state) may
+      // fall either way.
+      double ea, eb;
+      shape_of<STD>(P, e.packed, e.water, ea, eb);
+      const double r0 = pymax(ea, eb);
+      float ob0[12 + 4 * KMAX];
+      if constexpr (REGF) {
+        SALP_CONSTS;
+        select_foods_reg<FMAX, KMAX, false, true>(e, ff, mir, K, (STD ? StdConsts::tie_c0 : P.tie_c0), fq, nlive);
+        const double mg = CV(margin);
+        const bool hit = (e.x - r0 <= mg) || (e.x + r0 >= CV(wall_hi_x)) || (e.y - r0 <= mg) || (e.y + r0 >= CV(wall_hi_y));
+        const bool finished = hit || (e.ssf > P.max_steps_wo_food) || (!P.respawn && nlive == 0);
+        const bool have_rel0 = !__any(e.ssf == 0 || finished) && (fq.idx[0] >= 0);
+        const float rel0 = relative_heading<true>(fq.by[0], fq.bx[0], (float)e.th);
+        observe_lds<KMAX, STD>(e, P, r0, K, fq, nlive, have_rel0, rel0, ob0);
+      } else {
+        bool have_rel0 = false;
+        float rel0 = 0.f;
+        if (P.prox_w > 0) {
+          const Nearest g = nearest_food(e);
+          if (g.any) {
+            rel0 = relative_heading<true>((float)g.dy, (float)g.dx, (float)e.th);
+            have_rel0 = e.ssf != 0;
+          }
+        }
+        observe<FMAX, KMAX, STD>(e, P, r0, have_rel0, rel0, ob0);
+      }
+      policy_eval<12 + 4 * KMAX, FORCED ? 1 : 2>(io.act, pol_off, ob0, a0, a1);
+    }
   }
   // Everything loaded so far is complete before the loop is entered: otherwise the waitcnt pass keeps
   // a conservative `s_waitcnt vmcnt(1)` on the first use of the action inside the loop (for the entry
@@ -299,6 +358,11 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
         c0 = (float)(w0 >> 8) * 5.9604644775390625e-8f;                     // inhale control in [0, 1)
         c1 = (float)(w1 >> 8) * 1.1920928955078125e-7f - 1.0f;
       }
+      if (io.act_out && active) {
+        io.act_out[(rowbase + env) * AD] = c0;
+        if (!FORCED) io.act_out[(rowbase + env) * AD + 1] = c1;
+      }
+    } else if (POLICY) {
       if (io.act_out && active) {
         io.act_out[(rowbase + env) * AD] = c0;
         if (!FORCED) io.act_out[(rowbase + env) * AD + 1] = c1;
@@ -580,6 +644,10 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       }
+      // the next step's action from this step's row, while the row stores are in flight (the last step needs none)
+      if constexpr (POLICY) {
+        if (t + 1 < Hrun) policy_eval<12 + 4 * KMAX, FORCED ? 1 : 2>(io.act, pol_off, ob, a0, a1);
+      }
     }
     // One-food kernel (write-bound): drain this step's stores before the next step.  Measured
     // (profiles/r01/ab_notes.md): letting stores run ahead (vmcnt(9)) is 2-6 % SLOWER than draining —
@@ -818,6 +886,19 @@ struct salp_vec {
   const void* last_kernel;   // the main (else the predicated) kernel of the most recent launch: salp_vec_last_kernel_resources
 };
 
+struct salp_policy {
+  salp_vec* h;               // the handle it is bound to
+  salp_policy_desc_t d;
+  int device, obs_dim, act_dim;
+  int64_t n;                 // the handle's env count (fixes env -> policy)
+  int words;                 // public words of one policy
+  int stride;                // words of one policy in the device block (salp_policy.h)
+  float* block;              // device: header + P policies, what the kernel reads
+  float* pub;                // device: staging of the public layout [P][words] (host-pointer create / update)
+  int32_t* map;              // device: word k of a policy in the block <- public word map[k] (-1: zero)
+  hipStream_t last_stream;   // the stream of the most recent create / update
+};
+
 namespace {
 
 DevParams make_params(const salp_config_t& c, int64_t n, int64_t pitch, uint64_t seed, int64_t base) {
@@ -889,22 +970,25 @@ typedef void (*reset_fn)(DevParams, DevState, const uint8_t*, float*, int);
 // kSigPacked = ONE stream of transition records (salp_vec_step_packed / salp_vec_rollout_packed): no per-lane reward / flag /
 // info stores at all; unpredicated and predicated, K = 3 and generic K; no in-kernel action generation.
 enum { kSigPartial = 0, kSigMain = 1, kSigExtras = 2, kSigPacked = 3 };
-template <int FMAX, int KMAX, bool FORCED, bool STD, bool RAGGED, bool GEN>
+template <int FMAX, int KMAX, bool FORCED, bool STD, bool RAGGED, int ACT>
 rollout_fn pick_sig(int sig) {
-  if constexpr (GEN) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, true>;
+  if constexpr (ACT != ACT_READ) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, ACT>;
   else {
-    if (sig == kSigMain) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, false>;
-    if (sig == kSigPacked) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigPacked, RAGGED, false>;
+    if (sig == kSigMain) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, ACT_READ>;
+    if (sig == kSigPacked) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigPacked, RAGGED, ACT_READ>;
     if constexpr (!RAGGED)
-      if (sig == kSigExtras) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigExtras, false, false>;
-    return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigPartial, RAGGED, false>;
+      if (sig == kSigExtras) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigExtras, false, ACT_READ>;
+    return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigPartial, RAGGED, ACT_READ>;
   }
 }
+// `act`: where the actions come from (ACT_READ / ACT_GEN / ACT_POLICY)
 template <int FMAX, int KMAX, bool STD, bool RAGGED>
-rollout_fn pick_rollout(bool forced, int sig, bool gen) {
-  if (sig == kSigMain && gen)   // in-kernel action generation exists for the main-only output signature
-    return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, true>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, true>(sig);
-  return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, false>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, false>(sig);
+rollout_fn pick_rollout(bool forced, int sig, int act) {
+  if (sig == kSigMain && act == ACT_POLICY)   // the in-kernel policy, like the in-kernel generation, exists for the main-only output signature
+    return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, ACT_POLICY>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, ACT_POLICY>(sig);
+  if (sig == kSigMain && act == ACT_GEN)
+    return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, ACT_GEN>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, ACT_GEN>(sig);
+  return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, ACT_READ>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, ACT_READ>(sig);
 }
 
 // K = 3 (every preset): kernels by food-slot count, with the reference's constants as literals (STD) or — any other
@@ -914,7 +998,7 @@ rollout_fn pick_rollout(bool forced, int sig, bool gen) {
 bool can_generate_in_kernel(const salp_vec* h, bool full) { return full && h->kmax == 3; }
 
 template <bool STD, bool RAGGED>
-rollout_fn rollout_kernel_k3(const salp_vec* h, bool forced, int sig, bool gen) {
+rollout_fn rollout_kernel_k3(const salp_vec* h, bool forced, int sig, int gen) {
   if (h->fmax == 1) return pick_rollout<1, 3, STD, RAGGED>(forced, sig, gen);
   if (h->fmax == 4) return pick_rollout<4, 3, STD, RAGGED>(forced, sig, gen);
   if (h->fmax == 8) return pick_rollout<8, 3, STD, RAGGED>(forced, sig, gen);
@@ -922,22 +1006,22 @@ rollout_fn rollout_kernel_k3(const salp_vec* h, bool forced, int sig, bool gen) 
   return pick_rollout<16, 3, STD, RAGGED>(forced, sig, gen);
 }
 template <bool RAGGED>
-rollout_fn rollout_kernel_for(const salp_vec* h, int sig, bool gen) {
+rollout_fn rollout_kernel_for(const salp_vec* h, int sig, int gen) {
   const bool forced = h->P.forced != 0;
   if (h->kmax == 3)
     return h->std_consts ? rollout_kernel_k3<true, RAGGED>(h, forced, sig, gen) : rollout_kernel_k3<false, RAGGED>(h, forced, sig, gen);
   if (sig == kSigPacked) {
     if (h->fmax <= 12)
-      return forced ? (rollout_fn)salp_rollout_kernel<12, 8, true, false, kSigPacked, RAGGED, false>
-                    : (rollout_fn)salp_rollout_kernel<12, 8, false, false, kSigPacked, RAGGED, false>;
-    return forced ? (rollout_fn)salp_rollout_kernel<16, 8, true, false, kSigPacked, RAGGED, false>
-                  : (rollout_fn)salp_rollout_kernel<16, 8, false, false, kSigPacked, RAGGED, false>;
+      return forced ? (rollout_fn)salp_rollout_kernel<12, 8, true, false, kSigPacked, RAGGED, ACT_READ>
+                    : (rollout_fn)salp_rollout_kernel<12, 8, false, false, kSigPacked, RAGGED, ACT_READ>;
+    return forced ? (rollout_fn)salp_rollout_kernel<16, 8, true, false, kSigPacked, RAGGED, ACT_READ>
+                  : (rollout_fn)salp_rollout_kernel<16, 8, false, false, kSigPacked, RAGGED, ACT_READ>;
   }
   if (h->fmax <= 12)   // K != 3 with up to 12 foods: the register-food form of the generic instantiation (2 wavefronts per SIMD, not 1)
-    return forced ? (rollout_fn)salp_rollout_kernel<12, 8, true, false, kSigPartial, RAGGED, false>
-                  : (rollout_fn)salp_rollout_kernel<12, 8, false, false, kSigPartial, RAGGED, false>;
-  return forced ? (rollout_fn)salp_rollout_kernel<16, 8, true, false, kSigPartial, RAGGED, false>
-                : (rollout_fn)salp_rollout_kernel<16, 8, false, false, kSigPartial, RAGGED, false>;
+    return forced ? (rollout_fn)salp_rollout_kernel<12, 8, true, false, kSigPartial, RAGGED, ACT_READ>
+                  : (rollout_fn)salp_rollout_kernel<12, 8, false, false, kSigPartial, RAGGED, ACT_READ>;
+  return forced ? (rollout_fn)salp_rollout_kernel<16, 8, true, false, kSigPartial, RAGGED, ACT_READ>
+                : (rollout_fn)salp_rollout_kernel<16, 8, false, false, kSigPartial, RAGGED, ACT_READ>;
 }
 template <bool STD>
 reset_fn reset_kernel_k3(const salp_vec* h) {
@@ -989,10 +1073,11 @@ struct Bump {  // carve sub-buffers out of the staging allocation
 };
 
 // packed: io.obs is a record block (kSigPacked), io.final_obs non-NULL asks for the terminal-observation tail
-int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, bool packed = false) {
+// policy: io.act is a policy's device block (ACT_POLICY; the caller has checked K = 3 and the four main outputs)
+int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, bool packed = false, bool policy = false) {
   const bool main_outputs = io.obs && io.reward && io.terminated && io.truncated;
   const int sig = packed ? kSigPacked : (!main_outputs ? kSigPartial : ((io.final_obs || io.info) ? kSigExtras : kSigMain));
-  const bool gen = io.act == nullptr;               // only reached when can_generate_in_kernel()
+  const int gen = policy ? ACT_POLICY : (io.act == nullptr ? ACT_GEN : ACT_READ);   // ACT_GEN: only reached when can_generate_in_kernel()
   // envs in full wavefronts: unpredicated kernel
   int64_t n_full = h->n / kWave * kWave;
   // A small ragged batch (step-per-launch acting loops) is launch-bound: one predicated launch over the whole
@@ -1023,6 +1108,59 @@ int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, bool pa
                        n_full, h->n, (const ColdBlock*)h->cold);
     HIP_TRY(hipGetLastError());
   }
+  return SALP_OK;
+}
+
+}  // namespace
+
+namespace {
+
+// public layout -> device block of P policies (salp_policy.h): one thread per word of the block
+__global__ __launch_bounds__(kBlock) void salp_policy_relayout_kernel(float* __restrict__ block, const float* __restrict__ pub,
+                                                                      const int32_t* __restrict__ map, int stride, int words, int64_t total) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= total) return;
+  const int64_t p = i / stride;
+  const int m = map[i - p * stride];
+  block[PH_WORDS + i] = m >= 0 ? pub[p * words + m] : 0.f;
+}
+
+// The descriptor's ranges (include/salp_vec.h).  On success *words = public words of one policy.
+int check_policy_desc(const salp_vec* h, const salp_policy_desc_t* d, int* words) {
+  if (!h || !d) return fail(SALP_ERR_INVALID, "handle/desc is NULL");
+  if (d->struct_size != sizeof(salp_policy_desc_t)) return fail(SALP_ERR_INVALID, "salp_policy_desc_t.struct_size mismatch");
+  if (h->kmax != 3) return fail(SALP_ERR_INVALID, "policies need a handle with max_observed_food == 3");
+  if (d->n_hidden < 0 || d->n_hidden > 2) return fail(SALP_ERR_INVALID, "n_hidden must be 0, 1 or 2");
+  for (int l = 0; l < 2; ++l) {
+    const int w = d->hidden[l];
+    if (l < d->n_hidden ? (w < POLICY_CHUNK || w > POLICY_MAX_HIDDEN || w % POLICY_CHUNK) : (w != 0))
+      return fail(SALP_ERR_INVALID, "hidden widths must be multiples of 16 in [16, 64] (unused entries 0)");
+  }
+  if (d->out_activation != SALP_POLICY_OUT_TANH && d->out_activation != SALP_POLICY_OUT_CLIP)
+    return fail(SALP_ERR_INVALID, "out_activation must be SALP_POLICY_OUT_TANH or SALP_POLICY_OUT_CLIP");
+  if (d->n_policies < 1) return fail(SALP_ERR_INVALID, "n_policies must be >= 1");
+  if (d->n_policies > 1 && (h->n % d->n_policies != 0 || (h->n / d->n_policies) % kWave != 0))
+    return fail(SALP_ERR_INVALID, "n_policies > 1 needs n_envs % P == 0 and (n_envs / P) % 64 == 0");
+  int in = h->obs_dim, w = 0;
+  for (int l = 0; l < d->n_hidden; ++l) { w += d->hidden[l] * in + d->hidden[l]; in = d->hidden[l]; }
+  w += h->act_dim * in + 3 * h->act_dim;
+  if (words) *words = w;
+  return SALP_OK;
+}
+
+int policy_upload(salp_policy* pol, const float* weights, uint32_t flags, hipStream_t st) {
+  const size_t pub_b = (size_t)pol->d.n_policies * pol->words * sizeof(float);
+  pol->last_stream = st;
+  const float* src = weights;
+  if (!(flags & SALP_DEVICE_PTRS)) {
+    HIP_TRY(hipMemcpyAsync(pol->pub, weights, pub_b, hipMemcpyHostToDevice, st));
+    src = pol->pub;
+  }
+  const int64_t total = (int64_t)pol->d.n_policies * pol->stride;
+  hipLaunchKernelGGL(salp_policy_relayout_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                     pol->block, src, (const int32_t*)pol->map, pol->stride, pol->words, total);
+  HIP_TRY(hipGetLastError());
+  if (!(flags & SALP_DEVICE_PTRS)) HIP_TRY(hipStreamSynchronize(st));
   return SALP_OK;
 }
 
@@ -1405,6 +1543,144 @@ int salp_vec_step_packed(salp_vec_t* h, const float* act, float* rec, uint32_t f
 int salp_vec_rollout_packed(salp_vec_t* h, const float* act, int32_t horizon, float* rec, float* act_out,
                             uint32_t flags, void* stream) {
   return packed_impl(h, act, horizon, rec, act_out, flags, stream);
+}
+
+int salp_policy_words(const salp_vec_t* h, const salp_policy_desc_t* desc) {
+  int words = 0;
+  const int rc = check_policy_desc(h, desc, &words);
+  return rc != SALP_OK ? rc : words;
+}
+
+void salp_policy_destroy(salp_policy_t* pol) {
+  if (!pol) return;
+  DeviceScope dev_scope;
+  (void)dev_scope.enter(pol->device);
+  (void)hipStreamSynchronize(pol->last_stream);        // the policy's own uploads ...
+  (void)hipStreamSynchronize(pol->h->last_stream);     // ... and the handle's launches that read the block (hipFree does not wait on non-blocking streams)
+  if (pol->block) (void)hipFree(pol->block);
+  if (pol->pub) (void)hipFree(pol->pub);
+  if (pol->map) (void)hipFree(pol->map);
+  delete pol;
+}
+
+int salp_policy_create(salp_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags, void* stream,
+                       salp_policy_t** out) {
+  if (!out) return fail(SALP_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  int words = 0;
+  int rc = check_policy_desc(h, desc, &words);
+  if (rc != SALP_OK) return rc;
+  if (!weights) return fail(SALP_ERR_INVALID, "weights is NULL");
+  DeviceScope dev_scope;
+  HIP_TRY(dev_scope.enter(h->device));
+  salp_policy* pol = new (std::nothrow) salp_policy();
+  if (!pol) return fail(SALP_ERR_OOM, "host allocation failed");
+  memset(pol, 0, sizeof(*pol));
+  pol->h = h; pol->d = *desc; pol->device = h->device; pol->obs_dim = h->obs_dim; pol->act_dim = h->act_dim; pol->n = h->n;
+  pol->words = words;
+  // word k of a policy in the device block <- public word map[k] (salp_policy.h for the block, salp_vec.h for the public layout)
+  const int AD = h->act_dim, nh = desc->n_hidden;
+  std::string mapbuf;      // int32 entries
+  auto push = [&](int32_t v) { mapbuf.append(reinterpret_cast<const char*>(&v), sizeof(v)); };
+  int in = h->obs_dim, pubo = 0;
+  for (int l = 0; l < nh; ++l) {
+    const int O = desc->hidden[l], Wp = pubo, bp = pubo + O * in;
+    for (int c = 0; c < O / POLICY_CHUNK; ++c) {
+      for (int j = 0; j < POLICY_CHUNK; ++j) push(bp + c * POLICY_CHUNK + j);
+      for (int i = 0; i < in; ++i)
+        for (int j = 0; j < POLICY_CHUNK; ++j) push(Wp + (c * POLICY_CHUNK + j) * in + i);
+    }
+    pubo = bp + O; in = O;
+  }
+  {
+    const int Wl = pubo, bl = pubo + AD * in, sc = bl + AD, sh = sc + AD;
+    for (int k = 0; k < POLICY_TAIL_WORDS; ++k) push(k < AD ? bl + k : (k < 2 * AD ? sc + k - AD : (k < 3 * AD ? sh + k - 2 * AD : -1)));
+    const int rs = (in + POLICY_CHUNK - 1) / POLICY_CHUNK * POLICY_CHUNK;    // 24 -> 32 for the linear policy
+    for (int a = 0; a < AD; ++a)
+      for (int i = 0; i < rs; ++i) push(i < in ? Wl + a * in + i : -1);
+  }
+  pol->stride = (int)(mapbuf.size() / sizeof(int32_t));     // every piece above is a multiple of 16 words
+  const size_t block_b = ((size_t)PH_WORDS + (size_t)desc->n_policies * pol->stride) * sizeof(float);
+  const size_t pub_b = (size_t)desc->n_policies * words * sizeof(float);
+  hipError_t e = hipMalloc((void**)&pol->block, block_b);
+  if (e == hipSuccess) e = hipMalloc((void**)&pol->pub, pub_b);
+  if (e == hipSuccess) e = hipMalloc((void**)&pol->map, mapbuf.size());
+  if (e == hipSuccess) e = hipMemcpy(pol->map, mapbuf.data(), mapbuf.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    int32_t hd[PH_WORDS];
+    memset(hd, 0, sizeof(hd));
+    hd[PH_NHIDDEN] = nh; hd[PH_H0] = desc->hidden[0]; hd[PH_H1] = desc->hidden[1]; hd[PH_OUT] = desc->out_activation;
+    hd[PH_STRIDE] = pol->stride; hd[PH_COUNT] = desc->n_policies;
+    hd[PH_GROUP] = desc->n_policies > 1 ? (int32_t)(h->n / desc->n_policies) : 0x7FFFFFFF;
+    e = hipMemcpy(pol->block, hd, sizeof(hd), hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) {
+    const std::string m = std::string("hipMalloc/hipMemcpy(policy): ") + hipGetErrorString(e);
+    salp_policy_destroy(pol);
+    return fail(e == hipErrorOutOfMemory ? SALP_ERR_OOM : SALP_ERR_HIP, m);
+  }
+  rc = policy_upload(pol, weights, flags, (hipStream_t)stream);
+  if (rc != SALP_OK) { const std::string m = g_err; salp_policy_destroy(pol); g_err = m; return rc; }
+  *out = pol;
+  return SALP_OK;
+}
+
+int salp_policy_update(salp_policy_t* pol, const float* weights, uint32_t flags, void* stream) {
+  if (!pol || !weights) return fail(SALP_ERR_INVALID, "policy/weights is NULL");
+  DeviceScope dev_scope;
+  HIP_TRY(dev_scope.enter(pol->device));
+  return policy_upload(pol, weights, flags, (hipStream_t)stream);
+}
+
+int salp_vec_rollout_policy(salp_vec_t* h, const salp_policy_t* pol, int32_t H, float* obs, float* reward,
+                            uint8_t* terminated, uint8_t* truncated, float* act_out, uint32_t flags, void* stream) {
+  if (!h || !pol) return fail(SALP_ERR_INVALID, "handle/policy is NULL");
+  if (pol->h != h || pol->device != h->device || pol->obs_dim != h->obs_dim || pol->act_dim != h->act_dim || pol->n != h->n)
+    return fail(SALP_ERR_INVALID, "the policy belongs to another handle (or other dimensions)");
+  if (h->kmax != 3) return fail(SALP_ERR_INVALID, "policies need a handle with max_observed_food == 3");
+  if (H <= 0) return fail(SALP_ERR_INVALID, "horizon must be >= 1");
+  if (!obs || !reward || !terminated || !truncated)
+    return fail(SALP_ERR_INVALID, "obs, reward, terminated and truncated are all required");
+  if (pol->d.n_policies > 1 && (h->n % pol->d.n_policies != 0 || (h->n / pol->d.n_policies) % kWave != 0))
+    return fail(SALP_ERR_INVALID, "n_policies > 1 needs n_envs % P == 0 and (n_envs / P) % 64 == 0");
+  DeviceScope dev_scope;
+  HIP_TRY(dev_scope.enter(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  h->last_stream = st;
+  IOPtrs io;
+  memset(&io, 0, sizeof(io));
+  io.stats = h->stats_enabled ? h->stats : nullptr;
+  io.global_step = h->global_step;
+  io.act = pol->block;
+  if (flags & SALP_DEVICE_PTRS) {
+    io.obs = obs; io.reward = reward; io.terminated = terminated; io.truncated = truncated; io.act_out = act_out;
+    const int rc = launch_rollout(h, io, H, st, false, true);
+    if (rc == SALP_OK) h->global_step += H;
+    return rc;
+  }
+  // host pointers: stage through device memory, synchronous
+  const size_t HN = (size_t)H * (size_t)h->n;
+  const size_t need = 4096 + align_up(HN * h->act_dim * sizeof(float), 256) + align_up(HN * h->obs_dim * sizeof(float), 256) +
+                      align_up(HN * sizeof(float), 256) + 2 * align_up(HN, 256);
+  int rc = ensure_stage(h, need);
+  if (rc != SALP_OK) return rc;
+  Bump b{(char*)h->stage, 0};
+  float* d_aout = act_out ? b.take<float>(HN * h->act_dim) : nullptr;
+  float* d_obs = b.take<float>(HN * h->obs_dim);
+  float* d_rew = b.take<float>(HN);
+  uint8_t* d_term = b.take<uint8_t>(HN);
+  uint8_t* d_trunc = b.take<uint8_t>(HN);
+  io.obs = d_obs; io.reward = d_rew; io.terminated = d_term; io.truncated = d_trunc; io.act_out = d_aout;
+  rc = launch_rollout(h, io, H, st, false, true);
+  if (rc != SALP_OK) return rc;
+  h->global_step += H;
+  HIP_TRY(hipMemcpyAsync(obs, d_obs, HN * h->obs_dim * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(reward, d_rew, HN * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(terminated, d_term, HN, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(truncated, d_trunc, HN, hipMemcpyDeviceToHost, st));
+  if (d_aout) HIP_TRY(hipMemcpyAsync(act_out, d_aout, HN * h->act_dim * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return SALP_OK;
 }
 
 int salp_vec_get_state(salp_vec_t* h, double* f64, int32_t* i32, uint32_t flags, void* stream) {

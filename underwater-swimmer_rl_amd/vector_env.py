@@ -319,12 +319,44 @@ class SalpVectorEnv:
         return dict(obs=obs, reward=rew, terminated=term, truncated=trunc, final_obs=fin,
                     actions=a if a is not None else aout)
 
+    def make_policy(self, policy, weights=None):
+        """An in-kernel policy of this env (`policy.MLPPolicy`, one policy or a population): a `_capi.PolicyHandle` for
+        `rollout_policy`.  `handle.update(w, flags, stream)` takes new weights of the same shape in the public layout
+        (`MLPPolicy.pack()`); with a device tensor and SALP_DEVICE_PTRS it is stream-ordered and allocates nothing."""
+        if (policy.obs_dim, policy.act_dim) != (self.obs_dim, self.act_dim):
+            raise ValueError(f"the policy maps {policy.obs_dim} -> {policy.act_dim}, this env {self.obs_dim} -> {self.act_dim}")
+        policy.check_envs(self.num_envs)
+        return self._lib.policy_create(policy, weights, 0 if weights is None else self._flags, self._stream)
+
+    def rollout_policy(self, policy, horizon: int, want_actions: bool = True, out: Optional[dict] = None) -> dict:
+        """`horizon` closed-loop steps in one kernel launch: every action is `policy` applied to the observation before it
+        (the first one to the current observation).  `policy`: a handle of `make_policy`, or an `MLPPolicy` (a handle is
+        then made and kept for the next call with the same object).  Returns the dict of `rollout` with `actions`
+        ([H, N, act_dim], None without `want_actions`)."""
+        if not isinstance(policy, _capi.PolicyHandle):
+            cache = self.__dict__.setdefault("_policy_cache", {})
+            if id(policy) not in cache:
+                cache[id(policy)] = (policy, self.make_policy(policy))
+            policy = cache[id(policy)][1]
+        H, n = int(horizon), self.num_envs
+        if H < 1:
+            raise ValueError("horizon must be >= 1")
+        out = out or {}
+        obs = out.get("obs") if "obs" in out else self._buf("r_obs", (H, n, self.obs_dim), np.float32)
+        rew = out.get("reward") if "reward" in out else self._buf("r_reward", (H, n), np.float32)
+        term = out.get("terminated") if "terminated" in out else self._buf("r_term", (H, n), np.uint8)
+        trunc = out.get("truncated") if "truncated" in out else self._buf("r_trunc", (H, n), np.uint8)
+        aout = (out.get("actions") if "actions" in out else self._buf("r_act", (H, n, self.act_dim), np.float32)) if want_actions else None
+        self._lib.rollout_policy(policy, H, obs, rew, term, trunc, aout, self._flags, self._stream)
+        return dict(obs=obs, reward=rew, terminated=term, truncated=trunc, final_obs=None, actions=aout)
+
     def observe(self):
         obs = self._buf("obs", (self.num_envs, self.obs_dim), np.float32)
         self._lib.observe(obs, self._flags, self._stream)
         return obs
 
     def close(self):
+        self.__dict__.pop("_policy_cache", None)
         self._lib.close()
         self._bufs.clear()
         self._step_cache = None
