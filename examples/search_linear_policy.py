@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Cross-entropy search over LINEAR swimmer policies on the navigation configuration, the whole population inside the
-rollout kernel: 1024 policies x 64 envs per launch (`SalpVectorEnv.rollout_policy` with a stacked `MLPPolicy`), one launch
+rollout kernel: 1024 policies x 64 envs per launch (`SalpVectorEnv.evaluate_policy` with a stacked `MLPPolicy`), one launch
 per round, the weights refreshed in place between rounds (`handle.update`, no re-allocation).  A policy is
 a = clip(W obs + b, -1, 1) with 25 parameters; its score is the mean return of its 64 envs over `--steps` steps (food reward
-plus time penalty: reaching the food early scores high).  No pass threshold: it prints the best score per round and the
+plus time penalty: reaching the food early scores high).  The launch writes one 32-byte summary record per env and nothing
+per step (`rollout_policy` would write 102 B per env-step to sum one column of it).  No pass threshold: it prints the best score per round and the
 scripted pursuit rule's score on the same envs for comparison.
     python examples/search_linear_policy.py [--policies P] [--envs-per-policy E] [--rounds R] [--steps T]"""
 import argparse
@@ -18,7 +19,7 @@ import torch  # noqa: E402
 from underwater_swimmer_rl_amd import SalpVectorEnv  # noqa: E402
 from underwater_swimmer_rl_amd._capi import SALP_DEVICE_PTRS  # noqa: E402
 from underwater_swimmer_rl_amd.navigation_eval import navigation_config  # noqa: E402
-from underwater_swimmer_rl_amd.policy import MLPPolicy, pursuit_policy  # noqa: E402
+from underwater_swimmer_rl_amd.policy import EVAL_WORDS, MLPPolicy, pursuit_policy  # noqa: E402
 
 
 def population(theta):
@@ -45,10 +46,16 @@ def main():
     handle = env.make_policy(population(theta))
     stream = int(torch.cuda.current_stream(env.device).cuda_stream)
 
+    # output per round: what rollout_policy wrote (obs 96 B + reward 4 B + two flag bytes per env-step) against one record per env
+    per_step, per_env = 4 * env.obs_dim + 4 + 2, 4 * EVAL_WORDS
+    print(f"output bytes per round: {per_step} B x {P} x {E} x {T} = {per_step * P * E * T / 1e9:.3f} GB with rollout_policy, "
+          f"{per_env} B x {P} x {E} = {per_env * P * E / 1e6:.3f} MB with evaluate_policy")
+    record = torch.empty((P * E, EVAL_WORDS), dtype=torch.int32, device=env.device)
+
     def scores():
         env.reset(seed=1)                 # every round (and the baseline) sees the same episodes
-        out = env.rollout_policy(handle, T, want_actions=False)
-        return out["reward"].sum(0).reshape(P, E).mean(1)
+        out = env.evaluate_policy(handle, T, out=record)
+        return out["return_sum"].view(P, E).mean(1)
 
     n_elite = max(4, int(args.elite * P))
     t0 = time.perf_counter()
@@ -62,6 +69,7 @@ def main():
         print(f"round {r}: best {float(s.max()):9.2f}  elite mean {float(s[elite].mean()):9.2f}  population mean {float(s.mean()):9.2f}", flush=True)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    print(f"peak device memory allocated through torch: {torch.cuda.max_memory_allocated(env.device) / 1e6:.1f} MB")
     # the scripted rule on the same envs, every policy slot holding it
     base = pursuit_policy(3.0, env.obs_dim)
     handle.update(np.repeat(base.pack(), P, axis=0))

@@ -292,6 +292,36 @@ void salp_policy_destroy(salp_policy_t* pol);
 int salp_vec_rollout_policy(salp_vec_t* h, const salp_policy_t* pol, int32_t horizon, float* obs, float* reward,
                             uint8_t* terminated, uint8_t* truncated, float* act_out, uint32_t flags, void* stream);
 
+/* Policy evaluation: the closed-loop run of salp_vec_rollout_policy with NO per-step output — one summary record per env,
+ * [n_envs][SALP_EVAL_WORDS] 32-bit words (32 B per env; a device block must be 16-byte aligned), covering the `horizon` steps
+ * of the call.  It replaces `out = rollout_policy(...); score = out.reward.sum(0)` where only totals per env are wanted (the
+ * reference evaluates this way: test_model.py, eval/collect_navigation_data.py run_single_trial keep totals per episode).
+ *   SALP_EVAL_RETURN (words 0-1, float64)        the sum of the step rewards AS THE float32 VALUES reward[t] of
+ *                                                salp_vec_rollout_policy would hold, added in step order in fp64: a host loop
+ *                                                `acc += (double)reward[t]` reproduces it bit for bit
+ *   SALP_EVAL_FIRST_RETURN (words 2-3, float64), SALP_EVAL_FIRST_LENGTH (int32)
+ *                                                the same sum and the step count over the steps up to and including the first
+ *                                                step in which the env finished (terminated or truncated); all steps if it did not
+ *   SALP_EVAL_FIRST_END (int32)                  0 the env did not finish, 1 that first finishing step was terminated, 2 truncated
+ *                                                (terminated wins, as in salp_stats_t)
+ *   SALP_EVAL_EPISODES (int32)                   steps in which the env finished (with no_autoreset: every flagged step)
+ *   SALP_EVAL_FOOD (int32)                       steps with a capture
+ * Integer words are stored as integers and the float64 fields are 8-byte aligned: every field is a typed view of the block.
+ * flags: SALP_DEVICE_PTRS and / or SALP_EVAL_ACCUMULATE.  With SALP_EVAL_ACCUMULATE the records are read first and continued:
+ * sums and counts go on, the FIRST_* fields stay frozen once FIRST_END != 0, an all-zero record is a fresh one — a run cut
+ * into several calls, or replayed from a captured graph, yields the bits of one call.  Without it the records are overwritten.
+ * Which observation each action sees (the prologue's bit-exact row included), the policy assignment for P > 1, the state
+ * write-back, autoreset, global step and statistics are those of salp_vec_rollout_policy.  Host pointers: synchronous; device
+ * pointers: the call only launches kernels on `stream` (capturable).
+ * SALP_ERR_INVALID, with nothing launched and the handle unchanged, for a NULL rec, horizon < 1, a flag bit other than those
+ * two, a device rec that is not 16-byte aligned, a policy of another handle or other dimensions, or a P that n_envs does not
+ * allow. */
+enum { SALP_EVAL_ACCUMULATE = 4u };
+enum { SALP_EVAL_RETURN = 0,        /* words 0-1: float64 */
+       SALP_EVAL_FIRST_RETURN = 2,  /* words 2-3: float64 */
+       SALP_EVAL_FIRST_LENGTH = 4, SALP_EVAL_FIRST_END, SALP_EVAL_EPISODES, SALP_EVAL_FOOD, SALP_EVAL_WORDS /* 8 */ };
+int salp_vec_evaluate_policy(salp_vec_t* h, const salp_policy_t* pol, int32_t horizon, void* rec, uint32_t flags, void* stream);
+
 /* Current observation of every env without stepping. obs float [n_envs][obs_dim]. */
 int salp_vec_observe(salp_vec_t* h, float* obs, uint32_t flags, void* stream);
 
@@ -322,14 +352,15 @@ int64_t salp_vec_global_step(const salp_vec_t* h);
  * generic instantiation), [2] 1 = the reference's constants compiled in as literals, [3] forced breathing, [4] the
  * output signature the kernel was compiled for: 1 = obs, reward, terminated, truncated and nothing else, 2 = those four plus
  * final_obs and / or info, 0 = some of the four is NULL (every store tested; always 0 for the generic instantiation's unpacked calls),
- * 3 = the packed record (both halves of a split launch and the generic instantiation too), [5] 1 = actions drawn in the kernel,
- * 2 = actions computed by a policy in the kernel (salp_vec_rollout_policy),
+ * 3 = the packed record (both halves of a split launch and the generic instantiation too), 4 = the per-env summary record and
+ * no per-step output (salp_vec_evaluate_policy: both halves; always with [5] == 2), [5] 1 = actions drawn in the kernel,
+ * 2 = actions computed by a policy in the kernel (salp_vec_rollout_policy, salp_vec_evaluate_policy),
  * [6] envs served by the unpredicated launch (whole wavefronts), [7] envs served by the predicated launch.
  * [4] is the signature of the kernel that ran: the unpredicated launch's when there was one, else the predicated launch's
- * (predicated kernels exist for signatures 1, 3 and 0 only: a call with final_obs / info runs them as 0). */
+ * (predicated kernels exist for signatures 1, 3, 4 and 0 only: a call with final_obs / info runs them as 0). */
 int salp_vec_last_launch(const salp_vec_t* h, int64_t info[8]);
 /* The output signature of each half of that call: sig[0] the unpredicated launch, sig[1] the predicated launch, -1 for a
- * half that was not launched (or before any call). */
+ * half that was not launched (or before any call); 4 in each launched half of a salp_vec_evaluate_policy call. */
 int salp_vec_last_launch_signatures(const salp_vec_t* h, int64_t sig[2]);
 /* What that kernel (the unpredicated one when both were launched) holds per workgroup of 256 threads, from the runtime
  * (hipFuncGetAttributes, hipOccupancyMaxActiveBlocksPerMultiprocessor): info[0] registers per thread (VGPRs), [1] static LDS

@@ -10,6 +10,10 @@ consecutive calls as one sample (a 10-us step launch is below what one event pai
 "+policy": salp_vec_rollout_policy with the 24 -> 32 -> 32 -> A actor (sac.Actor, seed 0) evaluated in the kernel; it writes
 the actions it takes into the shared action block, so with --launches 1 and the "+policy" variant listed FIRST a plain
 variant behind it replays exactly those actions from the same state (the price of the policy block alone).
+"+evaluate": salp_vec_evaluate_policy with the same policy as "+policy" (one 32-byte summary record per env, no per-step
+output); pair it against "+policy" of the PARENT commit's library: `par+policy=parent.so new+evaluate=libsalp_hip.so`.
+--policy linear | mlp32 | mlp64 picks the policy of both: the 25-parameter linear clip rule (the pursuit rule), or the
+24 -> 32 -> 32 -> A / 24 -> 64 -> 64 -> A actor.
 "+actorgraph": the same actor in torch around salp_vec_step, `SalpVectorEnv.capture_policy_steps(n_steps = chunk)` replayed
 — the best closed-loop path without the in-kernel policy (runs the installed library whatever path is given)."""
 import ctypes, json, os, statistics, sys
@@ -24,6 +28,7 @@ def main():
     want_fin = False
     calls = 1
     overrides = {}
+    policy_kind = "mlp32"
     it = iter(sys.argv[1:])
     for a in it:
         if a == "--rounds": rounds = int(next(it))
@@ -34,6 +39,7 @@ def main():
         elif a == "--set":                           # --set width=801 (a SalpSnakeEnv keyword on top of the preset)
             k, v = next(it).split("=", 1); overrides[k] = (int(v) if v.lstrip("-").isdigit() else (v == "true") if v in ("true", "false") else float(v))
         elif a == "--calls": calls = int(next(it))
+        elif a == "--policy": policy_kind = next(it)
         elif a == "--final-obs": want_fin = True      # the non-FULL output signature (terminal observations written)
         else:
             k, v = a.split("=", 1); variants.append((k, os.path.abspath(v)))
@@ -56,16 +62,18 @@ def main():
         _capi.check(lib, lib.salp_vec_create(ctypes.byref(c), n, 0, 0, 0, ctypes.byref(h)), "create")
         handles[name] = (lib, h, c)
     policies, graphs, envs = {}, {}, []
-    if any("+policy" in name or "+actorgraph" in name for name, _ in variants):
-        from underwater_swimmer_rl_amd.policy import MLPPolicy
+    eval_rec = torch.zeros((n, _capi.EVAL_WORDS), dtype=torch.int32, device=dev)
+    if any("+policy" in name or "+actorgraph" in name or "+evaluate" in name for name, _ in variants):
+        from underwater_swimmer_rl_amd.policy import MLPPolicy, pursuit_policy
         from underwater_swimmer_rl_amd.sac import Actor
         torch.manual_seed(0)
         low, high = (None, None) if cfg.forced_breathing else ([0.0, -1.0], [1.0, 1.0])
-        actor = Actor(cfg.obs_dim, cfg.act_dim, hidden=(32, 32), act_low=low, act_high=high).to(dev)
-        mlp = MLPPolicy.from_actor(actor)
+        width = {"mlp32": 32, "mlp64": 64, "linear": 32}[policy_kind]
+        actor = Actor(cfg.obs_dim, cfg.act_dim, hidden=(width, width), act_low=low, act_high=high).to(dev)
+        mlp = pursuit_policy(3.0, cfg.obs_dim) if policy_kind == "linear" else MLPPolicy.from_actor(actor)
         w = mlp.pack()
         for name, _ in variants:
-            if "+policy" in name:
+            if "+policy" in name or "+evaluate" in name:
                 lib, h, _ = handles[name]
                 d, ph = mlp.desc(), ctypes.c_void_p()
                 _capi.check(lib, lib.salp_policy_create(h, ctypes.byref(d), w.ctypes.data_as(ctypes.c_void_p), 0, None, ctypes.byref(ph)), "policy_create")
@@ -83,6 +91,9 @@ def main():
         st = vp(torch.cuda.current_stream().cuda_stream)
         if "+actorgraph" in name:
             graphs[name].replay()
+            return
+        if "+evaluate" in name:
+            _capi.check(lib, lib.salp_vec_evaluate_policy(h, policies[name], H, vp(eval_rec.data_ptr()), _capi.SALP_DEVICE_PTRS, st), "evaluate_policy")
             return
         if "+policy" in name:
             _capi.check(lib, lib.salp_vec_rollout_policy(h, policies[name], H, vp(obs.data_ptr()), vp(rew.data_ptr()), vp(term.data_ptr()),

@@ -1,0 +1,49 @@
+#!/usr/bin/env python3
+"""Registers / LDS / scratch of every salp_rollout_kernel instantiation of a built libsalp_hip.so, from the code object's
+own metadata (no GPU needed): the gfx950 code object is taken out of the library's fat binary (llvm-objcopy,
+clang-offload-bundler) and its AMDGPU metadata note read with llvm-readelf.  One line per kernel, sorted, so that two
+libraries are compared with `diff`.  usage:
+    python profiles/kernel_metadata.py LIB.so [--sig N] [--act N]       (filters on the SIG / ACT template arguments)
+waves_per_simd = min(8, 512 / registers allocated in granules of 8, 160 KiB / LDS per workgroup of four wavefronts)."""
+import os, re, subprocess, sys, tempfile
+
+LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
+
+
+def kernels(lib):
+    with tempfile.TemporaryDirectory() as d:
+        fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "gfx950.co")
+        subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", lib, os.path.join(d, "copy.so")], check=True)
+        subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                        f"--input={fat}", f"--output={co}"], check=True)
+        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
+    md = notes[notes.index("amdhsa.kernels:"):]
+    out = []
+    for blk in md.split("  - .agpr_count:")[1:]:
+        blk = ".agpr_count:" + blk
+        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
+        t = re.search(r"salp_rollout_kernelILi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELi(\d+)ELb(\d)ELi(\d+)E", name)
+        if not t:
+            continue
+        g = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1))
+        regs, lds = g("vgpr_count"), g("group_segment_fixed_size")
+        alloc = max(8, (regs + 7) // 8 * 8)
+        waves = min(8, 512 // alloc, (160 * 1024) // lds if lds else 8)
+        out.append((tuple(int(x) for x in t.groups()),
+                    f"vgpr={regs} agpr={g('agpr_count')} sgpr={g('sgpr_count')} lds={lds} scratch={g('private_segment_fixed_size')} waves_per_simd={waves}"))
+    return sorted(out)
+
+
+def main():
+    lib, sig, act = sys.argv[1], None, None
+    it = iter(sys.argv[2:])
+    for a in it:
+        if a == "--sig": sig = int(next(it))
+        elif a == "--act": act = int(next(it))
+    for t, line in kernels(lib):
+        if (sig is None or t[4] == sig) and (act is None or t[6] == act):
+            print("<" + ", ".join(str(x) for x in t) + "> " + line)
+
+
+if __name__ == "__main__":
+    main()

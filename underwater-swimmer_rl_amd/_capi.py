@@ -20,6 +20,9 @@ INFO_COLS = 3
 # packed transition record (include/salp_vec.h "Packed transition record"; layout helpers: records.py)
 REC_FINAL_OBS = 2           # call flag next to SALP_DEVICE_PTRS
 REC_REWARD, REC_FLAGS, REC_FOOD_COLLECTED, REC_STEPS_SINCE_FOOD, REC_EXTRA_COLS = range(5)
+# per-env summary record of salp_vec_evaluate_policy (include/salp_vec.h "Policy evaluation"; views: policy.evaluation_views)
+EVAL_ACCUMULATE = 4         # call flag next to SALP_DEVICE_PTRS
+EVAL_RETURN, EVAL_FIRST_RETURN, EVAL_FIRST_LENGTH, EVAL_FIRST_END, EVAL_EPISODES, EVAL_FOOD, EVAL_WORDS = 0, 2, 4, 5, 6, 7, 8
 # snapshot rows (include/salp_vec.h)
 F_X, F_Y, F_VX, F_VY, F_THETA, F_OMEGA, F_NOZZLE, F_WATER, F_ELLIPSE_A, F_ELLIPSE_B, F_FOOD0 = range(11)
 (I_PHASE, I_TIMER, I_EXHALE_DUR, I_SHAPE_HOLD, I_STEPS_SINCE_FOOD, I_FOOD_COLLECTED, I_RNG_COUNTER,
@@ -34,6 +37,7 @@ EXPORTS = (
     "salp_vec_reseed", "salp_vec_last_launch", "salp_vec_last_kernel_resources", "salp_vec_last_launch_signatures",
     "salp_vec_record_width", "salp_vec_step_packed", "salp_vec_rollout_packed",
     "salp_policy_words", "salp_policy_create", "salp_policy_update", "salp_policy_destroy", "salp_vec_rollout_policy",
+    "salp_vec_evaluate_policy",
 )
 
 
@@ -113,6 +117,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         L.salp_policy_destroy.argtypes = [vp]
         L.salp_policy_destroy.restype = None
         L.salp_vec_rollout_policy.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, u32, vp]
+    if path is None or hasattr(L, "salp_vec_evaluate_policy"):
+        L.salp_vec_evaluate_policy.argtypes = [vp, vp, i32, vp, u32, vp]
     L.salp_vec_global_step.argtypes = [vp]
     L.salp_vec_global_step.restype = i64
     L.salp_vec_set_base_num_food.argtypes = [vp, i32]
@@ -235,6 +241,12 @@ class SalpLib:
                                                          self._ptr(term), self._ptr(trunc), self._ptr(act_out), flags,
                                                          ctypes.c_void_p(stream)), "salp_vec_rollout_policy")
 
+    def evaluate_policy(self, handle: "PolicyHandle", horizon, rec, flags, stream=0):
+        """salp_vec_evaluate_policy: rec int32 [n, EVAL_WORDS], one summary record per env and nothing per step; flags:
+        SALP_DEVICE_PTRS and / or EVAL_ACCUMULATE (continue the records in `rec`)."""
+        check(self.lib, self.lib.salp_vec_evaluate_policy(self._h, handle._p, int(horizon), self._ptr(rec), flags,
+                                                          ctypes.c_void_p(stream)), "salp_vec_evaluate_policy")
+
     def reseed(self, seed, obs, flags, stream=0):
         """New draw streams keyed by `seed`, every env reset from draw counter 0; no reallocation (capture-safe)."""
         check(self.lib, self.lib.salp_vec_reseed(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, self._ptr(obs), flags,
@@ -260,7 +272,7 @@ class SalpLib:
     def last_launch(self) -> dict:
         """The kernel instantiation of the most recent step / rollout call (salp_vec_last_launch).  `full_signature`: 1 = the four
         main outputs only, 2 = the four plus final_obs / info, 3 = the packed record (step_packed / rollout_packed, every
-        instantiation), 0 = every store tested (some main output absent, the generic instantiation, or a predicated launch
+        instantiation), 4 = the per-env summary record and no per-step output (evaluate_policy), 0 = every store tested (some main output absent, the generic instantiation, or a predicated launch
         asked for final_obs / info) — of the kernel that ran: the unpredicated launch's
         when there was one, else the predicated launch's.  `signature_unpredicated` / `signature_predicated`: each half's own,
         -1 for a half that was not launched (salp_vec_last_launch_signatures)."""

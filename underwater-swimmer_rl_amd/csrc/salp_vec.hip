@@ -46,6 +46,10 @@ constexpr int kWave = 64;
 //   per lane to scratch inside the step loop; at 1 the wavefront owns the SIMD's 512 registers and what does not fit in the
 //   256 VGPRs is parked in AGPRs (v_accvgpr_write / _read), not in memory (profiles/r05/policy_kernel_resources.txt).
 constexpr int waves_per_simd(int fmax, int kmax, bool std_consts, bool ragged, int sig, bool policy = false) {
+  // The summary kernels (sig 4) take their twins' bounds, but for the unpredicated 4-slot kernel with run-time constants: 1 (at 2
+  // it sat at 255-256 VGPRs with 12-132 B of scratch, its twin holds 0-12 B; at 1 258-272 registers, 2-16 of them AGPRs, none).
+  // From the code-object metadata of all 40: profiles/r06/eval_kernel_resources.txt.
+  if (policy && sig == 4 && fmax == 4 && !std_consts && !ragged) return 1;
   if (policy) return (ragged || fmax >= 8) ? 1 : 2;
   if (sig == 3 && ragged && kmax == 3 && fmax == 8) return 3;
   return fmax <= 1 ? 4 : (kmax != 3 ? (fmax <= 12 ? 2 : 1) : (fmax <= 8 ? 4 : (fmax <= 12 ? 3 : ((std_consts && !ragged) ? 3 : 2))));
@@ -113,13 +117,23 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
   // function, for the 4- and 8-slot kernels; the by-value launch parameters for the others
   constexpr bool GEN = ACT == ACT_GEN;
   constexpr bool POLICY = ACT == ACT_POLICY;
-  static_assert(!POLICY || (SIG == 1 && KMAX == 3), "policy kernels: the main-only signature, K = 3");
-  constexpr bool MEMC = !STD && KMAX == 3 && (FMAX == 4 || FMAX == 8);
+  // SIG 4 (kSigSummary): NO per-step output at all — salp_vec_evaluate_policy.  io.obs is the block of per-env summary records
+  // ([n][SALP_EVAL_WORDS] words, include/salp_vec.h), io.final_obs non-NULL says that the records are read first and continued
+  // (SALP_EVAL_ACCUMULATE).  The observation is formed in registers for the policy alone: no tile write, no flush, no
+  // reward / flag / action store; the record leaves next to the state write-back.  The LDS layout is that of the twin policy
+  // kernel (the rare paths still borrow the tile's bytes, the mirror sits behind it): LDS limits none of these kernels.
+  constexpr bool SUMMARY = SIG == 4;
+  static_assert(!POLICY || ((SIG == 1 || SIG == 4) && KMAX == 3), "policy kernels: the main-only and the summary signature, K = 3");
+  static_assert(!SUMMARY || POLICY, "the summary signature exists for the in-kernel policy only");
+  // (the summary kernels the other way round — by value with 4 / 8 slots, the device copy with 16: with no store in the step loop
+  // the twins' choice left 300-560 scalar registers spilled and 68-196 B of scratch reserved in four of them; so chosen, none
+  // of the 40 holds scratch where its twin holds none, profiles/r06/eval_kernel_resources.txt)
+  constexpr bool MEMC = !STD && KMAX == 3 && (SIG == 4 ? FMAX == 16 : (FMAX == 4 || FMAX == 8));
   DevParams P_pol = P_arg;
   P_pol.use_mem = MEMC ? 1 : 0;
   const DevParams& P = STD ? P_arg : P_pol;
   constexpr bool FULL = SIG != 0;         // obs, reward, terminated, truncated all present: their stores are unconditional
-  constexpr bool EXTRAS = SIG != 1;       // final_obs / info may be present (tested per use; SIG 0: every output is tested)
+  constexpr bool EXTRAS = SIG != 1 && !SUMMARY;   // final_obs / info may be present (tested per use; SIG 0: every output is tested)
   // SIG 3 (kSigPacked): ONE output stream of transition records (include/salp_vec.h "Packed transition record") — the
   // observation row plus one float4 (reward, flags word, food_collected, steps_since_food) — through the tile; io.obs is
   // the record block, io.final_obs non-NULL says that the rows carry a terminal-observation tail
@@ -162,7 +176,12 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
   constexpr bool HALF = !RAGGED && REGF && KMAX == 3 && FMAX == 16 && STD;
   constexpr int TILE_ROWS = HALF ? kWave / 2 : kWave;
   constexpr int TILE_FLOATS = TILE_ROWS * PITCH;
-  constexpr int WAVE_FLOATS = TILE_FLOATS + (REGF ? kWave * 2 * FMAX : 0);
+  // SUMMARY, register-food kernels: the env's record (32 B per lane) is kept in LDS behind the mirror and updated there every
+  // step — these kernels sit at their register limits (eight more registers across the loop put 12-132 B of scratch into the
+  // 4-slot ones, profiles/r06/ab_notes.md) and LDS limits none of them; the one-food kernels keep it in registers.
+  constexpr bool EVLDS = SUMMARY && FMAX > 1;
+  constexpr int EV_FLOATS = EVLDS ? kWave * SALP_EVAL_WORDS : 0;
+  constexpr int WAVE_FLOATS = TILE_FLOATS + (REGF ? kWave * 2 * FMAX : 0) + EV_FLOATS;
   static_assert(!REGF || (4 * FMAX <= TILE_ROWS * PITCH && 96 <= TILE_ROWS * PITCH), "the placement's FMAX accepted points (16 B each) must fit in the tile");
   __shared__ __attribute__((aligned(16))) float lds[(kBlock / kWave) * WAVE_FLOATS];
 
@@ -207,7 +226,7 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
 #pragma unroll
   for (int j = 0; j < QMAX; ++j) {
     int i = wave * WAVE_FLOATS + (lds_off[j] >= 0 ? lds_off[j] : 0);
-    if constexpr (!PACKED || TAILREG) asm volatile("" : "+v"(i));
+    if constexpr ((!PACKED || TAILREG) && !SUMMARY) asm volatile("" : "+v"(i));
     flush_src[j] = reinterpret_cast<const v4f*>(lds + i);
   }
   // PACKED flush plan: float4 f = j*64 + lane of a tile pass (TILE_ROWS rows of TQ float4: Q + 1, TAILREG Q) lives at tile
@@ -248,7 +267,7 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
   EnvT e;
   const FoodLds food{food_lds + (LDSF ? (wave * FMAX * kWave + lane) : 0)};
   const MirrorLds mir{reinterpret_cast<float2*>(tile + TILE_FLOATS) + lane};   // REGF only
-  FoodF32<REGF ? FMAX : 1, food_in_registers(FMAX, KMAX, STD, SIG == 1) && !HALF> ff;   // REGF: fp32 roundings of the food positions (salp_food_reg.h)
+  FoodF32<REGF ? FMAX : 1, food_in_registers(FMAX, KMAX, STD, SIG == 1 || SIG == 4) && !HALF> ff;   // REGF: fp32 roundings of the food positions (salp_food_reg.h)
   FoodScan<KMAX> fq;          // MULTI: nearest-K selection of the current food set around the current pose
   int nlive = 0;              // MULTI: live foods of this env, recounted whenever the food set changes
   int order_cache = -1;       // REGF: remembered exact order of a resting swimmer's foods (step_env_reg)
@@ -273,6 +292,26 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
   }
 
   double st_reward = 0.0;   // the one per-step statistic
+  // SUMMARY: the env's record (include/salp_vec.h SALP_EVAL_*): two doubles and four ints per lane, in registers (one food)
+  // or in the lane's own two float4 of LDS (EVLDS: float4 `lane` holds the sums, float4 `64 + lane` the counts — consecutive
+  // lanes 16 B apart, conflict-free; only the lane itself ever touches them, so no barrier is involved)
+  double ev_ret = 0.0, ev_first_ret = 0.0;
+  int ev_first_len = 0, ev_first_end = 0, ev_episodes = 0, ev_food = 0;
+  int4* const ev_lds = reinterpret_cast<int4*>(tile + WAVE_FLOATS - EV_FLOATS) + lane;
+  if constexpr (SUMMARY) {
+    int4 ra = make_int4(0, 0, 0, 0), rb = make_int4(0, 0, 0, 0);
+    if (io.final_obs && rows > 0) {     // SALP_EVAL_ACCUMULATE: continue the caller's record (complete at the vmcnt(0) below)
+      const int4* const rp = reinterpret_cast<const int4*>(io.obs) + envc * 2;
+      ra = rp[0]; rb = rp[1];
+    }
+    if constexpr (EVLDS) {
+      ev_lds[0] = ra; ev_lds[kWave] = rb;
+    } else {
+      ev_ret = __hiloint2double(ra.y, ra.x);
+      ev_first_ret = __hiloint2double(ra.w, ra.z);
+      ev_first_len = rb.x; ev_first_end = rb.y; ev_episodes = rb.z; ev_food = rb.w;
+    }
+  }
 
   float a0 = 0.f, a1 = 0.f;
   U4 aw0 = {0u, 0u, 0u, 0u}, aw1 = {0u, 0u, 0u, 0u};   // GEN: the current Philox block of each action component
@@ -363,7 +402,7 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
         if (!FORCED) io.act_out[(rowbase + env) * AD + 1] = c1;
       }
     } else if (POLICY) {
-      if (io.act_out && active) {
+      if (!SUMMARY && io.act_out && active) {
         io.act_out[(rowbase + env) * AD] = c0;
         if (!FORCED) io.act_out[(rowbase + env) * AD + 1] = c1;
       }
@@ -407,7 +446,7 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
       if constexpr (TAILREG) reinterpret_cast<float4*>(io.obs)[(rowbase + env) * RW4 + Q] = last;
       else *rec_stash = last;
     }
-    if (!PACKED && active) {
+    if (!PACKED && !SUMMARY && active) {
       // reward: one dword per lane (256 B per wavefront); flags: one byte per lane.  (Rebuilding the
       // 64 flag bytes from a ballot and storing 16 dwords was measured: no faster in the memory
       // pipeline and slower overall, profiles/r01/ab_notes.md.)
@@ -423,6 +462,32 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
       }
     }
     st_reward += (double)o.reward;
+    if constexpr (SUMMARY) {    // the float32 reward a rollout would have stored, added in step order in fp64; nothing below changes these
+      const double r64 = (double)o.reward;
+      const int end_now = o.terminated ? 1 : (o.truncated ? 2 : 0);     // terminated wins, as in the statistics below
+      if constexpr (EVLDS) {
+        int4 sa = ev_lds[0], sb = ev_lds[kWave];
+        const double ret = __hiloint2double(sa.y, sa.x) + r64;
+        double first = __hiloint2double(sa.w, sa.z);
+        const bool open = sb.y == 0;
+        if (open) first += r64;
+        sb.x += open ? 1 : 0;
+        sb.y = open ? end_now : sb.y;
+        sb.z += done ? 1 : 0;
+        sb.w += o.collected ? 1 : 0;
+        ev_lds[0] = make_int4(__double2loint(ret), __double2hiint(ret), __double2loint(first), __double2hiint(first));
+        ev_lds[kWave] = sb;
+      } else {
+        ev_ret += r64;
+        if (ev_first_end == 0) {
+          ev_first_ret += r64;
+          ev_first_len += 1;
+          ev_first_end = end_now;
+        }
+        ev_episodes += done ? 1 : 0;
+        ev_food += o.collected ? 1 : 0;
+      }
+    }
 
     SALP_STAMP(6);
     // rare events: respawn of a collected food (snake:179-180), then same-step autoreset
@@ -509,7 +574,7 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
           __builtin_amdgcn_wave_barrier();
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
-        else if constexpr (REGF) place_food_coop_reg<FMAX, STD, food_in_registers(FMAX, KMAX, STD, SIG == 1) && !HALF>(e, ff, mir, lane, C, genv, todo, limit, reinterpret_cast<double2*>(tile));
+        else if constexpr (REGF) place_food_coop_reg<FMAX, STD, food_in_registers(FMAX, KMAX, STD, SIG == 1 || SIG == 4) && !HALF>(e, ff, mir, lane, C, genv, todo, limit, reinterpret_cast<double2*>(tile));
         else place_food<FMAX, STD>(e, C, genv, todo, limit);
         todo = 0;
       }
@@ -528,7 +593,7 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
     }
     SALP_STAMP(7);
 
-    if (FULL || io.obs) {
+    if (SUMMARY ? (t + 1 < Hrun) : (FULL || io.obs)) {     // SUMMARY: the row exists for the next action only
       float ob[12 + 4 * KMAX];
       if constexpr (REGF) {
         // all FMAX slots of every lane alive (the steady state with respawn) => every lane shows K foods
@@ -538,8 +603,11 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
       else observe<FMAX, KMAX, STD>(e, P, rmax, have_rel, o.rel, ob);
       SALP_STAMP(8);
       // (per-lane 96-B rows stored straight from registers, without the LDS transpose: 2.1x slower, r01 ab_notes)
-      v4f* gout = reinterpret_cast<v4f*>(io.obs + (rowbase + env0) * OD) + lane;
-      if constexpr (PACKED) {
+      [[maybe_unused]] v4f* gout = nullptr;
+      if constexpr (!SUMMARY) gout = reinterpret_cast<v4f*>(io.obs + (rowbase + env0) * OD) + lane;
+      if constexpr (SUMMARY) {
+        // nothing is stored
+      } else if constexpr (PACKED) {
         // the record rows through the tile, in one pass or (HALF) two of 32 rows; each pass is PJ 16-B-per-lane stores
         v4f* const rec0 = reinterpret_cast<v4f*>(io.obs) + (rowbase + env0) * RW4;
         const v4f* const tile4 = reinterpret_cast<const v4f*>(tile);
@@ -646,7 +714,7 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
       }
       // the next step's action from this step's row, while the row stores are in flight (the last step needs none)
       if constexpr (POLICY) {
-        if (t + 1 < Hrun) policy_eval<12 + 4 * KMAX, FORCED ? 1 : 2>(io.act, pol_off, ob, a0, a1);
+        if (SUMMARY || t + 1 < Hrun) policy_eval<12 + 4 * KMAX, FORCED ? 1 : 2>(io.act, pol_off, ob, a0, a1);
       }
     }
     // One-food kernel (write-bound): drain this step's stores before the next step.  Measured
@@ -654,7 +722,7 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
     // wavefronts that stay in step keep the write stream of all CUs inside one contiguous [N x 96 B] slab
     // at a time.  The multi-food kernels are issue-bound at 2 wavefronts per SIMD: there the drain is a
     // stall nothing hides (-6.4 % without it, profiles/r02/ab_notes.md session 2).
-    if constexpr (!MULTI) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+    if constexpr (!MULTI && !SUMMARY) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)   (SUMMARY: the loop has no store to drain)
     SALP_STAMP(9);
   }
 #ifdef SALP_EXP_STAMPS
@@ -679,6 +747,16 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
       }
     } else {
       store_env(e, CS, C, env);
+    }
+    if constexpr (SUMMARY) {     // the env's record: two 16-byte stores
+      int4* const rp = reinterpret_cast<int4*>(io.obs) + env * 2;
+      if constexpr (EVLDS) {
+        rp[0] = ev_lds[0];
+        rp[1] = ev_lds[kWave];
+      } else {
+        rp[0] = make_int4(__double2loint(ev_ret), __double2hiint(ev_ret), __double2loint(ev_first_ret), __double2hiint(ev_first_ret));
+        rp[1] = make_int4(ev_first_len, ev_first_end, ev_episodes, ev_food);
+      }
     }
   }
 
@@ -969,10 +1047,15 @@ typedef void (*reset_fn)(DevParams, DevState, const uint8_t*, float*, int);
 // profiles/r03/ab_notes.md session 15).  The one-wavefront predicated launches exist as kSigMain and kSigPartial only.
 // kSigPacked = ONE stream of transition records (salp_vec_step_packed / salp_vec_rollout_packed): no per-lane reward / flag /
 // info stores at all; unpredicated and predicated, K = 3 and generic K; no in-kernel action generation.
-enum { kSigPartial = 0, kSigMain = 1, kSigExtras = 2, kSigPacked = 3 };
+// kSigSummary = NO per-step output: one record of SALP_EVAL_WORDS words per env at the end of the launch
+// (salp_vec_evaluate_policy); exists for the in-kernel policy and K = 3 only, unpredicated and predicated.
+enum { kSigPartial = 0, kSigMain = 1, kSigExtras = 2, kSigPacked = 3, kSigSummary = 4 };
 template <int FMAX, int KMAX, bool FORCED, bool STD, bool RAGGED, int ACT>
 rollout_fn pick_sig(int sig) {
-  if constexpr (ACT != ACT_READ) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, ACT>;
+  if constexpr (ACT == ACT_POLICY) {
+    if (sig == kSigSummary) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigSummary, RAGGED, ACT_POLICY>;
+    return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, ACT_POLICY>;
+  } else if constexpr (ACT != ACT_READ) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, ACT>;
   else {
     if (sig == kSigMain) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, ACT_READ>;
     if (sig == kSigPacked) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigPacked, RAGGED, ACT_READ>;
@@ -984,7 +1067,7 @@ rollout_fn pick_sig(int sig) {
 // `act`: where the actions come from (ACT_READ / ACT_GEN / ACT_POLICY)
 template <int FMAX, int KMAX, bool STD, bool RAGGED>
 rollout_fn pick_rollout(bool forced, int sig, int act) {
-  if (sig == kSigMain && act == ACT_POLICY)   // the in-kernel policy, like the in-kernel generation, exists for the main-only output signature
+  if ((sig == kSigMain || sig == kSigSummary) && act == ACT_POLICY)   // the in-kernel policy exists for the main-only output signature and for the summary
     return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, ACT_POLICY>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, ACT_POLICY>(sig);
   if (sig == kSigMain && act == ACT_GEN)
     return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, ACT_GEN>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, ACT_GEN>(sig);
@@ -1074,9 +1157,10 @@ struct Bump {  // carve sub-buffers out of the staging allocation
 
 // packed: io.obs is a record block (kSigPacked), io.final_obs non-NULL asks for the terminal-observation tail
 // policy: io.act is a policy's device block (ACT_POLICY; the caller has checked K = 3 and the four main outputs)
-int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, bool packed = false, bool policy = false) {
+// summary: io.obs is the block of summary records (kSigSummary; policy only), io.final_obs non-NULL = SALP_EVAL_ACCUMULATE
+int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, bool packed = false, bool policy = false, bool summary = false) {
   const bool main_outputs = io.obs && io.reward && io.terminated && io.truncated;
-  const int sig = packed ? kSigPacked : (!main_outputs ? kSigPartial : ((io.final_obs || io.info) ? kSigExtras : kSigMain));
+  const int sig = summary ? kSigSummary : packed ? kSigPacked : (!main_outputs ? kSigPartial : ((io.final_obs || io.info) ? kSigExtras : kSigMain));
   const int gen = policy ? ACT_POLICY : (io.act == nullptr ? ACT_GEN : ACT_READ);   // ACT_GEN: only reached when can_generate_in_kernel()
   // envs in full wavefronts: unpredicated kernel
   int64_t n_full = h->n / kWave * kWave;
@@ -1084,9 +1168,9 @@ int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, bool pa
   // range instead of two; the predicates only cost when the write stream is the bound.
   if (n_full < h->n && h->n * (int64_t)H <= (int64_t)1 << 22) n_full = 0;
   // the signature each launch was compiled for (pick_sig): the predicated kernels exist as kSigMain and kSigPartial only
-  // (kSigPacked exists in every form)
+  // (kSigPacked exists in every form, kSigSummary in both forms of the K = 3 policy kernels)
   const int sig_full = (h->kmax == 3 || packed) ? sig : kSigPartial;
-  const int sig_ragged = packed ? kSigPacked : ((h->kmax == 3 && sig == kSigMain) ? kSigMain : kSigPartial);
+  const int sig_ragged = (packed || summary) ? sig : ((h->kmax == 3 && sig == kSigMain) ? kSigMain : kSigPartial);
   h->last_sigs[0] = (n_full > 0) ? sig_full : -1;
   h->last_sigs[1] = (n_full < h->n) ? sig_ragged : -1;
   h->last_launch[0] = h->fmax; h->last_launch[1] = h->kmax; h->last_launch[2] = (h->kmax == 3) ? h->std_consts : 0;
@@ -1679,6 +1763,52 @@ int salp_vec_rollout_policy(salp_vec_t* h, const salp_policy_t* pol, int32_t H, 
   HIP_TRY(hipMemcpyAsync(terminated, d_term, HN, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(truncated, d_trunc, HN, hipMemcpyDeviceToHost, st));
   if (d_aout) HIP_TRY(hipMemcpyAsync(act_out, d_aout, HN * h->act_dim * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return SALP_OK;
+}
+
+// salp_vec_evaluate_policy: the kSigSummary kernels.  Everything is checked before anything is launched.
+int salp_vec_evaluate_policy(salp_vec_t* h, const salp_policy_t* pol, int32_t H, void* rec, uint32_t flags, void* stream) {
+  if (!h || !pol) return fail(SALP_ERR_INVALID, "handle/policy is NULL");
+  if (pol->h != h || pol->device != h->device || pol->obs_dim != h->obs_dim || pol->act_dim != h->act_dim || pol->n != h->n)
+    return fail(SALP_ERR_INVALID, "the policy belongs to another handle (or other dimensions)");
+  if (h->kmax != 3) return fail(SALP_ERR_INVALID, "policies need a handle with max_observed_food == 3");
+  if (!rec) return fail(SALP_ERR_INVALID, "rec is NULL");
+  if (H <= 0) return fail(SALP_ERR_INVALID, "horizon must be >= 1");
+  if (flags & ~(uint32_t)(SALP_DEVICE_PTRS | SALP_EVAL_ACCUMULATE))
+    return fail(SALP_ERR_INVALID, "unknown flag bits (SALP_DEVICE_PTRS and SALP_EVAL_ACCUMULATE are defined)");
+  if ((flags & SALP_DEVICE_PTRS) && ((uintptr_t)rec & 15u))
+    return fail(SALP_ERR_INVALID, "rec must be 16-byte aligned (a record is written as two 16-byte stores)");
+  if (pol->d.n_policies > 1 && (h->n % pol->d.n_policies != 0 || (h->n / pol->d.n_policies) % kWave != 0))
+    return fail(SALP_ERR_INVALID, "n_policies > 1 needs n_envs % P == 0 and (n_envs / P) % 64 == 0");
+  DeviceScope dev_scope;
+  HIP_TRY(dev_scope.enter(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  h->last_stream = st;
+  const bool accumulate = (flags & SALP_EVAL_ACCUMULATE) != 0;
+  IOPtrs io;
+  memset(&io, 0, sizeof(io));
+  io.stats = h->stats_enabled ? h->stats : nullptr;
+  io.global_step = h->global_step;
+  io.act = pol->block;
+  if (flags & SALP_DEVICE_PTRS) {
+    io.obs = (float*)rec; io.final_obs = accumulate ? (float*)rec : nullptr;
+    const int rc = launch_rollout(h, io, H, st, false, true, true);
+    if (rc == SALP_OK) h->global_step += H;
+    return rc;
+  }
+  // host pointers: stage through device memory, synchronous
+  const size_t rec_b = (size_t)h->n * SALP_EVAL_WORDS * sizeof(int32_t);
+  int rc = ensure_stage(h, align_up(rec_b, 256) + 512);
+  if (rc != SALP_OK) return rc;
+  Bump b{(char*)h->stage, 0};
+  int32_t* d_rec = b.take<int32_t>((size_t)h->n * SALP_EVAL_WORDS);
+  if (accumulate) HIP_TRY(hipMemcpyAsync(d_rec, rec, rec_b, hipMemcpyHostToDevice, st));
+  io.obs = (float*)d_rec; io.final_obs = accumulate ? (float*)d_rec : nullptr;
+  rc = launch_rollout(h, io, H, st, false, true, true);
+  if (rc != SALP_OK) return rc;
+  h->global_step += H;
+  HIP_TRY(hipMemcpyAsync(rec, d_rec, rec_b, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return SALP_OK;
 }

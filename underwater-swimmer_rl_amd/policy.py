@@ -194,6 +194,59 @@ class MLPPolicy:
         return back(self._forward(g, True)[1])
 
 
+# ---------------------------------------------------------------------- evaluation records (salp_vec_evaluate_policy)
+EVAL_RETURN, EVAL_FIRST_RETURN, EVAL_FIRST_LENGTH, EVAL_FIRST_END, EVAL_EPISODES, EVAL_FOOD, EVAL_WORDS = 0, 2, 4, 5, 6, 7, 8
+
+
+def evaluation_views(record) -> dict:
+    """Typed views (no copy) of a block of summary records, int32 [N, 8] (numpy array or torch tensor, contiguous):
+    `record` itself, `return_sum` and `first_return` float64 [N], `first_length`, `first_end`, `episodes`, `food` int32 [N]
+    (include/salp_vec.h SALP_EVAL_*)."""
+    if isinstance(record, np.ndarray):
+        if record.dtype != np.int32 or record.ndim != 2 or record.shape[1] != EVAL_WORDS or not record.flags.c_contiguous:
+            raise ValueError("record must be a contiguous int32 [N, 8] block")
+        f64 = record.view(np.float64)                       # [N, 4]
+    else:
+        import torch
+        if record.dtype != torch.int32 or record.dim() != 2 or record.shape[1] != EVAL_WORDS or not record.is_contiguous():
+            raise ValueError("record must be a contiguous int32 [N, 8] block")
+        f64 = record.view(torch.float64)
+    return dict(record=record, return_sum=f64[:, EVAL_RETURN // 2], first_return=f64[:, EVAL_FIRST_RETURN // 2],
+                first_length=record[:, EVAL_FIRST_LENGTH], first_end=record[:, EVAL_FIRST_END],
+                episodes=record[:, EVAL_EPISODES], food=record[:, EVAL_FOOD])
+
+
+def summarize_rollout(reward, terminated, truncated, captured=None, record=None) -> np.ndarray:
+    """The summary records of a rollout's per-step outputs — the numpy statement of what salp_vec_evaluate_policy leaves:
+    reward float32 [H, N], terminated / truncated [H, N] (0 / 1), captured [H, N] (a capture in that step; None: no food
+    count).  Returns int32 [N, 8].  The sums are sequential float64 additions of the float32 rewards in step order.
+    `record`: records to continue (SALP_EVAL_ACCUMULATE; not modified) — an all-zero record is a fresh one."""
+    reward = np.asarray(reward)
+    if reward.dtype != np.float32:
+        raise ValueError("reward must be float32: the sums are over the float32 values a rollout stores")
+    H, N = reward.shape
+    term = np.asarray(terminated).astype(bool).reshape(H, N)
+    trunc = np.asarray(truncated).astype(bool).reshape(H, N)
+    cap = np.zeros((H, N), bool) if captured is None else np.asarray(captured).astype(bool).reshape(H, N)
+    rec = np.zeros((N, EVAL_WORDS), np.int32) if record is None else np.array(record, dtype=np.int32, order="C").reshape(N, EVAL_WORDS)
+    v = evaluation_views(rec)
+    ret, first_ret = v["return_sum"].copy(), v["first_return"].copy()
+    first_len, first_end = v["first_length"].copy(), v["first_end"].copy()
+    episodes, food = v["episodes"].copy(), v["food"].copy()
+    for t in range(H):
+        r = reward[t].astype(np.float64)
+        ret = ret + r
+        open_ = first_end == 0
+        first_ret = np.where(open_, first_ret + r, first_ret)
+        first_len = first_len + open_.astype(np.int32)
+        first_end = np.where(open_, np.where(term[t], 1, np.where(trunc[t], 2, 0)), first_end).astype(np.int32)    # terminated wins
+        episodes = episodes + (term[t] | trunc[t]).astype(np.int32)
+        food = food + cap[t].astype(np.int32)
+    v["return_sum"][:], v["first_return"][:] = ret, first_ret
+    v["first_length"][:], v["first_end"][:], v["episodes"][:], v["food"][:] = first_len, first_end, episodes, food
+    return rec
+
+
 def pursuit_policy(gain: float = 3.0, obs_dim: int = 24) -> MLPPolicy:
     """`navigation_eval.pursuit_policy` as an in-kernel policy: clip(-gain * obs[13], -1, 1)."""
     W = np.zeros((1, obs_dim), np.float32)

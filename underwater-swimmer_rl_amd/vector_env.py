@@ -350,6 +350,40 @@ class SalpVectorEnv:
         self._lib.rollout_policy(policy, H, obs, rew, term, trunc, aout, self._flags, self._stream)
         return dict(obs=obs, reward=rew, terminated=term, truncated=trunc, final_obs=None, actions=aout)
 
+    def evaluate_policy(self, policy, horizon: int, out=None, accumulate: bool = False) -> dict:
+        """`horizon` closed-loop steps of `rollout_policy` in one kernel launch with NO per-step output: one summary record
+        per env (32 B) instead of [H, N] observations, rewards and flags.  Returns typed views of one int32 [N, 8] block
+        (`policy.evaluation_views`): `record`, `return_sum` and `first_return` (float64 [N]: the float32 step rewards added
+        in step order — over the call, and up to the env's first episode end), `first_length`, `first_end` (0 not finished,
+        1 terminated, 2 truncated), `episodes`, `food` (int32 [N]).  `out`: a block (or a dict returned earlier) to write
+        into; `accumulate=True` continues the records in `out` (required then), so that a run cut into several calls gives
+        the bits of one call.  A policy's score: `return_sum.view(P, E).mean(1)`."""
+        from .policy import EVAL_WORDS, evaluation_views
+        if not isinstance(policy, _capi.PolicyHandle):
+            cache = self.__dict__.setdefault("_policy_cache", {})
+            if id(policy) not in cache:
+                cache[id(policy)] = (policy, self.make_policy(policy))
+            policy = cache[id(policy)][1]
+        H, n = int(horizon), self.num_envs
+        if H < 1:
+            raise ValueError("horizon must be >= 1")
+        if accumulate and out is None:
+            raise ValueError("accumulate=True continues the records in `out`: pass the block of the call before")
+        rec = out["record"] if isinstance(out, dict) else out
+        if rec is None:
+            rec = (self._torch.empty((n, EVAL_WORDS), dtype=self._torch.int32, device=self.device) if self._torch is not None
+                   else np.empty((n, EVAL_WORDS), np.int32))
+        if self._torch is not None:        # the pointer goes to the kernel as a device pointer: it must be one, on this GPU
+            if not isinstance(rec, self._torch.Tensor) or rec.device != self.device:
+                raise ValueError(f"out must be a torch tensor on {self.device}")
+        elif not isinstance(rec, np.ndarray):
+            raise ValueError("out must be a numpy array (this env returns host arrays)")
+        if tuple(rec.shape) != (n, EVAL_WORDS):
+            raise ValueError(f"out must be an int32 [{n}, {EVAL_WORDS}] block")
+        views = evaluation_views(rec)       # checks dtype and contiguity
+        self._lib.evaluate_policy(policy, H, rec, self._flags | (_capi.EVAL_ACCUMULATE if accumulate else 0), self._stream)
+        return views
+
     def observe(self):
         obs = self._buf("obs", (self.num_envs, self.obs_dim), np.float32)
         self._lib.observe(obs, self._flags, self._stream)
