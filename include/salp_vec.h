@@ -280,10 +280,13 @@ int salp_policy_update(salp_policy_t* pol, const float* weights, uint32_t flags,
 void salp_policy_destroy(salp_policy_t* pol);
 
 /* rollout() with the actions computed in the kernel: the action of step 0 is the policy applied to the env's current
- * observation (what salp_vec_observe returns); the action of step t + 1 is the policy applied to the row written to obs[t]
- * (after a same-step autoreset the first observation of the new episode; with no_autoreset the row as returned).
+ * observation; the action of step t + 1 is the policy applied to the row written to obs[t] (after a same-step autoreset
+ * the first observation of the new episode; with no_autoreset the row as returned).
  * When the state was left by a step, the observation of step 0 is formed with the bits of that step's row, so a rollout
- * cut into several calls takes the same actions, bit for bit, as one call.
+ * cut into several calls takes the same actions, bit for bit, as one call.  For a state that no step left (reset,
+ * set_state) it is the row salp_vec_observe returns up to the last bits of ONE column: the relative bearing of the nearest
+ * food (column 13) goes through the step's arctangent polynomial or through salp_vec_observe's, which differ by a few units
+ * in the last place (as a step's own row and salp_vec_observe after it do).
  * obs, reward, terminated, truncated as in salp_vec_rollout, all four required; act_out (may be NULL) receives the actions
  * taken, float [horizon][n_envs][act_dim].  Global step, statistics, state write-back and autoreset are those of
  * salp_vec_rollout.  With device pointers the call only launches kernels on `stream` (capturable).

@@ -624,3 +624,66 @@ int salp_oracle_set_base_num_food(salp_oracle_t* h, int k) {
   h->base_num_food = k;
   return 0;
 }
+
+/* The in-kernel policy of include/salp_vec.h "Policy", restated from the header's words and the PUBLIC weight layout
+   alone: for each layer in order W[out][in] row-major, then b[out]; then scale[act_dim], shift[act_dim].  ONE policy
+   (`weights` holds salp_policy_words floats; desc->n_policies is not looked at: a population is a loop over its
+   policies in the caller).  fp32 throughout: every unit starts from its bias and adds its inputs in ascending index
+   order with one fmaf each; fmaxf(acc, 0) on hidden layers; then libm tanhf or the clamp; one multiply by scale, one
+   add of shift (two roundings; the build has -ffp-contract=off).  u (nullable) [M][act_dim]: the value before the
+   output activation; a [M][act_dim]: the action.  *subnormals (nullable): how many of the values formed on the way
+   (every partial sum, u, the activation, the product, the action) were non-zero subnormals. */
+static int is_subnormal(float v) { return v != 0.0f && fabsf(v) < 1.17549435e-38f; }
+
+int salp_oracle_policy_forward(const salp_policy_desc_t* desc, int32_t obs_dim, int32_t act_dim, const float* weights,
+                               const float* obs, int64_t M, float* u, float* a, int64_t* subnormals) {
+  if (!desc || !weights || !obs || !a || M < 0) return -1;
+  if (desc->struct_size != sizeof(salp_policy_desc_t) || desc->n_hidden < 0 || desc->n_hidden > 2) return -1;
+  if (obs_dim < 1 || obs_dim > 64 || act_dim < 1 || act_dim > 2) return -1;
+  if (desc->out_activation != SALP_POLICY_OUT_TANH && desc->out_activation != SALP_POLICY_OUT_CLIP) return -1;
+  int width[4], L = 0;                     /* layer l maps width[l] inputs to width[l + 1] outputs */
+  width[L++] = obs_dim;
+  for (int l = 0; l < desc->n_hidden; ++l) {
+    const int w = desc->hidden[l];
+    if (w < 16 || w > 64 || w % 16) return -1;
+    width[L++] = w;
+  }
+  width[L] = act_dim;
+  size_t words = 0;
+  for (int l = 0; l < L; ++l) words += (size_t)width[l + 1] * width[l] + width[l + 1];
+  const float* scale = weights + words;
+  const float* shift = scale + act_dim;
+  int64_t sub = 0;
+#pragma omp parallel for num_threads(g_threads) schedule(static) reduction(+ : sub)
+  for (int64_t m = 0; m < M; ++m) {
+    float x[64], y[64];
+    for (int i = 0; i < obs_dim; ++i) x[i] = obs[m * obs_dim + i];
+    const float* p = weights;
+    for (int l = 0; l < L; ++l) {
+      const int in = width[l], out = width[l + 1];
+      const float* W = p;
+      const float* b = p + (size_t)out * in;
+      for (int j = 0; j < out; ++j) {
+        float acc = b[j];
+        for (int i = 0; i < in; ++i) {
+          acc = fmaf(W[(size_t)j * in + i], x[i], acc);
+          sub += is_subnormal(acc);
+        }
+        y[j] = (l + 1 < L) ? fmaxf(acc, 0.0f) : acc;
+      }
+      for (int j = 0; j < out; ++j) x[j] = y[j];
+      p = b + out;
+    }
+    for (int k = 0; k < act_dim; ++k) {
+      const float uk = x[k];
+      const float t = desc->out_activation == SALP_POLICY_OUT_CLIP ? fminf(fmaxf(uk, -1.0f), 1.0f) : tanhf(uk);
+      const float prod = t * scale[k];
+      const float ak = prod + shift[k];
+      sub += is_subnormal(t) + is_subnormal(prod) + is_subnormal(ak);
+      if (u) u[m * act_dim + k] = uk;
+      a[m * act_dim + k] = ak;
+    }
+  }
+  if (subnormals) *subnormals = sub;
+  return 0;
+}

@@ -37,6 +37,11 @@ int salp_oracle_get_state(salp_oracle_t* h, double* f64, int32_t* i32);
 int salp_oracle_set_state(salp_oracle_t* h, const double* f64, const int32_t* i32);
 int64_t salp_oracle_global_step(const salp_oracle_t* h);
 int salp_oracle_set_base_num_food(salp_oracle_t* h, int k);   /* snake:36 base_num_food_items, 0..num_food_items */
+/* The in-kernel policy (include/salp_vec.h "Policy") in the header's own arithmetic, from the public weight layout of
+ * ONE policy: obs [M][obs_dim] -> u [M][act_dim] (nullable; before the output activation) and a [M][act_dim].
+ * subnormals (nullable): the number of non-zero subnormal values formed on the way.  See salp_oracle.c. */
+int salp_oracle_policy_forward(const salp_policy_desc_t* desc, int32_t obs_dim, int32_t act_dim, const float* weights,
+                               const float* obs, int64_t M, float* u, float* a, int64_t* subnormals);
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,7 @@ def lib():
         L.salp_oracle_global_step.argtypes = [vp]
         L.salp_oracle_global_step.restype = i64
         L.salp_oracle_set_base_num_food.argtypes = [vp, ctypes.c_int]
+        L.salp_oracle_policy_forward.argtypes = [vp, i32, i32, vp, vp, i64, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -68,6 +69,35 @@ def philox(counter, key):
     out = np.zeros(4, dtype=np.uint32)
     lib().salp_oracle_philox4x32_10(_p(c), _p(k), _p(out))
     return tuple(int(v) for v in out)
+
+
+def policy_forward(policy, obs, weights=None):
+    """The in-kernel policy restated in C in the arithmetic include/salp_vec.h promises (salp_oracle_policy_forward): fp32,
+    bias first, one fmaf per input in ascending index order, two roundings behind the output activation.
+    `policy`: an `MLPPolicy` (its shape; P >= 1); `weights`: float32 [P, words] in the public layout, default
+    `policy.pack()`; obs [..., N, obs_dim], env i of the N belonging to policy i // (N / P).
+    Returns u (before the output activation) and a, float32 [..., N, act_dim], and the number of non-zero subnormal values
+    formed on the way."""
+    x = np.ascontiguousarray(obs, dtype=np.float32)
+    P, OD, AD = policy.n_policies, policy.obs_dim, policy.act_dim
+    if x.shape[-1] != OD:
+        raise ValueError(f"obs rows have {x.shape[-1]} columns, the policy takes {OD}")
+    w = np.ascontiguousarray(policy.pack() if weights is None else weights, dtype=np.float32).reshape(P, policy.words)
+    policy.check_envs(x.shape[-2])
+    lead, N = x.shape[:-2], x.shape[-2]
+    g = np.ascontiguousarray(np.moveaxis(x.reshape(-1, P, N // P, OD), 1, 0))           # [P, L, G, OD]
+    u = np.empty(g.shape[:-1] + (AD,), np.float32)
+    a = np.empty_like(u)
+    d, total = policy.desc(), 0
+    for k in range(P):
+        sub = ctypes.c_int64(0)
+        rc = lib().salp_oracle_policy_forward(ctypes.byref(d), OD, AD, _p(w[k]), _p(g[k]), g[k].size // OD, _p(u[k]), _p(a[k]),
+                                              ctypes.byref(sub))
+        if rc != 0:
+            raise RuntimeError(f"salp_oracle_policy_forward failed: {rc}")
+        total += sub.value
+    back = lambda v: np.ascontiguousarray(np.moveaxis(v, 0, 1)).reshape(lead + (N, AD))
+    return back(u), back(a), total
 
 
 class OracleVec:

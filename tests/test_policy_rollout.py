@@ -5,6 +5,7 @@ with an error bound small enough that the GPU comparison means something."""
 import numpy as np
 import pytest
 
+import oracle_lib as ol
 import parity_cases as pc
 import policy_cases as cases
 from underwater_swimmer_rl_amd.policy import MLPPolicy, U, pursuit_policy
@@ -18,7 +19,8 @@ def _actor(hidden, act_dim=1, free=False, seed=0):
     return Actor(24, act_dim, hidden=hidden, act_low=low, act_high=high)
 
 
-@pytest.mark.parametrize("hidden,act_dim,free", [((32, 32), 1, False), ((64, 16), 2, True), ((48,), 1, False)])
+@pytest.mark.parametrize("hidden,act_dim,free", [((32, 32), 1, False), ((64, 16), 2, True), ((48,), 1, False), ((16, 64), 1, False),
+                                                 ((48, 32), 2, True)])
 def test_pack_reproduces_the_actors_parameters(hidden, act_dim, free):
     actor = _actor(hidden, act_dim, free)
     p = MLPPolicy.from_actor(actor)
@@ -103,19 +105,15 @@ def test_argument_validation():
 
 
 def _fp32_forward(p, obs):
-    """The library's arithmetic emulated on the CPU: float32, bias first, inputs in index order, one fused multiply-add
-    each (a float64 product of two float32 is exact, so rounding acc + w x once to float32 IS the fma)."""
-    x = obs.astype(np.float32)
-    for li, (W, b) in enumerate(p.layers):
-        acc = np.broadcast_to(b[0], x.shape[:-1] + (W.shape[1],)).astype(np.float32)
-        for i in range(W.shape[2]):
-            acc = (acc.astype(np.float64) + W[0, :, i].astype(np.float64) * x[..., i:i + 1].astype(np.float64)).astype(np.float32)
-        x = np.maximum(acc, np.float32(0)) if li + 1 < len(p.layers) else acc
-    t = np.tanh(x.astype(np.float64)).astype(np.float32) if p.out == "tanh" else np.clip(x, np.float32(-1), np.float32(1))
-    return (t * p.scale[0]).astype(np.float32) + p.shift[0]
+    """The library's arithmetic on the CPU: float32, bias first, inputs in index order, one fmaf each, tanhf or the clamp,
+    two roundings — the C restatement of include/salp_vec.h "Policy" (oracle/salp_oracle.c salp_oracle_policy_forward)."""
+    u, a, subnormals = ol.policy_forward(p, obs)
+    assert subnormals == 0
+    return a
 
 
-@pytest.mark.parametrize("hidden,out", [((32, 32), "tanh"), ((64, 64), "tanh"), ((16,), "tanh"), ((), "clip")])
+@pytest.mark.parametrize("hidden,out", [((32, 32), "tanh"), ((64, 64), "tanh"), ((16,), "tanh"), ((), "clip"), ((16, 64), "tanh"),
+                                        ((48, 32), "clip")])
 def test_error_bound_covers_an_fp32_evaluation_and_is_not_slack(hidden, out):
     p = cases.random_policy(24, 2, hidden, out, 7, 1.0, 3.0, free_breathing=True)
     obs = np.random.default_rng(5).uniform(-1.2, 1.2, (4000, 24)).astype(np.float32)
