@@ -50,6 +50,18 @@
  *     a_j = (w >> 8) * 2^-23 - 1   in [-1, 1)      (nozzle direction)
  *     a_0 = (w >> 8) * 2^-24       in [0, 1)       (inhale control, 2-action mode only)
  *   (one block serves four consecutive steps of a component).
+ *   Policy noise (salp_vec_rollout_policy_sampled, salp_vec_evaluate_policy_sampled; "Sampled actions" below):
+ *     block(env, n) = Philox4x32-10(counter = (env_lo, env_hi, n, 3), key)
+ *   env is the global env index, n the low 32 bits of the policy's noise step for that env-step (the fourth counter word
+ *   separates the streams: 0 env draws, 1 and 2 device action streams, 3 policy noise).  The env's own draw counter
+ *   (SALP_I_RNG_COUNTER) is not consumed: the simulator's trajectory stays a function of the actions alone.
+ *   Action component j takes one standard normal draw from words (w[2j], w[2j+1]) of the one block, fp32 (Box-Muller):
+ *     u1 = ((w[2j] >> 8) + 1) * 2^-24   in (0, 1]       u2 = (w[2j+1] >> 8) * 2^-24   in [0, 1)
+ *     z  = sqrtf(-2 * logf(u1)) * cospif(2 * u2)         (cospif, the device library's cos(pi x), is the one used)
+ *   The noise step is a 64-bit device word owned by the policy object: the kernels read it at entry (the action of step t
+ *   of a call uses n0 + t), and a one-thread kernel enqueued behind the call's launches adds `horizon` — so a replayed
+ *   hipGraph draws fresh noise.  salp_policy_create_gaussian starts it at 0; salp_vec_reseed re-keys the stream (the key
+ *   is the handle's) and leaves the step alone.
  */
 #ifndef SALP_VEC_H
 #define SALP_VEC_H
@@ -279,6 +291,45 @@ int salp_policy_create(salp_vec_t* h, const salp_policy_desc_t* desc, const floa
 int salp_policy_update(salp_policy_t* pol, const float* weights, uint32_t flags, void* stream);
 void salp_policy_destroy(salp_policy_t* pol);
 
+/* Gaussian policy: the stochastic actor of the learners (sac.Actor: mean and log-std heads on one body, tanh squashing).
+ * Weights of ONE policy, float32, `salp_policy_words_gaussian` words: the hidden layers as above; then the mean head
+ * W_mu[A][in], b_mu[A]; then the log-std head W_ls[A][in], b_ls[A]; then scale[A], shift[A].  out_activation must be
+ * SALP_POLICY_OUT_TANH; the other ranges (0-2 hidden layers of 16..64 units, K = 3 handles, P and n_envs) are those of
+ * salp_policy_create.  The result is an ordinary salp_policy_t: salp_policy_update takes the Gaussian layout for it, and
+ * salp_vec_rollout_policy / salp_vec_evaluate_policy run its MEAN — every output equals, bit for bit, that of the plain
+ * policy built from the same body and mean head. */
+int salp_policy_words_gaussian(const salp_vec_t* h, const salp_policy_desc_t* desc);
+int salp_policy_create_gaussian(salp_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags, void* stream,
+                                salp_policy_t** out);
+/* The noise step of a Gaussian policy ("Randomness").  set: stream-ordered (a one-thread kernel on `stream`).  get: waits for
+ * the stream of the policy's most recent create / update / set / sampled call, then reads the word with a blocking copy — so
+ * it must not be called while a stream is capturing.  Ordering is stream ordering and nothing else: salp_policy_set_noise_step
+ * and the sampled calls that are to see its value must be issued on the same stream (or on streams the caller has ordered).
+ * The sampled entry points take the policy as const and still advance this word on the device: a salp_policy_t is not
+ * thread-safe, like the handle it is bound to.  SALP_ERR_INVALID for a policy that is not Gaussian. */
+int salp_policy_set_noise_step(salp_policy_t* pol, uint64_t n, void* stream);
+int salp_policy_noise_step(salp_policy_t* pol, uint64_t* n);
+
+/* Sampled actions: salp_vec_rollout_policy / salp_vec_evaluate_policy with the stochastic form of a Gaussian policy.  Per
+ * action component j, fp32, in one fixed order in every kernel (z_j: the draw of "Randomness" for this env and noise step):
+ *   mu = mean head (the deterministic arithmetic above);  ls = the log-std head in the same fmaf order, then
+ *   ls = fminf(fmaxf(ls, -20), 2);  sd = expf(ls);  u = fmaf(sd, z, mu);  a = tanhf(u) * scale + shift   (two roundings)
+ *   m = -2 * u;  sp = fmaxf(m, 0) + log1pf(expf(-fabsf(m)));  c = (log 2 - u) - sp
+ *   g = -0.5 * (z * z);  g = g - ls;  g = g - 0.5 log(2 pi);  g = g - 2 * c;      logp = 0 + g_0 (+ g_1), in index order
+ * — sac.Actor.forward's value with (u - mu) / std taken as z.  Every operation above is one fp32 rounding (no contraction).
+ * Which observation each action sees (the bit-exact prologue row included), P > 1 assignment, autoreset, state write-back,
+ * global step, statistics, the split launch for ragged n, device / host pointers and capturability are those of the
+ * deterministic twins.  logp_out (may be NULL): float [horizon][n_envs]; act_out may be NULL.  After the launches the policy's
+ * noise step has advanced by `horizon` (on the device, stream-ordered; if that last one-thread launch itself fails the call
+ * returns the HIP error with the envs stepped and the noise step not advanced: set it before sampling on).
+ * SALP_ERR_INVALID, with nothing launched and the handle and the noise step unchanged, for a policy that is not Gaussian
+ * and for everything the deterministic twin refuses. */
+int salp_vec_rollout_policy_sampled(salp_vec_t* h, const salp_policy_t* pol, int32_t horizon, float* obs, float* reward,
+                                    uint8_t* terminated, uint8_t* truncated, float* act_out, float* logp_out,
+                                    uint32_t flags, void* stream);
+int salp_vec_evaluate_policy_sampled(salp_vec_t* h, const salp_policy_t* pol, int32_t horizon, void* rec,
+                                     uint32_t flags, void* stream);
+
 /* rollout() with the actions computed in the kernel: the action of step 0 is the policy applied to the env's current
  * observation; the action of step t + 1 is the policy applied to the row written to obs[t] (after a same-step autoreset
  * the first observation of the new episode; with no_autoreset the row as returned).
@@ -357,7 +408,8 @@ int64_t salp_vec_global_step(const salp_vec_t* h);
  * final_obs and / or info, 0 = some of the four is NULL (every store tested; always 0 for the generic instantiation's unpacked calls),
  * 3 = the packed record (both halves of a split launch and the generic instantiation too), 4 = the per-env summary record and
  * no per-step output (salp_vec_evaluate_policy: both halves; always with [5] == 2), [5] 1 = actions drawn in the kernel,
- * 2 = actions computed by a policy in the kernel (salp_vec_rollout_policy, salp_vec_evaluate_policy),
+ * 2 = actions computed by a policy in the kernel (salp_vec_rollout_policy, salp_vec_evaluate_policy), 3 = actions sampled
+ * from a Gaussian policy in the kernel (salp_vec_rollout_policy_sampled, salp_vec_evaluate_policy_sampled: separate instantiations),
  * [6] envs served by the unpredicated launch (whole wavefronts), [7] envs served by the predicated launch.
  * [4] is the signature of the kernel that ran: the unpredicated launch's when there was one, else the predicated launch's
  * (predicated kernels exist for signatures 1, 3, 4 and 0 only: a call with final_obs / info runs them as 0). */

@@ -38,6 +38,8 @@ EXPORTS = (
     "salp_vec_record_width", "salp_vec_step_packed", "salp_vec_rollout_packed",
     "salp_policy_words", "salp_policy_create", "salp_policy_update", "salp_policy_destroy", "salp_vec_rollout_policy",
     "salp_vec_evaluate_policy",
+    "salp_policy_words_gaussian", "salp_policy_create_gaussian", "salp_policy_set_noise_step", "salp_policy_noise_step",
+    "salp_vec_rollout_policy_sampled", "salp_vec_evaluate_policy_sampled",
 )
 
 
@@ -119,6 +121,14 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         L.salp_vec_rollout_policy.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, u32, vp]
     if path is None or hasattr(L, "salp_vec_evaluate_policy"):
         L.salp_vec_evaluate_policy.argtypes = [vp, vp, i32, vp, u32, vp]
+    if path is None or hasattr(L, "salp_vec_rollout_policy_sampled"):
+        from .policy import CPolicyDesc
+        L.salp_policy_words_gaussian.argtypes = [vp, ctypes.POINTER(CPolicyDesc)]
+        L.salp_policy_create_gaussian.argtypes = [vp, ctypes.POINTER(CPolicyDesc), vp, u32, vp, ctypes.POINTER(vp)]
+        L.salp_policy_set_noise_step.argtypes = [vp, u64, vp]
+        L.salp_policy_noise_step.argtypes = [vp, ctypes.POINTER(u64)]
+        L.salp_vec_rollout_policy_sampled.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, u32, vp]
+        L.salp_vec_evaluate_policy_sampled.argtypes = [vp, vp, i32, vp, u32, vp]
     L.salp_vec_global_step.argtypes = [vp]
     L.salp_vec_global_step.restype = i64
     L.salp_vec_set_base_num_food.argtypes = [vp, i32]
@@ -211,20 +221,24 @@ class SalpLib:
     def policy_words(self, policy) -> int:
         """salp_policy_words: float32 words of one policy of this shape on this handle (raises for a shape out of range)."""
         d = policy.desc()
-        rc = self.lib.salp_policy_words(self._h, ctypes.byref(d))
+        gauss = bool(getattr(policy, "gaussian", False))
+        rc = (self.lib.salp_policy_words_gaussian if gauss else self.lib.salp_policy_words)(self._h, ctypes.byref(d))
         if rc < 0:
-            check(self.lib, rc, "salp_policy_words")
+            check(self.lib, rc, "salp_policy_words_gaussian" if gauss else "salp_policy_words")
         return int(rc)
 
     def policy_create(self, policy, weights=None, flags=0, stream=0) -> "PolicyHandle":
         """salp_policy_create for an `MLPPolicy` (shape and, unless `weights` is given, its packed float32 weights; `weights`
-        with SALP_DEVICE_PTRS: a device block in the public layout [P, words])."""
+        with SALP_DEVICE_PTRS: a device block in the public layout [P, words]); salp_policy_create_gaussian for a
+        `GaussianPolicy`."""
         d = policy.desc()
         w = policy.pack() if weights is None else weights
         h = ctypes.c_void_p()
-        check(self.lib, self.lib.salp_policy_create(self._h, ctypes.byref(d), self._ptr(w), flags, ctypes.c_void_p(stream),
-                                                    ctypes.byref(h)), "salp_policy_create")
-        ph = PolicyHandle(self, h, policy.n_policies, int(policy.words))
+        gauss = bool(getattr(policy, "gaussian", False))
+        name = "salp_policy_create_gaussian" if gauss else "salp_policy_create"
+        check(self.lib, getattr(self.lib, name)(self._h, ctypes.byref(d), self._ptr(w), flags, ctypes.c_void_p(stream),
+                                                ctypes.byref(h)), name)
+        ph = PolicyHandle(self, h, policy.n_policies, int(policy.words), gauss)
         if not hasattr(self, "_policies"):
             self._policies = []
         self._policies.append(ph)
@@ -246,6 +260,18 @@ class SalpLib:
         SALP_DEVICE_PTRS and / or EVAL_ACCUMULATE (continue the records in `rec`)."""
         check(self.lib, self.lib.salp_vec_evaluate_policy(self._h, handle._p, int(horizon), self._ptr(rec), flags,
                                                           ctypes.c_void_p(stream)), "salp_vec_evaluate_policy")
+
+    def rollout_policy_sampled(self, handle: "PolicyHandle", horizon, obs, reward, term, trunc, act_out, logp_out, flags, stream=0):
+        """salp_vec_rollout_policy_sampled: a Gaussian policy's sampled actions; act_out and logp_out may be None."""
+        check(self.lib, self.lib.salp_vec_rollout_policy_sampled(self._h, handle._p, int(horizon), self._ptr(obs), self._ptr(reward),
+                                                                 self._ptr(term), self._ptr(trunc), self._ptr(act_out),
+                                                                 self._ptr(logp_out), flags, ctypes.c_void_p(stream)),
+              "salp_vec_rollout_policy_sampled")
+
+    def evaluate_policy_sampled(self, handle: "PolicyHandle", horizon, rec, flags, stream=0):
+        """salp_vec_evaluate_policy_sampled: evaluate_policy under a Gaussian policy's sampled actions."""
+        check(self.lib, self.lib.salp_vec_evaluate_policy_sampled(self._h, handle._p, int(horizon), self._ptr(rec), flags,
+                                                                  ctypes.c_void_p(stream)), "salp_vec_evaluate_policy_sampled")
 
     def reseed(self, seed, obs, flags, stream=0):
         """New draw streams keyed by `seed`, every env reset from draw counter 0; no reallocation (capture-safe)."""
@@ -310,8 +336,21 @@ class SalpLib:
 class PolicyHandle:
     """One salp_policy_t: a policy block on a handle's device (SalpLib.policy_create)."""
 
-    def __init__(self, owner: SalpLib, p, n_policies: int, words: int):
+    def __init__(self, owner: SalpLib, p, n_policies: int, words: int, gaussian: bool = False):
         self.owner, self._p, self.n_policies, self.words = owner, p, int(n_policies), int(words)
+        self.gaussian = bool(gaussian)
+
+    @property
+    def noise_step(self) -> int:
+        """salp_policy_noise_step: the Gaussian policy's noise step (waits for the policy's last stream)."""
+        n = ctypes.c_uint64()
+        check(self.owner.lib, self.owner.lib.salp_policy_noise_step(self._p, ctypes.byref(n)), "salp_policy_noise_step")
+        return int(n.value)
+
+    def set_noise_step(self, n: int, stream=0):
+        """salp_policy_set_noise_step: stream-ordered."""
+        check(self.owner.lib, self.owner.lib.salp_policy_set_noise_step(self._p, int(n) & 0xFFFFFFFFFFFFFFFF, ctypes.c_void_p(stream)),
+              "salp_policy_set_noise_step")
 
     def update(self, weights, flags=0, stream=0):
         self.owner.policy_update(self, weights, flags, stream)

@@ -8,6 +8,14 @@
 //                                                        W[16 c + j][i], j = 0 .. 15        (16 (IN + 1) words per chunk)
 //   tail (16 words):                                     b_last[A], scale[A], shift[A], zero padding
 //   last layer, per action a:                            W_last[a][0 .. IN-1], zero-padded to a multiple of 16 words
+// A Gaussian policy (salp_policy_create_gaussian; header word PH_GAUSS then holds the value 1 — a mark for whoever inspects a block,
+// no kernel reads it: the host decides from its own record which kernels a policy may run) carries its log-std head behind that, in the
+// same form:
+//   log-std tail (16 words):                             b_ls[A], zero padding
+//   log-std head, per action a:                          W_ls[a][0 .. IN-1], zero-padded to a multiple of 16 words
+// so the block of its mean policy is a prefix of each policy's words and the deterministic evaluation never reads the rest.
+// Header words PH_NOISE, PH_NOISE + 1: the policy's 64-bit noise step (include/salp_vec.h "Randomness"), read by the
+// sampling kernels at entry and advanced by a one-thread kernel behind them.
 // The weights are wave-uniform (a wavefront never mixes policies), so everything is read through the constant address
 // space with scalar loads (s_load_dwordx16: one load feeds 16 v_fmac with a scalar operand each); the base is made opaque
 // inside policy_eval so that the loads stay in the function instead of being hoisted across the step loop.
@@ -15,7 +23,8 @@
 // Arithmetic (fixed, the same in every instantiation): fp32; every unit starts from its bias and adds its inputs in index
 // order with one fmaf each; relu = fmaxf(., 0); tanhf or a clamp to [-1, 1]; then one multiply by scale and one add of
 // shift (two roundings).  The last layer is fused into the chunk loop of the layer before it — chunks and their units
-// are visited in index order, so its sum keeps the same order — and the only activations that are stored are those of
+// are visited in index order, so its sum keeps the same order (the log-std head of a sampling evaluation rides along in the
+// same way) — and the only activations that are stored are those of
 // the FIRST of two hidden layers: at most 64 VGPRs (indexed at compile time; the widths are run-time values tested per
 // group of 16, wave-uniform).
 #pragma once
@@ -23,7 +32,7 @@
 
 namespace salp {
 
-enum { PH_NHIDDEN = 0, PH_H0, PH_H1, PH_OUT, PH_STRIDE, PH_GROUP, PH_COUNT, PH_WORDS = 16 };
+enum { PH_NHIDDEN = 0, PH_H0, PH_H1, PH_OUT, PH_STRIDE, PH_GROUP, PH_COUNT, PH_GAUSS, PH_NOISE = 8 /* two words, lo then hi */, PH_WORDS = 16 };
 enum { POLICY_CHUNK = 16, POLICY_MAX_HIDDEN = 64, POLICY_TAIL_WORDS = 16 };
 
 #ifdef __HIPCC__
@@ -64,8 +73,11 @@ __device__ __forceinline__ void policy_last_chunk(pol_float* wl, int row_stride,
 
 // The action of one env from its observation row `x` (OD = 24 floats in registers).  `blk`: the device block;
 // `pol_off`: word offset of this wavefront's policy behind the header (wave-uniform).
-template <int OD, int AD>
-__device__ __forceinline__ void policy_eval(const float* blk, uint32_t pol_off, const float (&x)[OD], float& c0, float& c1) {
+// SAMPLED: the tanh-Gaussian sample of include/salp_vec.h "Sampled actions" from the standard normal draws z0, z1; `logp`
+// receives its log-probability.  The mean's arithmetic is that of the deterministic evaluation, unit by unit.
+template <int OD, int AD, bool SAMPLED>
+__device__ __forceinline__ void policy_eval_impl(const float* blk, uint32_t pol_off, const float (&x)[OD], float& c0, float& c1,
+                                                 [[maybe_unused]] float z0, [[maybe_unused]] float z1, [[maybe_unused]] float& logp) {
   static_assert(OD == 24, "the policy kernels exist for max_observed_food == 3");
   const uint64_t adr = (uint64_t)(uintptr_t)blk;
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)adr);
@@ -82,6 +94,16 @@ __device__ __forceinline__ void policy_eval(const float* blk, uint32_t pol_off, 
   pol_float* wl = tail + POLICY_TAIL_WORDS;
   const pol_v8 tl = pol_load8(tail);      // b_last[AD], scale[AD], shift[AD]
   float u[2] = {tl[0], AD == 2 ? tl[1] : 0.f};
+  [[maybe_unused]] float ls[2] = {0.f, 0.f};        // SAMPLED: the log-std head's sums
+  [[maybe_unused]] pol_float* wl2 = wl;
+  if constexpr (SAMPLED) {
+    const int rs = nh == 0 ? 2 * POLICY_CHUNK : (nh == 1 ? h0 : h1);      // row stride of the last layer
+    pol_float* tail2 = wl + AD * rs;
+    wl2 = tail2 + POLICY_TAIL_WORDS;
+    const pol_v8 t2 = pol_load8(tail2);    // b_ls[AD]
+    ls[0] = t2[0];
+    if (AD == 2) ls[1] = t2[1];
+  }
 
   if (nh == 0) {
 #pragma unroll
@@ -93,6 +115,17 @@ __device__ __forceinline__ void policy_eval(const float* blk, uint32_t pol_off, 
 #pragma unroll
       for (int i = 0; i < 8; ++i) u[a] = __builtin_fmaf(wb[i], x[16 + i], u[a]);
     }
+    if constexpr (SAMPLED) {
+#pragma unroll
+      for (int a = 0; a < AD; ++a) {
+        const pol_v16 wa = pol_load16(wl2 + a * 32);
+        const pol_v8 wb = pol_load8(wl2 + a * 32 + 16);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) ls[a] = __builtin_fmaf(wa[i], x[i], ls[a]);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ls[a] = __builtin_fmaf(wb[i], x[16 + i], ls[a]);
+      }
+    }
   } else if (nh == 1) {
 #pragma unroll 1
     for (int c = 0; c < c0n; ++c) {
@@ -101,6 +134,7 @@ __device__ __forceinline__ void policy_eval(const float* blk, uint32_t pol_off, 
 #pragma unroll
       for (int j = 0; j < POLICY_CHUNK; ++j) acc[j] = fmaxf(acc[j], 0.f);
       policy_last_chunk<AD>(wl, h0, c, acc, u);
+      if constexpr (SAMPLED) policy_last_chunk<AD>(wl2, h0, c, acc, ls);
     }
   } else {
     float h[POLICY_MAX_HIDDEN];
@@ -140,15 +174,53 @@ __device__ __forceinline__ void policy_eval(const float* blk, uint32_t pol_off, 
 #pragma unroll
       for (int j = 0; j < POLICY_CHUNK; ++j) acc[j] = fmaxf(acc[j], 0.f);
       policy_last_chunk<AD>(wl, h1, c, acc, u);
+      if constexpr (SAMPLED) policy_last_chunk<AD>(wl2, h1, c, acc, ls);
     }
   }
+  if constexpr (SAMPLED) {
+    // a Gaussian policy's output activation is tanh (salp_policy_create_gaussian); the log-probability's terms are added
+    // in component order, each a fixed sequence of fp32 roundings (include/salp_vec.h "Sampled actions")
+    float lp = 0.f;
 #pragma unroll
-  for (int a = 0; a < AD; ++a) {
-    const float v = out_act ? fminf(fmaxf(u[a], -1.0f), 1.0f) : tanhf(u[a]);
-    u[a] = v * tl[AD + a] + tl[2 * AD + a];
+    for (int a = 0; a < AD; ++a) {
+      const float z = a == 0 ? z0 : z1;
+      const float l = fminf(fmaxf(ls[a], -20.0f), 2.0f);
+      const float sd = expf(l);
+      const float s = __builtin_fmaf(sd, z, u[a]);
+      const float m2 = -2.0f * s;
+      const float sp = fmaxf(m2, 0.f) + log1pf(expf(-fabsf(m2)));
+      const float c = (0.693147180559945309f - s) - sp;
+      float g = -0.5f * (z * z);
+      g = g - l;
+      g = g - 0.918938533204672742f;
+      g = g - 2.0f * c;
+      lp = lp + g;
+      u[a] = tanhf(s) * tl[AD + a] + tl[2 * AD + a];
+    }
+    logp = lp;
+  } else {
+#pragma unroll
+    for (int a = 0; a < AD; ++a) {
+      const float v = out_act ? fminf(fmaxf(u[a], -1.0f), 1.0f) : tanhf(u[a]);
+      u[a] = v * tl[AD + a] + tl[2 * AD + a];
+    }
   }
   c0 = u[0];
   if (AD == 2) c1 = u[1];
+}
+
+template <int OD, int AD>
+__device__ __forceinline__ void policy_eval(const float* blk, uint32_t pol_off, const float (&x)[OD], float& c0, float& c1) {
+  float unused = 0.f;
+  policy_eval_impl<OD, AD, false>(blk, pol_off, x, c0, c1, 0.f, 0.f, unused);
+}
+
+// One standard normal draw from two words of the policy's noise block (include/salp_vec.h "Randomness"): Box-Muller on
+// u1 in (0, 1], u2 in [0, 1), 24 bits each
+__device__ __forceinline__ float policy_normal(uint32_t wa, uint32_t wb) {
+  const float u1 = (float)((wa >> 8) + 1u) * 5.9604644775390625e-8f;
+  const float u2 = (float)(wb >> 8) * 5.9604644775390625e-8f;
+  return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
 }
 #endif  // __HIPCC__
 

@@ -45,7 +45,14 @@ constexpr int kWave = 64;
 //   and 4 slots: 2 (256 registers, no scratch).  8 slots and more, and every predicated launch: 1 — at 2 they spilled 50-580 B
 //   per lane to scratch inside the step loop; at 1 the wavefront owns the SIMD's 512 registers and what does not fit in the
 //   256 VGPRs is parked in AGPRs (v_accvgpr_write / _read), not in memory (profiles/r05/policy_kernel_resources.txt).
-constexpr int waves_per_simd(int fmax, int kmax, bool std_consts, bool ragged, int sig, bool policy = false) {
+constexpr int waves_per_simd(int fmax, int kmax, bool std_consts, bool ragged, int sig, bool policy = false, bool sampled = false,
+                             bool forced = false) {
+  // The sampling policy kernels (ACT_POLICY_SAMPLED) take their deterministic twins' bounds, but for six unpredicated kernels
+  // that at 2 held 2-16 scratch instructions (12-36 B per lane) where the twin holds fewer or none — the 4-slot rollout kernels,
+  // the free-breathing 4-slot summary kernel with literal constants, the free-breathing one-food summary kernel with run-time
+  // constants: 1.  From the code-object metadata of all 80: profiles/r07/sampled_kernel_resources.txt.
+  if (sampled && !ragged && fmax == 4 && (sig == 1 || !forced)) return 1;
+  if (sampled && !ragged && fmax == 1 && sig == 4 && !std_consts && !forced) return 1;
   // The summary kernels (sig 4) take their twins' bounds, but for the unpredicated 4-slot kernel with run-time constants: 1 (at 2
   // it sat at 255-256 VGPRs with 12-132 B of scratch, its twin holds 0-12 B; at 1 258-272 registers, 2-16 of them AGPRs, none).
   // From the code-object metadata of all 40: profiles/r06/eval_kernel_resources.txt.
@@ -73,7 +80,10 @@ struct IOPtrs {
   uint8_t* terminated;    // [H][n]
   uint8_t* truncated;     // [H][n]
   float* final_obs;       // [H][n][obs_dim] rows of finished envs only
-  int32_t* info;          // [H][n][3]
+  union {
+    int32_t* info;        // [H][n][3]
+    float* logp_out;      // ACT_POLICY_SAMPLED (whose signatures have no info): [H][n] or null
+  };
   float* act_out;         // [H][n][act_dim]
   DevStats* stats;        // [SALP_STATS_REPLICAS] or null
   int64_t global_step;    // step index of t = 0 (device-generated actions)
@@ -110,13 +120,17 @@ struct ColdBlock {
 // policy (salp_policy.h) applied to the env's current observation, computed in the prologue with the step's own
 // functions; the action of step t + 1 is the policy applied to the row just written to obs[t], evaluated from the
 // registers behind the tile flush, while the row stores drain.  No read stream; act_out as with ACT_GEN.
-enum { ACT_READ = 0, ACT_GEN = 1, ACT_POLICY = 2 };
+// ACT = ACT_POLICY_SAMPLED: the same closed loop with the stochastic form of a Gaussian policy (salp_vec_rollout_policy_sampled,
+// salp_vec_evaluate_policy_sampled): the action of step t is sampled with the policy's noise block n0 + t of the env, n0 =
+// the policy's noise step read from its device block at entry; its log-probability goes to logp_out with the action.
+enum { ACT_READ = 0, ACT_GEN = 1, ACT_POLICY = 2, ACT_POLICY_SAMPLED = 3 };
 template <int FMAX, int KMAX, bool FORCED, bool STD, int SIG, bool RAGGED, int ACT>
-__global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG, ACT == ACT_POLICY)) void salp_rollout_kernel(DevParams P_arg, DevState S, IOPtrs io, int H, int64_t env_begin, int64_t env_end, const ColdBlock* __restrict__ cold) {
+__global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG, ACT >= ACT_POLICY, ACT == ACT_POLICY_SAMPLED, FORCED)) void salp_rollout_kernel(DevParams P_arg, DevState S, IOPtrs io, int H, int64_t env_begin, int64_t env_end, const ColdBlock* __restrict__ cold) {
   // STD = false: where the hot path's constants come from (open_consts, salp_device.h) — the device copy, function by
   // function, for the 4- and 8-slot kernels; the by-value launch parameters for the others
   constexpr bool GEN = ACT == ACT_GEN;
-  constexpr bool POLICY = ACT == ACT_POLICY;
+  constexpr bool SAMPLED = ACT == ACT_POLICY_SAMPLED;
+  constexpr bool POLICY = ACT == ACT_POLICY || SAMPLED;
   // SIG 4 (kSigSummary): NO per-step output at all — salp_vec_evaluate_policy.  io.obs is the block of per-env summary records
   // ([n][SALP_EVAL_WORDS] words, include/salp_vec.h), io.final_obs non-NULL says that the records are read first and continued
   // (SALP_EVAL_ACCUMULATE).  The observation is formed in registers for the policy alone: no tile write, no flush, no
@@ -320,6 +334,8 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
     a1 = FORCED ? 0.f : io.act[envc * AD + 1];
   }
   uint32_t pol_off = 0u;    // POLICY: word offset of this wavefront's policy in the block (wave-uniform)
+  [[maybe_unused]] uint32_t noise0 = 0u;   // SAMPLED: low word of the policy's noise step at entry (wave-uniform)
+  [[maybe_unused]] float lp = 0.f;         // SAMPLED: log-probability of the action in a0 / a1
   if constexpr (POLICY) {
     if (rows > 0) {
       pol_int* const hd = (pol_int*)(uintptr_t)io.act;
@@ -327,6 +343,7 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
       uint32_t pi = (uint32_t)env0 / group;          // env i runs policy i / (n_envs / P)
       pi = pi < npol ? pi : npol - 1u;
       pol_off = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pi * (uint32_t)hd[PH_STRIDE]));
+      if constexpr (SAMPLED) noise0 = (uint32_t)hd[PH_NOISE];
       // the env's current observation, as the end of a step forms it (below), from the loaded state: the SAME bits as the
       // row of the step that left this state, so that a rollout cut into several calls takes the actions of one call.
       // The one thing in a row that the state does not spell out is which bearing polynomial its nearest food went
@@ -361,6 +378,11 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
         }
         observe<FMAX, KMAX, STD>(e, P, r0, have_rel0, rel0, ob0);
       }
+      if constexpr (SAMPLED) {
+        const U4 nw = philox4x32_10((uint32_t)genv, (uint32_t)(genv >> 32), noise0, 3u, P.seed[0], P.seed[1]);
+        policy_eval_impl<12 + 4 * KMAX, FORCED ? 1 : 2, true>(io.act, pol_off, ob0, a0, a1, policy_normal(nw.x, nw.y),
+                                                               FORCED ? 0.f : policy_normal(nw.z, nw.w), lp);
+      } else
       policy_eval<12 + 4 * KMAX, FORCED ? 1 : 2>(io.act, pol_off, ob0, a0, a1);
     }
   }
@@ -405,6 +427,9 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
       if (!SUMMARY && io.act_out && active) {
         io.act_out[(rowbase + env) * AD] = c0;
         if (!FORCED) io.act_out[(rowbase + env) * AD + 1] = c1;
+      }
+      if constexpr (SAMPLED && !SUMMARY) {
+        if (io.logp_out && active) io.logp_out[rowbase + env] = lp;
       }
     } else {  // prefetch the next step's action (the last step re-reads its own: keeps the load unconditional)
       const int64_t nb = (rowbase + ((t + 1 < H) ? P.n : 0) + envc) * AD;
@@ -714,6 +739,13 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
       }
       // the next step's action from this step's row, while the row stores are in flight (the last step needs none)
       if constexpr (POLICY) {
+        if constexpr (SAMPLED) {
+          if (SUMMARY || t + 1 < Hrun) {
+            const U4 nw = philox4x32_10((uint32_t)genv, (uint32_t)(genv >> 32), noise0 + (uint32_t)(t + 1), 3u, P.seed[0], P.seed[1]);
+            policy_eval_impl<12 + 4 * KMAX, FORCED ? 1 : 2, true>(io.act, pol_off, ob, a0, a1, policy_normal(nw.x, nw.y),
+                                                                   FORCED ? 0.f : policy_normal(nw.z, nw.w), lp);
+          }
+        } else
         if (SUMMARY || t + 1 < Hrun) policy_eval<12 + 4 * KMAX, FORCED ? 1 : 2>(io.act, pol_off, ob, a0, a1);
       }
     }
@@ -974,7 +1006,8 @@ struct salp_policy {
   float* block;              // device: header + P policies, what the kernel reads
   float* pub;                // device: staging of the public layout [P][words] (host-pointer create / update)
   int32_t* map;              // device: word k of a policy in the block <- public word map[k] (-1: zero)
-  hipStream_t last_stream;   // the stream of the most recent create / update
+  int gaussian;              // salp_policy_create_gaussian: a log-std head behind the mean head, a noise step in the header
+  mutable hipStream_t last_stream;   // the stream of the most recent create / update / noise-step write (sampled calls included)
 };
 
 namespace {
@@ -1052,9 +1085,9 @@ typedef void (*reset_fn)(DevParams, DevState, const uint8_t*, float*, int);
 enum { kSigPartial = 0, kSigMain = 1, kSigExtras = 2, kSigPacked = 3, kSigSummary = 4 };
 template <int FMAX, int KMAX, bool FORCED, bool STD, bool RAGGED, int ACT>
 rollout_fn pick_sig(int sig) {
-  if constexpr (ACT == ACT_POLICY) {
-    if (sig == kSigSummary) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigSummary, RAGGED, ACT_POLICY>;
-    return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, ACT_POLICY>;
+  if constexpr (ACT == ACT_POLICY || ACT == ACT_POLICY_SAMPLED) {
+    if (sig == kSigSummary) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigSummary, RAGGED, ACT>;
+    return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, ACT>;
   } else if constexpr (ACT != ACT_READ) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, ACT>;
   else {
     if (sig == kSigMain) return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, ACT_READ>;
@@ -1064,9 +1097,11 @@ rollout_fn pick_sig(int sig) {
     return (rollout_fn)salp_rollout_kernel<FMAX, KMAX, FORCED, STD, kSigPartial, RAGGED, ACT_READ>;
   }
 }
-// `act`: where the actions come from (ACT_READ / ACT_GEN / ACT_POLICY)
+// `act`: where the actions come from (ACT_READ / ACT_GEN / ACT_POLICY / ACT_POLICY_SAMPLED)
 template <int FMAX, int KMAX, bool STD, bool RAGGED>
 rollout_fn pick_rollout(bool forced, int sig, int act) {
+  if ((sig == kSigMain || sig == kSigSummary) && act == ACT_POLICY_SAMPLED)   // the same two signatures, sampling
+    return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, ACT_POLICY_SAMPLED>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, ACT_POLICY_SAMPLED>(sig);
   if ((sig == kSigMain || sig == kSigSummary) && act == ACT_POLICY)   // the in-kernel policy exists for the main-only output signature and for the summary
     return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, ACT_POLICY>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, ACT_POLICY>(sig);
   if (sig == kSigMain && act == ACT_GEN)
@@ -1156,12 +1191,16 @@ struct Bump {  // carve sub-buffers out of the staging allocation
 };
 
 // packed: io.obs is a record block (kSigPacked), io.final_obs non-NULL asks for the terminal-observation tail
-// policy: io.act is a policy's device block (ACT_POLICY; the caller has checked K = 3 and the four main outputs)
+// policy: 0, or ACT_POLICY / ACT_POLICY_SAMPLED: io.act is a policy's device block (the caller has checked K = 3 and the four
+// main outputs; ACT_POLICY_SAMPLED: a Gaussian policy, io.logp_out may be set)
 // summary: io.obs is the block of summary records (kSigSummary; policy only), io.final_obs non-NULL = SALP_EVAL_ACCUMULATE
-int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, bool packed = false, bool policy = false, bool summary = false) {
+int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, bool packed = false, int policy = 0, bool summary = false) {
   const bool main_outputs = io.obs && io.reward && io.terminated && io.truncated;
-  const int sig = summary ? kSigSummary : packed ? kSigPacked : (!main_outputs ? kSigPartial : ((io.final_obs || io.info) ? kSigExtras : kSigMain));
-  const int gen = policy ? ACT_POLICY : (io.act == nullptr ? ACT_GEN : ACT_READ);   // ACT_GEN: only reached when can_generate_in_kernel()
+  // (policy: final_obs / info do not exist — io.final_obs is the summary's accumulate flag, io.info's slot holds logp_out)
+  const bool extras = !policy && (io.final_obs || io.info);
+  const int sig = summary ? kSigSummary : packed ? kSigPacked : (!main_outputs ? kSigPartial : (extras ? kSigExtras : kSigMain));
+  if (policy && sig != kSigMain && sig != kSigSummary) return fail(SALP_ERR_INVALID, "policy kernels exist for the main-only and the summary signature");
+  const int gen = policy ? policy : (io.act == nullptr ? ACT_GEN : ACT_READ);   // ACT_GEN: only reached when can_generate_in_kernel()
   // envs in full wavefronts: unpredicated kernel
   int64_t n_full = h->n / kWave * kWave;
   // A small ragged batch (step-per-launch acting loops) is launch-bound: one predicated launch over the whole
@@ -1209,8 +1248,16 @@ __global__ __launch_bounds__(kBlock) void salp_policy_relayout_kernel(float* __r
   block[PH_WORDS + i] = m >= 0 ? pub[p * words + m] : 0.f;
 }
 
+// The policy's noise step (header words PH_NOISE, PH_NOISE + 1 of its device block): one thread, behind the launches that read it
+__global__ void salp_policy_noise_kernel(float* block, uint64_t add, uint64_t set, int do_set) {
+  uint32_t* const w = reinterpret_cast<uint32_t*>(block) + PH_NOISE;
+  const uint64_t v = do_set ? set : ((((uint64_t)w[1] << 32) | w[0]) + add);
+  w[0] = (uint32_t)v;
+  w[1] = (uint32_t)(v >> 32);
+}
+
 // The descriptor's ranges (include/salp_vec.h).  On success *words = public words of one policy.
-int check_policy_desc(const salp_vec* h, const salp_policy_desc_t* d, int* words) {
+int check_policy_desc(const salp_vec* h, const salp_policy_desc_t* d, int* words, bool gaussian = false) {
   if (!h || !d) return fail(SALP_ERR_INVALID, "handle/desc is NULL");
   if (d->struct_size != sizeof(salp_policy_desc_t)) return fail(SALP_ERR_INVALID, "salp_policy_desc_t.struct_size mismatch");
   if (h->kmax != 3) return fail(SALP_ERR_INVALID, "policies need a handle with max_observed_food == 3");
@@ -1222,12 +1269,15 @@ int check_policy_desc(const salp_vec* h, const salp_policy_desc_t* d, int* words
   }
   if (d->out_activation != SALP_POLICY_OUT_TANH && d->out_activation != SALP_POLICY_OUT_CLIP)
     return fail(SALP_ERR_INVALID, "out_activation must be SALP_POLICY_OUT_TANH or SALP_POLICY_OUT_CLIP");
+  if (gaussian && d->out_activation != SALP_POLICY_OUT_TANH)
+    return fail(SALP_ERR_INVALID, "a Gaussian policy's out_activation must be SALP_POLICY_OUT_TANH");
   if (d->n_policies < 1) return fail(SALP_ERR_INVALID, "n_policies must be >= 1");
   if (d->n_policies > 1 && (h->n % d->n_policies != 0 || (h->n / d->n_policies) % kWave != 0))
     return fail(SALP_ERR_INVALID, "n_policies > 1 needs n_envs % P == 0 and (n_envs / P) % 64 == 0");
   int in = h->obs_dim, w = 0;
   for (int l = 0; l < d->n_hidden; ++l) { w += d->hidden[l] * in + d->hidden[l]; in = d->hidden[l]; }
   w += h->act_dim * in + 3 * h->act_dim;
+  if (gaussian) w += h->act_dim * in + h->act_dim;     // the log-std head
   if (words) *words = w;
   return SALP_OK;
 }
@@ -1647,12 +1697,12 @@ void salp_policy_destroy(salp_policy_t* pol) {
   delete pol;
 }
 
-int salp_policy_create(salp_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags, void* stream,
-                       salp_policy_t** out) {
+static int policy_create_impl(salp_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags, void* stream,
+                              salp_policy_t** out, bool gaussian) {
   if (!out) return fail(SALP_ERR_INVALID, "out is NULL");
   *out = nullptr;
   int words = 0;
-  int rc = check_policy_desc(h, desc, &words);
+  int rc = check_policy_desc(h, desc, &words, gaussian);
   if (rc != SALP_OK) return rc;
   if (!weights) return fail(SALP_ERR_INVALID, "weights is NULL");
   DeviceScope dev_scope;
@@ -1661,7 +1711,7 @@ int salp_policy_create(salp_vec_t* h, const salp_policy_desc_t* desc, const floa
   if (!pol) return fail(SALP_ERR_OOM, "host allocation failed");
   memset(pol, 0, sizeof(*pol));
   pol->h = h; pol->d = *desc; pol->device = h->device; pol->obs_dim = h->obs_dim; pol->act_dim = h->act_dim; pol->n = h->n;
-  pol->words = words;
+  pol->words = words; pol->gaussian = gaussian ? 1 : 0;
   // word k of a policy in the device block <- public word map[k] (salp_policy.h for the block, salp_vec.h for the public layout)
   const int AD = h->act_dim, nh = desc->n_hidden;
   std::string mapbuf;      // int32 entries
@@ -1677,11 +1727,17 @@ int salp_policy_create(salp_vec_t* h, const salp_policy_desc_t* desc, const floa
     pubo = bp + O; in = O;
   }
   {
-    const int Wl = pubo, bl = pubo + AD * in, sc = bl + AD, sh = sc + AD;
+    // Gaussian: W_mu, b_mu, W_ls, b_ls, scale, shift in the public layout; the log-std head behind the mean head in the block
+    const int Wl = pubo, bl = pubo + AD * in, W2 = bl + AD, b2 = W2 + AD * in, sc = gaussian ? b2 + AD : bl + AD, sh = sc + AD;
     for (int k = 0; k < POLICY_TAIL_WORDS; ++k) push(k < AD ? bl + k : (k < 2 * AD ? sc + k - AD : (k < 3 * AD ? sh + k - 2 * AD : -1)));
     const int rs = (in + POLICY_CHUNK - 1) / POLICY_CHUNK * POLICY_CHUNK;    // 24 -> 32 for the linear policy
     for (int a = 0; a < AD; ++a)
       for (int i = 0; i < rs; ++i) push(i < in ? Wl + a * in + i : -1);
+    if (gaussian) {
+      for (int k = 0; k < POLICY_TAIL_WORDS; ++k) push(k < AD ? b2 + k : -1);
+      for (int a = 0; a < AD; ++a)
+        for (int i = 0; i < rs; ++i) push(i < in ? W2 + a * in + i : -1);
+    }
   }
   pol->stride = (int)(mapbuf.size() / sizeof(int32_t));     // every piece above is a multiple of 16 words
   const size_t block_b = ((size_t)PH_WORDS + (size_t)desc->n_policies * pol->stride) * sizeof(float);
@@ -1694,7 +1750,7 @@ int salp_policy_create(salp_vec_t* h, const salp_policy_desc_t* desc, const floa
     int32_t hd[PH_WORDS];
     memset(hd, 0, sizeof(hd));
     hd[PH_NHIDDEN] = nh; hd[PH_H0] = desc->hidden[0]; hd[PH_H1] = desc->hidden[1]; hd[PH_OUT] = desc->out_activation;
-    hd[PH_STRIDE] = pol->stride; hd[PH_COUNT] = desc->n_policies;
+    hd[PH_STRIDE] = pol->stride; hd[PH_COUNT] = desc->n_policies; hd[PH_GAUSS] = pol->gaussian;   // (noise step: 0)
     hd[PH_GROUP] = desc->n_policies > 1 ? (int32_t)(h->n / desc->n_policies) : 0x7FFFFFFF;
     e = hipMemcpy(pol->block, hd, sizeof(hd), hipMemcpyHostToDevice);
   }
@@ -1709,6 +1765,45 @@ int salp_policy_create(salp_vec_t* h, const salp_policy_desc_t* desc, const floa
   return SALP_OK;
 }
 
+int salp_policy_create(salp_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags, void* stream,
+                       salp_policy_t** out) {
+  return policy_create_impl(h, desc, weights, flags, stream, out, false);
+}
+
+int salp_policy_words_gaussian(const salp_vec_t* h, const salp_policy_desc_t* desc) {
+  int words = 0;
+  const int rc = check_policy_desc(h, desc, &words, true);
+  return rc != SALP_OK ? rc : words;
+}
+
+int salp_policy_create_gaussian(salp_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags, void* stream,
+                                salp_policy_t** out) {
+  return policy_create_impl(h, desc, weights, flags, stream, out, true);
+}
+
+int salp_policy_set_noise_step(salp_policy_t* pol, uint64_t n, void* stream) {
+  if (!pol) return fail(SALP_ERR_INVALID, "policy is NULL");
+  if (!pol->gaussian) return fail(SALP_ERR_INVALID, "the policy is not Gaussian: it has no noise step");
+  DeviceScope dev_scope;
+  HIP_TRY(dev_scope.enter(pol->device));
+  pol->last_stream = (hipStream_t)stream;
+  hipLaunchKernelGGL(salp_policy_noise_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pol->block, (uint64_t)0, n, 1);
+  HIP_TRY(hipGetLastError());
+  return SALP_OK;
+}
+
+int salp_policy_noise_step(salp_policy_t* pol, uint64_t* n) {
+  if (!pol || !n) return fail(SALP_ERR_INVALID, "policy/n is NULL");
+  if (!pol->gaussian) return fail(SALP_ERR_INVALID, "the policy is not Gaussian: it has no noise step");
+  DeviceScope dev_scope;
+  HIP_TRY(dev_scope.enter(pol->device));
+  HIP_TRY(hipStreamSynchronize(pol->last_stream));
+  uint32_t w[2] = {0u, 0u};
+  HIP_TRY(hipMemcpy(w, reinterpret_cast<const uint32_t*>(pol->block) + PH_NOISE, sizeof(w), hipMemcpyDeviceToHost));
+  *n = ((uint64_t)w[1] << 32) | w[0];
+  return SALP_OK;
+}
+
 int salp_policy_update(salp_policy_t* pol, const float* weights, uint32_t flags, void* stream) {
   if (!pol || !weights) return fail(SALP_ERR_INVALID, "policy/weights is NULL");
   DeviceScope dev_scope;
@@ -1716,9 +1811,23 @@ int salp_policy_update(salp_policy_t* pol, const float* weights, uint32_t flags,
   return policy_upload(pol, weights, flags, (hipStream_t)stream);
 }
 
-int salp_vec_rollout_policy(salp_vec_t* h, const salp_policy_t* pol, int32_t H, float* obs, float* reward,
-                            uint8_t* terminated, uint8_t* truncated, float* act_out, uint32_t flags, void* stream) {
+// Behind the launches of a sampled call: the policy's noise step goes on by the call's horizon, on the device (a replayed
+// graph draws fresh noise).  The policy arrives const (the entry points' signature), yet this writes its noise word in
+// device memory and its last_stream (`mutable`): include/salp_vec.h says so.  Should this one-thread launch fail, the
+// rollout kernels are already enqueued: the call then returns the error with the envs stepped and the global step advanced
+// but the noise step where it was — the caller must set it (salp_policy_set_noise_step) before sampling on.
+static int advance_noise(const salp_policy_t* pol, int H, hipStream_t st) {
+  pol->last_stream = st;
+  hipLaunchKernelGGL(salp_policy_noise_kernel, dim3(1), dim3(1), 0, st, pol->block, (uint64_t)H, (uint64_t)0, 0);
+  HIP_TRY(hipGetLastError());
+  return SALP_OK;
+}
+
+// salp_vec_rollout_policy (sampled = false, logp_out = NULL) and salp_vec_rollout_policy_sampled
+static int rollout_policy_impl(salp_vec_t* h, const salp_policy_t* pol, int32_t H, float* obs, float* reward, uint8_t* terminated,
+                               uint8_t* truncated, float* act_out, float* logp_out, uint32_t flags, void* stream, bool sampled) {
   if (!h || !pol) return fail(SALP_ERR_INVALID, "handle/policy is NULL");
+  if (sampled && !pol->gaussian) return fail(SALP_ERR_INVALID, "sampling needs a Gaussian policy (salp_policy_create_gaussian)");
   if (pol->h != h || pol->device != h->device || pol->obs_dim != h->obs_dim || pol->act_dim != h->act_dim || pol->n != h->n)
     return fail(SALP_ERR_INVALID, "the policy belongs to another handle (or other dimensions)");
   if (h->kmax != 3) return fail(SALP_ERR_INVALID, "policies need a handle with max_observed_food == 3");
@@ -1736,40 +1845,59 @@ int salp_vec_rollout_policy(salp_vec_t* h, const salp_policy_t* pol, int32_t H, 
   io.stats = h->stats_enabled ? h->stats : nullptr;
   io.global_step = h->global_step;
   io.act = pol->block;
+  const int kind = sampled ? ACT_POLICY_SAMPLED : ACT_POLICY;
   if (flags & SALP_DEVICE_PTRS) {
     io.obs = obs; io.reward = reward; io.terminated = terminated; io.truncated = truncated; io.act_out = act_out;
-    const int rc = launch_rollout(h, io, H, st, false, true);
+    if (sampled) io.logp_out = logp_out;
+    const int rc = launch_rollout(h, io, H, st, false, kind);
     if (rc == SALP_OK) h->global_step += H;
+    if (rc == SALP_OK && sampled) return advance_noise(pol, H, st);
     return rc;
   }
   // host pointers: stage through device memory, synchronous
   const size_t HN = (size_t)H * (size_t)h->n;
   const size_t need = 4096 + align_up(HN * h->act_dim * sizeof(float), 256) + align_up(HN * h->obs_dim * sizeof(float), 256) +
-                      align_up(HN * sizeof(float), 256) + 2 * align_up(HN, 256);
+                      2 * align_up(HN * sizeof(float), 256) + 2 * align_up(HN, 256);
   int rc = ensure_stage(h, need);
   if (rc != SALP_OK) return rc;
   Bump b{(char*)h->stage, 0};
   float* d_aout = act_out ? b.take<float>(HN * h->act_dim) : nullptr;
+  float* d_logp = (sampled && logp_out) ? b.take<float>(HN) : nullptr;
   float* d_obs = b.take<float>(HN * h->obs_dim);
   float* d_rew = b.take<float>(HN);
   uint8_t* d_term = b.take<uint8_t>(HN);
   uint8_t* d_trunc = b.take<uint8_t>(HN);
   io.obs = d_obs; io.reward = d_rew; io.terminated = d_term; io.truncated = d_trunc; io.act_out = d_aout;
-  rc = launch_rollout(h, io, H, st, false, true);
+  if (sampled) io.logp_out = d_logp;
+  rc = launch_rollout(h, io, H, st, false, kind);
   if (rc != SALP_OK) return rc;
   h->global_step += H;
+  if (sampled) { rc = advance_noise(pol, H, st); if (rc != SALP_OK) return rc; }
   HIP_TRY(hipMemcpyAsync(obs, d_obs, HN * h->obs_dim * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(reward, d_rew, HN * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(terminated, d_term, HN, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(truncated, d_trunc, HN, hipMemcpyDeviceToHost, st));
   if (d_aout) HIP_TRY(hipMemcpyAsync(act_out, d_aout, HN * h->act_dim * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (d_logp) HIP_TRY(hipMemcpyAsync(logp_out, d_logp, HN * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return SALP_OK;
 }
 
-// salp_vec_evaluate_policy: the kSigSummary kernels.  Everything is checked before anything is launched.
-int salp_vec_evaluate_policy(salp_vec_t* h, const salp_policy_t* pol, int32_t H, void* rec, uint32_t flags, void* stream) {
+int salp_vec_rollout_policy(salp_vec_t* h, const salp_policy_t* pol, int32_t H, float* obs, float* reward,
+                            uint8_t* terminated, uint8_t* truncated, float* act_out, uint32_t flags, void* stream) {
+  return rollout_policy_impl(h, pol, H, obs, reward, terminated, truncated, act_out, nullptr, flags, stream, false);
+}
+
+int salp_vec_rollout_policy_sampled(salp_vec_t* h, const salp_policy_t* pol, int32_t H, float* obs, float* reward,
+                                    uint8_t* terminated, uint8_t* truncated, float* act_out, float* logp_out,
+                                    uint32_t flags, void* stream) {
+  return rollout_policy_impl(h, pol, H, obs, reward, terminated, truncated, act_out, logp_out, flags, stream, true);
+}
+
+// salp_vec_evaluate_policy (and _sampled): the kSigSummary kernels.  Everything is checked before anything is launched.
+static int evaluate_policy_impl(salp_vec_t* h, const salp_policy_t* pol, int32_t H, void* rec, uint32_t flags, void* stream, bool sampled) {
   if (!h || !pol) return fail(SALP_ERR_INVALID, "handle/policy is NULL");
+  if (sampled && !pol->gaussian) return fail(SALP_ERR_INVALID, "sampling needs a Gaussian policy (salp_policy_create_gaussian)");
   if (pol->h != h || pol->device != h->device || pol->obs_dim != h->obs_dim || pol->act_dim != h->act_dim || pol->n != h->n)
     return fail(SALP_ERR_INVALID, "the policy belongs to another handle (or other dimensions)");
   if (h->kmax != 3) return fail(SALP_ERR_INVALID, "policies need a handle with max_observed_food == 3");
@@ -1791,10 +1919,12 @@ int salp_vec_evaluate_policy(salp_vec_t* h, const salp_policy_t* pol, int32_t H,
   io.stats = h->stats_enabled ? h->stats : nullptr;
   io.global_step = h->global_step;
   io.act = pol->block;
+  const int kind = sampled ? ACT_POLICY_SAMPLED : ACT_POLICY;
   if (flags & SALP_DEVICE_PTRS) {
     io.obs = (float*)rec; io.final_obs = accumulate ? (float*)rec : nullptr;
-    const int rc = launch_rollout(h, io, H, st, false, true, true);
+    const int rc = launch_rollout(h, io, H, st, false, kind, true);
     if (rc == SALP_OK) h->global_step += H;
+    if (rc == SALP_OK && sampled) return advance_noise(pol, H, st);
     return rc;
   }
   // host pointers: stage through device memory, synchronous
@@ -1805,12 +1935,21 @@ int salp_vec_evaluate_policy(salp_vec_t* h, const salp_policy_t* pol, int32_t H,
   int32_t* d_rec = b.take<int32_t>((size_t)h->n * SALP_EVAL_WORDS);
   if (accumulate) HIP_TRY(hipMemcpyAsync(d_rec, rec, rec_b, hipMemcpyHostToDevice, st));
   io.obs = (float*)d_rec; io.final_obs = accumulate ? (float*)d_rec : nullptr;
-  rc = launch_rollout(h, io, H, st, false, true, true);
+  rc = launch_rollout(h, io, H, st, false, kind, true);
   if (rc != SALP_OK) return rc;
   h->global_step += H;
+  if (sampled) { rc = advance_noise(pol, H, st); if (rc != SALP_OK) return rc; }
   HIP_TRY(hipMemcpyAsync(rec, d_rec, rec_b, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return SALP_OK;
+}
+
+int salp_vec_evaluate_policy(salp_vec_t* h, const salp_policy_t* pol, int32_t H, void* rec, uint32_t flags, void* stream) {
+  return evaluate_policy_impl(h, pol, H, rec, flags, stream, false);
+}
+
+int salp_vec_evaluate_policy_sampled(salp_vec_t* h, const salp_policy_t* pol, int32_t H, void* rec, uint32_t flags, void* stream) {
+  return evaluate_policy_impl(h, pol, H, rec, flags, stream, true);
 }
 
 int salp_vec_get_state(salp_vec_t* h, double* f64, int32_t* i32, uint32_t flags, void* stream) {

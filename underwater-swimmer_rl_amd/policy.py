@@ -8,6 +8,10 @@ without hidden layers and with `out="clip"`, the scripted pursuit rule.  Needs n
 `pack()` is the public weight layout of the C ABI (torch's nn.Linear: per layer W[out][in] row-major, then b[out]; then
 scale, shift).  `reference(obs)` evaluates the float32 weights in float64; `error_bound(obs)` bounds how far a correct fp32
 evaluation in the library's fixed order may be from it.
+
+`GaussianPolicy` adds the log-std head of `sac.Actor` (salp_policy_create_gaussian): the kernel then SAMPLES the action,
+`tanh(mu + exp(log_std) z) * scale + shift`, from the policy's own Philox stream (`noise`) and returns its log-probability
+(include/salp_vec.h "Sampled actions"); `reference(obs, z)` / `error_bound(obs, z)` state and bound that computation.
 """
 from __future__ import annotations
 
@@ -192,6 +196,261 @@ class MLPPolicy:
         """float64 [..., N, act_dim]: |fp32 action - reference(obs)| of a correct evaluation stays below this."""
         g, back = self._grouped(obs)
         return back(self._forward(g, True)[1])
+
+
+# ---------------------------------------------------------------------- the sampling policy (salp_policy_create_gaussian)
+LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0       # sac.LOG_STD_MIN / MAX (stable-baselines3): the clamp of the log-std head
+NOISE_STREAM = 3                            # fourth Philox counter word of the policy noise (0 env draws, 1 / 2 device actions)
+# Accuracy of the device library's functions as the bounds below use them: |computed - exact| <= C * 2^-23 * |exact| on
+# the ranges the sampling arithmetic reaches (and an exact 0 where the exact value is 0).  Each C is TWICE the largest
+# error that the stand-alone probe profiles/micro/math_accuracy_probe.hip measured against float64 on an MI355X (the device
+# functions alone, dense grids, no kernel of the library involved; profiles/r07/ab_notes.md) — no ROCm accuracy table is
+# installed next to the compiler.  TANHF is the figure `MLPPolicy._forward` has used since the policy kernels exist.
+ULP_EXPF = 1.42     # measured 0.7054 on [-80, 2] (2^24 points), doubled
+ULP_LOGF = 2.70     # measured 1.3459 on every u1 = k 2^-24, k = 1 .. 2^24, doubled
+ULP_SQRTF = 1.0     # measured 0.5000 (correctly rounded) on every -2 logf(u1), doubled
+ULP_COSPIF = 1.46   # measured 0.7268 on every 2 u2 = k 2^-23, k = 0 .. 2^24 - 1, doubled
+ULP_LOG1PF = 1.05   # measured 0.5246 on [0, 1) (2^24 points) and 2^-e (1 + m 2^-12), e <= 126, doubled
+ULP_TANHF = 5.0
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+
+
+def philox4x32_10(counter, key) -> np.ndarray:
+    """Vectorised Philox4x32-10: counter [..., 4], key [..., 2] (broadcast against each other) -> uint32 [..., 4]."""
+    c = np.asarray(counter, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    k = np.asarray(key, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    shape = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], shape).copy() for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], shape).copy() for i in range(2))
+    mask, sh = np.uint64(0xFFFFFFFF), np.uint64(32)
+    for _ in range(10):
+        p0, p1 = np.uint64(_PHILOX_M0) * c0, np.uint64(_PHILOX_M1) * c2          # 32 x 32 -> 64 bits: no overflow in uint64
+        c0, c1, c2, c3 = (p1 >> sh) ^ c1 ^ k0, p1 & mask, (p0 >> sh) ^ c3 ^ k1, p0 & mask
+        k0, k1 = (k0 + np.uint64(_PHILOX_W0)) & mask, (k1 + np.uint64(_PHILOX_W1)) & mask
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def _key_words(key) -> Tuple[int, int]:
+    """The handle's key: the 64-bit seed (low word, high word), or the two words themselves."""
+    if isinstance(key, (tuple, list, np.ndarray)):
+        return int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF
+    return int(key) & 0xFFFFFFFF, (int(key) >> 32) & 0xFFFFFFFF
+
+
+def noise_words(key, env_index, n) -> np.ndarray:
+    """The policy-noise blocks, uint32 [..., 4]: Philox4x32-10(counter = (env_lo, env_hi, n mod 2^32, 3), key); `env_index`
+    (global) and `n` (noise step) broadcast against each other."""
+    env = np.asarray(env_index, dtype=np.uint64)
+    nn = np.asarray(n).astype(np.uint64) & np.uint64(0xFFFFFFFF)
+    env, nn = np.broadcast_arrays(env, nn)
+    ctr = np.stack([env & np.uint64(0xFFFFFFFF), env >> np.uint64(32), nn, np.full(env.shape, NOISE_STREAM, np.uint64)], axis=-1)
+    return philox4x32_10(ctr, np.array(_key_words(key), np.uint64))
+
+
+def normal_from_words(wa, wb) -> np.ndarray:
+    """float64 Box-Muller of the definition: u1 = ((wa >> 8) + 1) 2^-24 in (0, 1], u2 = (wb >> 8) 2^-24 in [0, 1),
+    z = sqrt(-2 log u1) cos(2 pi u2) (cos(pi x) evaluated with the argument reduced exactly, as cospi does)."""
+    u1 = ((np.asarray(wa, np.uint32) >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
+    k = (np.asarray(wb, np.uint32) >> np.uint32(8)).astype(np.int64)             # u2 = k 2^-24; cos(2 pi u2) by octant of k
+    q, r = k >> 22, (k & ((1 << 22) - 1)).astype(np.float64) * 2.0 ** -23          # 2 u2 = q / 2 + r, r in [0, 1/2)
+    cr, sr = np.cos(np.pi * r), np.sin(np.pi * r)
+    c = np.where(q == 0, cr, np.where(q == 1, -sr, np.where(q == 2, -cr, sr)))
+    return np.sqrt(-2.0 * np.log(u1)) * c
+
+
+class GaussianPolicy(MLPPolicy):
+    """P >= 1 tanh-Gaussian policies of one shape (`sac.Actor`): the `MLPPolicy` of the body and the MEAN head — `layers`,
+    `reference(obs)` without z, everything a deterministic run uses — plus the log-std head `log_std = (W [P, A, in], b [P, A])`
+    on the same last hidden layer."""
+    gaussian = True
+
+    def __init__(self, layers, log_std, scale, shift):
+        super().__init__(layers, scale, shift, "tanh")
+        W, b = log_std
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        if W.shape != self.layers[-1][0].shape or b.shape != self.layers[-1][1].shape:
+            raise ValueError(f"the log-std head must have the mean head's shape {self.layers[-1][0].shape}; got {W.shape}, {b.shape}")
+        self.log_std = (W, b)
+
+    # ------------------------------------------------------------------ constructors
+    @classmethod
+    def from_layers(cls, layers, log_std, scale=None, shift=None) -> "GaussianPolicy":
+        """One policy from [(W [out, in], b [out]), ...] (the last one the mean head) and log_std = (W [A, in], b [A])."""
+        m = MLPPolicy.from_layers(layers, scale, shift, "tanh")
+        return cls(m.layers, (np.asarray(log_std[0], dtype=np.float32)[None], np.asarray(log_std[1], dtype=np.float32)[None]),
+                   m.scale, m.shift)
+
+    @classmethod
+    def from_actor(cls, actor) -> "GaussianPolicy":
+        """A `sac.Actor` whose hidden sizes fit: body, `mu`, `log_std`, scale, shift."""
+        m = MLPPolicy.from_actor(actor)
+        ls = actor.log_std
+        return cls(m.layers, (ls.weight.detach().cpu().numpy()[None], ls.bias.detach().cpu().numpy()[None]), m.scale, m.shift)
+
+    @classmethod
+    def linear(cls, *a, **k):
+        raise TypeError("GaussianPolicy.from_layers builds a policy without hidden layers")
+
+    @classmethod
+    def stack(cls, policies: Sequence["GaussianPolicy"]) -> "GaussianPolicy":
+        m = MLPPolicy.stack([p.mean_policy() for p in policies])
+        return cls(m.layers, (np.concatenate([p.log_std[0] for p in policies]), np.concatenate([p.log_std[1] for p in policies])),
+                   m.scale, m.shift)
+
+    def mean_policy(self) -> MLPPolicy:
+        """The `MLPPolicy` of the same body and mean head: what salp_vec_rollout_policy runs for this policy."""
+        return MLPPolicy(self.layers, self.scale, self.shift, "tanh")
+
+    # ------------------------------------------------------------------ shape
+    @property
+    def words(self) -> int:
+        """float32 words of one policy in the public Gaussian layout (salp_policy_words_gaussian)."""
+        W = self.log_std[0]
+        return super().words + W.shape[1] * W.shape[2] + W.shape[1]
+
+    def pack(self) -> np.ndarray:
+        """The public layout, float32 [P, words]: hidden layers, W_mu, b_mu, W_ls, b_ls, scale, shift."""
+        P = self.n_policies
+        parts = []
+        for W, b in self.layers:
+            parts += [W.reshape(P, -1), b]
+        parts += [self.log_std[0].reshape(P, -1), self.log_std[1], self.scale, self.shift]
+        return np.ascontiguousarray(np.concatenate(parts, axis=1), dtype=np.float32)
+
+    # ------------------------------------------------------------------ noise
+    @staticmethod
+    def noise_words(key, env_index, n) -> np.ndarray:
+        return noise_words(key, env_index, n)
+
+    def noise(self, key, env_index, n) -> np.ndarray:
+        """float64 z [..., act_dim] of the definition (include/salp_vec.h "Randomness"): component j from words
+        (w[2j], w[2j+1]) of block(env, n).  `key`: the handle's seed; `env_index` (global) and `n` broadcast."""
+        w = noise_words(key, env_index, n)
+        return np.stack([normal_from_words(w[..., 2 * j], w[..., 2 * j + 1]) for j in range(self.act_dim)], axis=-1)
+
+    # ------------------------------------------------------------------ evaluation
+    def _sampled(self, x, z, with_bound: bool):
+        """x float64 [P, M, obs_dim], z float64 [P, M, A].  Returns (action, logp, e_action, e_logp): the float64 values of
+        the definition and (with_bound) how far a correct fp32 evaluation in the library's order may be from them.  The
+        running bound of `_forward` up to both heads (per layer gamma_{n+1} (sum |w| |x| + |b|), the incoming error
+        carried through |W|; the clamp is 1-Lipschitz, and exact where the head is beyond it by more than its bound); then
+          z:    logf, the exact doubling, sqrtf (which halves a relative error), cospif and one product: relative
+          sd:   the error of ls carried through exp — sd (e^{e_ls} - 1) — plus expf's own
+          u:    e_mu + e_sd (|z| + e_z) + sd e_z, one rounding of the fma
+          a:    tanh is 1-Lipschitz, tanhf's own error, the two roundings of scale / shift
+          logp: per component 0.5 e_z (2 |z| + e_z) + e_ls + 2 e_u (the squash term 2 (log 2 - u - softplus(-2u)) has a
+                derivative within [-2, 2]), plus the rounding of every operation and library call at its own magnitude.
+        Where a magnitude of a COMPUTED value is needed it is the exact one plus its bound.  No measured number but the
+        named ULP_* constants enters."""
+        e = np.zeros_like(x)
+        for W, b in self.layers[:-1]:
+            x, e = _affine(W, b, x, e, with_bound)
+            x = np.maximum(x, 0.0)
+        mu, e_mu = _affine(*self.layers[-1], x, e, with_bound)
+        lsr, e_ls = _affine(*self.log_std, x, e, with_bound)
+        ls = np.clip(lsr, LOG_STD_MIN, LOG_STD_MAX)
+        if with_bound:      # a head that is beyond a clamp by more than its own bound leaves the clamp's constant, exactly
+            e_ls = np.where((lsr + e_ls < LOG_STD_MIN) | (lsr - e_ls > LOG_STD_MAX), 0.0, e_ls)
+        sd = np.exp(ls)
+        u = mu + sd * z
+        t = np.tanh(u)
+        sc, sh = self.scale.astype(np.float64)[:, None, :], self.shift.astype(np.float64)[:, None, :]
+        a = t * sc + sh
+        m2 = -2.0 * u
+        E = np.exp(-np.abs(m2))
+        L = np.log1p(E)
+        sp = np.maximum(m2, 0.0) + L
+        c = (np.log(2.0) - u) - sp
+        K = 0.5 * np.log(2.0 * np.pi)
+        g1 = -0.5 * z * z
+        g2 = g1 - ls
+        g3 = g2 - K
+        g4 = g3 - 2.0 * c
+        logp = g4.sum(axis=-1)
+        if not with_bound:
+            return a, logp, None, None
+        ulp = 2.0 * U
+        # z = sqrtf(-2 logf(u1)) * cospif(2 u2): relative errors (1 + r_log)^(1/2) (1 + r_sqrt) (1 + r_cos) (1 + u) - 1
+        r_log, r_sqrt, r_cos = ULP_LOGF * ulp, ULP_SQRTF * ulp, ULP_COSPIF * ulp
+        r_z = (1.0 + 0.5 * r_log * (1.0 + r_log)) * (1.0 + r_sqrt) * (1.0 + r_cos) * (1.0 + U) - 1.0
+        az = np.abs(z)
+        e_z = r_z * az
+        d_sd = sd * np.expm1(e_ls)
+        e_sd = d_sd + ULP_EXPF * ulp * (sd + d_sd)
+        e_u = e_mu + e_sd * (az + e_z) + sd * e_z
+        e_u = e_u + U * (np.abs(u) + e_u)
+        # action
+        e_t = e_u + ULP_TANHF * ulp * (np.abs(t) + e_u)
+        prod = (np.abs(t) + e_t) * np.abs(sc)
+        e_prod = np.abs(sc) * e_t + U * prod
+        e_a = e_prod + U * (np.abs(a) + e_prod)
+        # log-probability: the inputs' errors through the exact expression, then every operation's own rounding
+        e_in = 0.5 * e_z * (2.0 * az + e_z) + e_ls + 2.0 * e_u
+        El = np.minimum(1.0, E * np.exp(2.0 * e_u))                       # the largest exp(-|m2|) within the input's error
+        Ll = np.log1p(El)
+        spl = np.abs(m2) + 2.0 * e_u + Ll
+        # expf, carried through log1p (1-Lipschitz); arguments below the probed -80 give results under 2^-115: covered absolutely
+        r_E = ULP_EXPF * ulp * El + 2.0 ** -100
+        r_L = ULP_LOG1PF * ulp * (Ll + r_E)
+        r_sp = r_E + r_L + U * (spl + r_E + r_L)
+        r_d = U * np.log(2.0) + U * (np.log(2.0) + np.abs(u) + e_u)        # the constant's rounding, the subtraction's
+        mag_c = np.abs(c) + 2.0 * e_u + r_sp + r_d
+        r_c = r_sp + r_d + U * mag_c
+        r_g1 = 0.5 * U * (az + e_z) ** 2                                   # z * z (the halving is exact)
+        mag = np.abs(g1) + 0.5 * e_z * (2.0 * az + e_z) + r_g1
+        mag2 = mag + np.abs(ls) + e_ls
+        r_g2 = U * mag2
+        mag3 = mag2 + r_g2 + K * (1.0 + U)
+        r_g3 = U * K + U * mag3
+        mag4 = mag3 + r_g3 + 2.0 * mag_c
+        r_g4 = U * mag4
+        e_g = e_in + r_g1 + r_g2 + r_g3 + 2.0 * r_c + r_g4
+        e_logp = e_g.sum(axis=-1)
+        if self.act_dim > 1:                                               # the sum of the components: one rounding more each
+            e_logp = e_logp + (self.act_dim - 1) * U * (np.abs(g4).sum(axis=-1) + e_logp)
+        return a, logp, e_a, e_logp
+
+    def _grouped_z(self, obs, z):
+        g, back = self._grouped(obs)
+        zz = np.asarray(z, dtype=np.float64)
+        x = np.asarray(obs)
+        if zz.shape != x.shape[:-1] + (self.act_dim,):
+            raise ValueError(f"z must have shape {x.shape[:-1] + (self.act_dim,)}, got {zz.shape}")
+        lead, N, P = x.shape[:-2], x.shape[-2], self.n_policies
+        gz = np.moveaxis(zz.reshape(-1, P, N // P, self.act_dim), 1, 0).reshape(P, -1, self.act_dim)
+
+        def back1(v):                                                       # [P, L * G] -> [..., N]
+            return np.moveaxis(v.reshape(P, -1, N // P), 0, 1).reshape(lead + (N,))
+        return g, gz, back, back1
+
+    def reference(self, obs, z=None):
+        """Without z: the mean policy's float64 actions (what a deterministic run takes).  With z float64 [..., N, act_dim]:
+        (action [..., N, act_dim], logp [..., N]) of the sampling definition in float64 under the float32 weights."""
+        if z is None:
+            return super().reference(obs)
+        g, gz, back, back1 = self._grouped_z(obs, z)
+        a, lp, _, _ = self._sampled(g, gz, False)
+        return back(a), back1(lp)
+
+    def error_bound(self, obs, z=None):
+        """Without z: the mean policy's bound.  With z: (e_action [..., N, act_dim], e_logp [..., N])."""
+        if z is None:
+            return super().error_bound(obs)
+        g, gz, back, back1 = self._grouped_z(obs, z)
+        _, _, ea, el = self._sampled(g, gz, True)
+        return back(ea), back1(el)
+
+
+def _affine(W, b, x, e, with_bound: bool):
+    """y = W x + b in float64 and the running fp32 bound of `MLPPolicy._forward` for one layer."""
+    W64, b64 = W.astype(np.float64), b.astype(np.float64)
+    y = np.einsum("poi,pmi->pmo", W64, x) + b64[:, None, :]
+    if with_bound:
+        aW = np.abs(W64)
+        mag = np.einsum("poi,pmi->pmo", aW, np.abs(x) + e) + np.abs(b64)[:, None, :]
+        e = _gamma(W.shape[2] + 1) * mag + np.einsum("poi,pmi->pmo", aW, e)
+    return y, e
 
 
 # ---------------------------------------------------------------------- evaluation records (salp_vec_evaluate_policy)

@@ -417,6 +417,38 @@ def train_sac(env, agent: SAC, total_vector_steps: int, buffer: Optional[DeviceR
             **{k: float(v) for k, v in last.items()}}
 
 
+IN_KERNEL_HIDDEN_MAX = 64      # widest hidden layer of an actor that runs inside the rollout kernel (include/salp_vec.h "Policy")
+
+
+@torch.no_grad()
+def collect_in_kernel(env, agent: SAC, buffer: DeviceReplayBuffer, horizon: int, handle=None):
+    """`horizon` vector steps of experience in ONE launch: the agent's actor is packed as a `policy.GaussianPolicy`, the
+    rollout kernel samples its tanh-Gaussian actions itself (`env.rollout_policy(..., sample=True)`), and the H x N
+    transitions go to `buffer` in step order: `obs` = the row each action saw (the current observation, then obs[t - 1]),
+    `next_obs` = obs[t].  Transitions whose step was TRUNCATED are left out — the policy kernels return no terminal
+    observation, and after the same-step autoreset obs[t] is the next episode's first row; terminated ones are kept (the
+    target ignores their next_obs).  Returns the policy handle: pass it back as `handle` and the next call only uploads the
+    actor's new weights (`handle.update`)."""
+    from .policy import GaussianPolicy
+    wide = [h for h in agent.cfg.hidden_sizes if h > IN_KERNEL_HIDDEN_MAX]
+    if wide or len(agent.cfg.hidden_sizes) > 2:
+        raise ValueError(f"collect_in_kernel: the actor's hidden sizes {tuple(agent.cfg.hidden_sizes)} do not fit the rollout kernel "
+                         f"(at most 2 hidden layers of at most {IN_KERNEL_HIDDEN_MAX} units, multiples of 16)")
+    pol = GaussianPolicy.from_actor(agent.actor)
+    if handle is None:
+        handle = env.make_policy(pol)
+    else:
+        handle.update(pol.pack(), 0, env._stream)
+    H, n = int(horizon), env.num_envs
+    first = env.observe().clone()
+    out = env.rollout_policy(handle, H, sample=True)
+    seen = torch.cat([first[None], out["obs"][:-1]])
+    keep = (out["truncated"] == 0).reshape(-1)
+    flat = lambda t: t.reshape((H * n,) + tuple(t.shape[2:]))[keep]
+    buffer.add(flat(seen), flat(out["actions"]), flat(out["reward"]), flat(out["obs"]), flat(out["terminated"]))
+    return handle
+
+
 def train_sac_graphed(env, agent: SAC, total_vector_steps: int, buffer: Optional[DeviceReplayBuffer] = None,
                       reward_fn=None, stop_at_first_food: bool = False, poll_every: int = 8,
                       warmup_iters: int = 3, force_segments: bool = False) -> Dict[str, float]:

@@ -320,19 +320,21 @@ class SalpVectorEnv:
                     actions=a if a is not None else aout)
 
     def make_policy(self, policy, weights=None):
-        """An in-kernel policy of this env (`policy.MLPPolicy`, one policy or a population): a `_capi.PolicyHandle` for
-        `rollout_policy`.  `handle.update(w, flags, stream)` takes new weights of the same shape in the public layout
+        """An in-kernel policy of this env (`policy.MLPPolicy` or `policy.GaussianPolicy`, one policy or a population): a
+        `_capi.PolicyHandle` for `rollout_policy` (a Gaussian one also for `sample=True`; it carries `noise_step`).  `handle.update(w, flags, stream)` takes new weights of the same shape in the public layout
         (`MLPPolicy.pack()`); with a device tensor and SALP_DEVICE_PTRS it is stream-ordered and allocates nothing."""
         if (policy.obs_dim, policy.act_dim) != (self.obs_dim, self.act_dim):
             raise ValueError(f"the policy maps {policy.obs_dim} -> {policy.act_dim}, this env {self.obs_dim} -> {self.act_dim}")
         policy.check_envs(self.num_envs)
         return self._lib.policy_create(policy, weights, 0 if weights is None else self._flags, self._stream)
 
-    def rollout_policy(self, policy, horizon: int, want_actions: bool = True, out: Optional[dict] = None) -> dict:
+    def rollout_policy(self, policy, horizon: int, want_actions: bool = True, out: Optional[dict] = None, sample: bool = False) -> dict:
         """`horizon` closed-loop steps in one kernel launch: every action is `policy` applied to the observation before it
         (the first one to the current observation).  `policy`: a handle of `make_policy`, or an `MLPPolicy` (a handle is
         then made and kept for the next call with the same object).  Returns the dict of `rollout` with `actions`
-        ([H, N, act_dim], None without `want_actions`)."""
+        ([H, N, act_dim], None without `want_actions`).  `sample=True` (a `GaussianPolicy`): the actions are sampled in
+        the kernel (tanh-Gaussian, the policy's noise stream) and the dict gains `logp` [H, N]; with `sample=False` a
+        Gaussian policy runs its mean."""
         if not isinstance(policy, _capi.PolicyHandle):
             cache = self.__dict__.setdefault("_policy_cache", {})
             if id(policy) not in cache:
@@ -347,17 +349,22 @@ class SalpVectorEnv:
         term = out.get("terminated") if "terminated" in out else self._buf("r_term", (H, n), np.uint8)
         trunc = out.get("truncated") if "truncated" in out else self._buf("r_trunc", (H, n), np.uint8)
         aout = (out.get("actions") if "actions" in out else self._buf("r_act", (H, n, self.act_dim), np.float32)) if want_actions else None
+        if sample:
+            logp = out.get("logp") if "logp" in out else self._buf("r_logp", (H, n), np.float32)
+            self._lib.rollout_policy_sampled(policy, H, obs, rew, term, trunc, aout, logp, self._flags, self._stream)
+            return dict(obs=obs, reward=rew, terminated=term, truncated=trunc, final_obs=None, actions=aout, logp=logp)
         self._lib.rollout_policy(policy, H, obs, rew, term, trunc, aout, self._flags, self._stream)
         return dict(obs=obs, reward=rew, terminated=term, truncated=trunc, final_obs=None, actions=aout)
 
-    def evaluate_policy(self, policy, horizon: int, out=None, accumulate: bool = False) -> dict:
+    def evaluate_policy(self, policy, horizon: int, out=None, accumulate: bool = False, sample: bool = False) -> dict:
         """`horizon` closed-loop steps of `rollout_policy` in one kernel launch with NO per-step output: one summary record
         per env (32 B) instead of [H, N] observations, rewards and flags.  Returns typed views of one int32 [N, 8] block
         (`policy.evaluation_views`): `record`, `return_sum` and `first_return` (float64 [N]: the float32 step rewards added
         in step order — over the call, and up to the env's first episode end), `first_length`, `first_end` (0 not finished,
         1 terminated, 2 truncated), `episodes`, `food` (int32 [N]).  `out`: a block (or a dict returned earlier) to write
         into; `accumulate=True` continues the records in `out` (required then), so that a run cut into several calls gives
-        the bits of one call.  A policy's score: `return_sum.view(P, E).mean(1)`."""
+        the bits of one call.  A policy's score: `return_sum.view(P, E).mean(1)`.  `sample=True` (a `GaussianPolicy`):
+        the run takes the policy's sampled actions, as `rollout_policy(..., sample=True)` would."""
         from .policy import EVAL_WORDS, evaluation_views
         if not isinstance(policy, _capi.PolicyHandle):
             cache = self.__dict__.setdefault("_policy_cache", {})
@@ -381,7 +388,8 @@ class SalpVectorEnv:
         if tuple(rec.shape) != (n, EVAL_WORDS):
             raise ValueError(f"out must be an int32 [{n}, {EVAL_WORDS}] block")
         views = evaluation_views(rec)       # checks dtype and contiguity
-        self._lib.evaluate_policy(policy, H, rec, self._flags | (_capi.EVAL_ACCUMULATE if accumulate else 0), self._stream)
+        call = self._lib.evaluate_policy_sampled if sample else self._lib.evaluate_policy
+        call(policy, H, rec, self._flags | (_capi.EVAL_ACCUMULATE if accumulate else 0), self._stream)
         return views
 
     def observe(self):
