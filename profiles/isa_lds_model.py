@@ -27,7 +27,7 @@ def model(f):
     w = sum(cycles(wr_groups(), lambda l, q=q: f(l, q), 32) for q in range(Q))
     rd = sum(cycles(rd_groups(), lambda l, j=j: f((j * 64 + l) // Q, (j * 64 + l) % Q), 64) for j in range(Q))
     return w, rd
-# Packed-record tile (salp_vec.hip, PACKED): rows of QP = 7 float4 at an unpadded 112-B pitch, no swizzle.  7 is odd, so
+# Packed-record tile (salp_rollout_kernel.h, PACKED): rows of QP = 7 float4 at an unpadded 112-B pitch, no swizzle.  7 is odd, so
 # eight consecutive rows start in eight different 16-B bank groups; the flush reads float4 j*64 + lane of a linear tile.
 QP = 7
 def PACKED(r, c): return r * 16 * QP + 16 * c

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Registers / LDS / scratch of every salp_rollout_kernel instantiation of a built libsalp_hip.so, from the code object's
-own metadata (no GPU needed): the gfx950 code object is taken out of the library's fat binary (llvm-objcopy,
-clang-offload-bundler) and its AMDGPU metadata note read with llvm-readelf.  One line per kernel, sorted, so that two
+own metadata (no GPU needed): the gfx950 code objects are taken out of the library's fat binary (llvm-objcopy,
+clang-offload-bundler) and their AMDGPU metadata notes read with llvm-readelf.  One line per kernel, sorted, so that two
 libraries are compared with `diff`.  usage:
     python profiles/kernel_metadata.py LIB.so [--sig N] [--act N]       (filters on the SIG / ACT template arguments)
 waves_per_simd = min(8, 512 / registers allocated in granules of 8, 160 KiB / LDS per workgroup of four wavefronts)."""
@@ -10,13 +10,31 @@ import os, re, subprocess, sys, tempfile
 LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
 
 
+MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+
+
 def kernels(lib):
+    """The .hip_fatbin section holds one bundle per translation unit (salp_vec.hip, salp_robot.hip, every rollout kernel
+    unit), each starting with MAGIC: the gfx950 code object of every one of them is read."""
+    out = []
     with tempfile.TemporaryDirectory() as d:
         fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "gfx950.co")
         subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", lib, os.path.join(d, "copy.so")], check=True)
-        subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                        f"--input={fat}", f"--output={co}"], check=True)
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
+        with open(fat, "rb") as f:
+            data = f.read()
+        starts = [m.start() for m in re.finditer(re.escape(MAGIC), data)]
+        for a, b in zip(starts, starts[1:] + [len(data)]):
+            with open(fat, "wb") as f:
+                f.write(data[a:b])
+            subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                            f"--input={fat}", f"--output={co}"], check=True)
+            notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
+            if "amdhsa.kernels:" in notes:
+                out += code_object_kernels(notes)
+    return sorted(out)
+
+
+def code_object_kernels(notes):
     md = notes[notes.index("amdhsa.kernels:"):]
     out = []
     for blk in md.split("  - .agpr_count:")[1:]:
@@ -31,7 +49,7 @@ def kernels(lib):
         waves = min(8, 512 // alloc, (160 * 1024) // lds if lds else 8)
         out.append((tuple(int(x) for x in t.groups()),
                     f"vgpr={regs} agpr={g('agpr_count')} sgpr={g('sgpr_count')} lds={lds} scratch={g('private_segment_fixed_size')} waves_per_simd={waves}"))
-    return sorted(out)
+    return out
 
 
 def main():

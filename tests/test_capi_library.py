@@ -117,6 +117,86 @@ def _build_module():
     return b
 
 
+ROLLOUT_K3_UNITS = {f"salp_rollout_f{slots}_{consts}.hip" for slots in (1, 4, 8, 12, 16) for consts in ("std", "rt")}
+
+
+def test_build_compiles_every_hip_source():
+    """csrc/build.py compiles what is there: its source list is the csrc/*.hip glob, the rollout kernel units among them."""
+    import glob
+    b = _build_module()
+    csrc = os.path.join(ROOT, "underwater-swimmer_rl_amd", "csrc")
+    assert sorted(os.path.realpath(s) for s in b.sources()) == sorted(os.path.realpath(s) for s in glob.glob(os.path.join(csrc, "*.hip")))
+    assert {os.path.basename(s) for s in b.sources()} == {"salp_vec.hip", "salp_robot.hip", "salp_rollout_generic.hip"} | ROLLOUT_K3_UNITS
+
+
+def test_rollout_units_are_compiled_without_machine_licm():
+    """-mllvm -disable-machine-licm (csrc/build.py on why) goes to every rollout kernel unit and to salp_vec.hip, not to
+    salp_robot.hip; and never more than 16 compilers run at once."""
+    b = _build_module()
+    flags = {os.path.basename(s): f for s, f in b.SRC_FLAGS.items()}
+    assert set(flags) == {os.path.basename(s) for s in b.sources()}
+    for name, f in flags.items():
+        assert (" ".join(f) == "-mllvm -disable-machine-licm") == (name != "salp_robot.hip"), (name, f)
+    assert sum(n.startswith("salp_rollout_") for n in flags) == 11
+    old = os.environ.get("MAX_JOBS")
+    try:
+        for given, want in (("3", 3), ("64", 16), ("0", 1)):
+            os.environ["MAX_JOBS"] = given
+            assert b.max_jobs() == want
+        del os.environ["MAX_JOBS"]
+        assert 1 <= b.max_jobs() <= 16
+    finally:
+        if old is not None:
+            os.environ["MAX_JOBS"] = old
+
+
+STAND_IN_COMPILER = """#!/bin/sh
+# stands for hipcc: fails at once for sources whose path contains $STAND_IN_FAIL, else writes the object and stays
+echo "$$" >> "$STAND_IN_PIDS"
+while [ $# -gt 1 ]; do [ "$1" = "-o" ] && obj=$2; shift; done
+case "$1" in *"$STAND_IN_FAIL"*) exit 1;; esac
+: > "$obj"
+sleep 600 &
+echo "$!" >> "$STAND_IN_PIDS"
+wait
+"""
+
+
+def _alive(pid):
+    try:
+        with open(f"/proc/{pid}/stat") as f:
+            return f.read().rsplit(")", 1)[1].split()[0] != "Z"
+    except OSError:
+        return False
+
+
+@pytest.mark.parametrize("fail, started", [("salp_robot.hip", 8), (".hip", 8)])
+def test_a_failed_compile_raises_and_leaves_nothing_behind(tmp_path, monkeypatch, fail, started):
+    """One compiler fails while seven others run (salp_robot.hip is the first source), or all eight fail in the same
+    instant (an error in the shared header): build() raises the compiler's CalledProcessError, starts no further
+    compiler, leaves no compiler or child of one running and no object file."""
+    import glob
+    import subprocess
+    import time
+    cc, pids = tmp_path / "hipcc", tmp_path / "pids"
+    cc.write_text(STAND_IN_COMPILER)
+    cc.chmod(0o755)
+    for k, v in (("HIPCC", str(cc)), ("MAX_JOBS", "8"), ("STAND_IN_FAIL", fail), ("STAND_IN_PIDS", str(pids))):
+        monkeypatch.setenv(k, v)
+    b = _build_module()
+    out = str(tmp_path / "lib.so")
+    with pytest.raises(subprocess.CalledProcessError) as e:
+        b.build(force=True, out=out)
+    assert e.value.returncode == 1 and e.value.cmd[0] == str(cc)
+    assert glob.glob(str(tmp_path / "*.o")) == [] and not os.path.exists(out) and not os.path.exists(out + ".hash")
+    seen = [int(x) for x in pids.read_text().split()]
+    assert len(seen) == started + (7 if fail == "salp_robot.hip" else 0)      # the stand-ins and the sleeping children
+    deadline = time.monotonic() + 5.0          # a signalled child may take a moment to go
+    while any(_alive(p) for p in seen) and time.monotonic() < deadline:
+        time.sleep(0.01)
+    assert [p for p in seen if _alive(p)] == []
+
+
 def test_build_dependencies_cover_every_source_file(lib):
     """The staleness check of csrc/build.py: every header / source the library is compiled from is a dependency (globbed),
     and an edit to any ONE of them — content, not file time — makes the built library stale.  (Round 2 shipped a
@@ -130,7 +210,8 @@ def test_build_dependencies_cover_every_source_file(lib):
     want = glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(ROOT, "include", "*.h"))
     assert sorted(os.path.realpath(d) for d in deps) == sorted(os.path.realpath(w) for w in want)
     names = {os.path.basename(d) for d in deps}
-    assert {"salp_vec.hip", "salp_robot.hip", "salp_device.h", "salp_food_lds.h", "salp_food_reg.h", "salp_vec.h", "salp_robot.h"} <= names
+    assert {"salp_vec.hip", "salp_robot.hip", "salp_device.h", "salp_food_lds.h", "salp_food_reg.h", "salp_vec.h", "salp_robot.h",
+            "salp_rollout_kernel.h", "salp_rollout_generic.hip"} | ROLLOUT_K3_UNITS <= names
     assert b.is_current()                       # the fixture built it: the stored hash matches the tree
     # touch every dependency in turn (in a scratch copy of the tree) and see the library go stale
     with tempfile.TemporaryDirectory() as tmp:

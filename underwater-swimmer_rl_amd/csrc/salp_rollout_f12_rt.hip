@@ -1,0 +1,4 @@
+// The K = 3 rollout kernels with 12 food slots and run-time constants (salp_rollout_kernel.h).
+#include "salp_rollout_kernel.h"
+
+RolloutPick salp_rollout_f12_rt(bool ragged, bool forced, int sig, int act) { return pick_k3<12, false>(ragged, forced, sig, act); }
