@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "salp_fp64_math.h"   // sincos_small
+
 namespace salp {
 
 // ---- in-kernel phase stamps (experiment build -DSALP_EXP_STAMPS, profiles/stamp_profile.py) ---------------------
@@ -273,37 +275,8 @@ __device__ __forceinline__ void draw_xy(EnvCore& e, const DevParams& P, uint64_t
 }
 
 // ------------------------------------------------------------------ fp64 trigonometry
-// sin and cos of |x| <= ~6 (thrust angles are bounded by pi + pi/3 + pi/2): Cody-Waite reduction by
-// pi/2 in two pieces (k <= 4, so k*PIO2_1 is exact) and the fdlibm kernel polynomials on
-// [-pi/4, pi/4].  <= 1 ulp-class accuracy; explicit fma() is allowed here because these values
-// have no bit-exact counterpart on the CPU anyway (glibc's sin/cos are a different algorithm).
-__device__ __forceinline__ void sincos_small(double x, double& s, double& c) {
-  const double fn = __builtin_rint(x * 6.36619772367581382433e-01);
-  double r = fma(-fn, 1.57079632673412561417e+00, x);
-  r = fma(-fn, 6.07710050650619224932e-11, r);
-  const double z = r * r;
-  // kernel sin
-  double ps = fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
-  ps = fma(z, ps, 2.75573137070700676789e-06);
-  ps = fma(z, ps, -1.98412698298579493134e-04);
-  ps = fma(z, ps, 8.33333333332248946124e-03);
-  const double v = z * r;
-  const double sr = fma(v, fma(z, ps, -1.66666666666666324348e-01), r);
-  // kernel cos
-  double pc = fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
-  pc = fma(z, pc, -2.75573143513906633035e-07);
-  pc = fma(z, pc, 2.48015872894767294178e-05);
-  pc = fma(z, pc, -1.38888888888741095749e-03);
-  pc = fma(z, pc, 4.16666666666666019037e-02);
-  const double hz = 0.5 * z;
-  const double w = 1.0 - hz;
-  const double cr = w + (((1.0 - w) - hz) + z * (z * pc));
-  const int q = (int)fn & 3;
-  const double s0 = (q & 1) ? cr : sr;
-  const double c0 = (q & 1) ? sr : cr;
-  s = (q & 2) ? -s0 : s0;
-  c = ((q + 1) & 2) ? -c0 : c0;
-}
+// sincos_small (Cody-Waite reduction by pi/2, fdlibm kernel polynomials) lives in salp_fp64_math.h with the other
+// hand-written fp64 routines that have a host twin and an error bound of their own under test.
 
 // sin(x) for |x| <= pi/3 (the nozzle angle): odd Taylor polynomial to x^21, error < 2e-22.
 __device__ __forceinline__ double sin_nozzle(double x) {

@@ -27,6 +27,7 @@
 
 #include "../../include/salp_robot.h"
 #include "salp_device.h"   // philox4x32_10, u53
+#include "salp_fp64_math.h"   // sincos_small, sincos_euler, advance_euler_sincos, rcp_nr, sqrt_nr
 
 using namespace salp;
 
@@ -58,58 +59,7 @@ struct Rb {   // one robot in registers
 
 __device__ __forceinline__ double clipd(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
-// sin/cos of an Euler angle.  The angles are unbounded (yaw winds up).  sincos_small (salp_device.h)
-// reduces by pi/2 with fused multiply-adds against a 33 + 53 bit split of pi/2 and keeps the quadrant in
-// an int, good to |x| ~ 1e9; past 1e8 rad (never seen; wave-uniform test) the angle is first folded
-// into [-pi, pi] against a double-double 2*pi, which holds to < 1e-16 rad up to |x| ~ 1e15.
-__device__ __forceinline__ void sincos_euler(double x, double& s, double& c) {
-  if (__any(fabs(x) > 1.0e8)) {
-    const double k = __builtin_rint(x * 0.15915494309189535);
-    x = fma(-k, 2.4492935982947064e-16, fma(-k, 6.283185307179586, x));
-  }
-  sincos_small(x, s, c);
-}
 __device__ __forceinline__ double sq(double x) { return x * x; }
-
-// (s, c) <- sin / cos of (angle + d) from sin / cos of the angle, |d| <= 0.25 rad: Taylor polynomials of sin d and
-// cos d (truncation < 1e-16) and the angle-addition formulas; ~16 operations instead of a full sincos.
-__device__ __forceinline__ void rotate_sincos(double& s, double& c, double d) {
-  const double z = d * d;
-  double ps = fma(z, 2.7557319223985893e-06, -1.9841269841269841e-04);    // 1/9!, -1/7!
-  ps = fma(z, ps, 8.3333333333333332e-03);
-  ps = fma(z, ps, -1.6666666666666666e-01);
-  const double sd = fma(d * z, ps, d);
-  double pc = fma(z, -2.7557319223985888e-07, 2.4801587301587302e-05);    // -1/10!, 1/8!
-  pc = fma(z, pc, -1.3888888888888889e-03);
-  pc = fma(z, pc, 4.1666666666666664e-02);
-  pc = fma(z, pc, -0.5);
-  const double cd = fma(z, pc, 1.0);
-  const double ns = fma(s, cd, c * sd), nc = fma(c, cd, -(s * sd));
-  s = ns; c = nc;
-}
-
-// 1/x for a normal, finite x: v_rcp_f64 and two Newton steps (<= 1 ulp; no range scaling / fix-up pass)
-__device__ __forceinline__ double rcp_nr(double x) {
-  double y = __builtin_amdgcn_rcp(x);
-  double e = fma(-x, y, 1.0);
-  y = fma(y, e, y);
-  e = fma(-x, y, 1.0);
-  return fma(y, e, y);
-}
-// sqrt(x) for x = 0 or x well inside the normal range: v_rsq_f64, one coupled Newton step and a final
-// residual correction (<= 1 ulp); tiny arguments take the library routine
-__device__ __forceinline__ double sqrt_nr(double x) {
-  if (__any(x < 1.0e-200 && x != 0.0)) return sqrt(x);
-  const double y = __builtin_amdgcn_rsq(x);
-  double g = x * y, h = 0.5 * y;
-  const double rr = fma(-h, g, 0.5);
-  g = fma(g, rr, g); h = fma(h, rr, h);
-  const double rr2 = fma(-h, g, 0.5);
-  g = fma(g, rr2, g); h = fma(h, rr2, h);
-  const double d = fma(-g, g, x);
-  g = fma(d, h, g);
-  return x == 0.0 ? 0.0 : g;
-}
 
 __device__ __forceinline__ void load_robot(Rb& r, const RobotState& S, const RobotParams& P, int64_t i) {
   const int64_t p = P.pitch;
@@ -402,6 +352,40 @@ void salp_robot_trajectory_kernel(RobotParams P0, RobotTrajectory J) {
   if (m) {
     const double c = (double)J.cycles;
     m[0] = m[0] / c; m[1] = m[1] / c; m[2] = m[2] / c; m[4] = m[4] / c;
+  }
+}
+
+// ---- test support: the fp64 primitives on their own (salp_robot_math_probe, declared in salp_fp64_math.h) ----------
+// Element i on thread i, so wavefront w holds the elements [64 w, 64 w + 64); `function` is uniform, so every vote
+// inside is taken over the whole wavefront (over its lanes below n in the last one).
+__global__ __launch_bounds__(kRBlock) void salp_robot_math_probe_kernel(int function, const double* in, double* out, int64_t n,
+                                                                        int32_t steps) {
+  const int64_t i = (int64_t)blockIdx.x * kRBlock + threadIdx.x;
+  if (i >= n) return;
+  switch (function) {
+    case SALP_MATH_SINCOS_SMALL: { double s, c; sincos_small(in[i], s, c); out[i] = s; out[n + i] = c; break; }
+    case SALP_MATH_SINCOS_EULER: { double s, c; sincos_euler(in[i], s, c); out[i] = s; out[n + i] = c; break; }
+    case SALP_MATH_ROTATE: {
+      double s = in[i], c = in[n + i];
+      rotate_sincos(s, c, in[2 * n + i]);
+      out[i] = s; out[n + i] = c;
+      break;
+    }
+    case SALP_MATH_CHAIN: {
+      double e = in[i], s, c, s1 = 0.0, c1 = 1.0, s2 = 0.0, c2 = 1.0;
+      sincos_euler(e, s, c);
+#pragma unroll 1
+      for (int32_t k = 0; k < steps; ++k) {
+        const double d = in[(int64_t)(1 + k) * n + i];
+        e += d;
+        advance_euler_sincos(e, 0.0, 0.0, d, 0.0, 0.0, s, c, s1, c1, s2, c2);
+      }
+      out[i] = s; out[n + i] = c; out[2 * n + i] = e;
+      break;
+    }
+    case SALP_MATH_RCP_NR: out[i] = rcp_nr(in[i]); break;
+    case SALP_MATH_SQRT_NR: out[i] = sqrt_nr(in[i]); break;
+    default: break;
   }
 }
 
@@ -780,6 +764,42 @@ int salp_robot_vec_get_state(salp_robot_vec_t* h, double* state, uint32_t flags,
                             (size_t)h->n * sizeof(double), SALP_R_COUNT,
                             (flags & 1u) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
   if (!(flags & 1u)) RHIP_TRY(hipStreamSynchronize(st));
+  return 0;
+}
+
+// Test support (salp_fp64_math.h): one of the fp64 primitives over host arrays, staged like the other host-pointer calls.
+int salp_robot_math_probe(int device_id, int function, const double* in, double* out, int64_t n, int32_t steps) {
+  if (!in || !out) return rfail(-1, "in / out is NULL");
+  if (n < 1 || n > ((int64_t)1 << 24)) return rfail(-1, "n must be in [1, 2^24]");
+  size_t rows_in = 1, rows_out = 2;
+  switch (function) {
+    case SALP_MATH_SINCOS_SMALL: case SALP_MATH_SINCOS_EULER: break;
+    case SALP_MATH_ROTATE: rows_in = 3; break;
+    case SALP_MATH_CHAIN:
+      if (steps < 0 || steps > 65536) return rfail(-1, "steps must be in [0, 65536]");
+      rows_in = 1 + (size_t)steps; rows_out = 3;
+      break;
+    case SALP_MATH_RCP_NR: case SALP_MATH_SQRT_NR: rows_out = 1; break;
+    default: return rfail(-1, "unknown function code");
+  }
+  const size_t ib = rows_in * (size_t)n * sizeof(double), ob = rows_out * (size_t)n * sizeof(double);
+  if (ib > ((size_t)1 << 31)) return rfail(-1, "input larger than 2 GiB");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return rfail(-2, "no HIP device visible (this library has no CPU fallback)");
+  if (device_id < 0 || device_id >= ndev) return rfail(-2, "device_id out of range");
+  DeviceScope dev_scope;
+  RHIP_TRY(dev_scope.enter(device_id));
+  struct Buffers {
+    double *in = nullptr, *out = nullptr;
+    ~Buffers() { if (in) (void)hipFree(in); if (out) (void)hipFree(out); }
+  } d;
+  RHIP_TRY(hipMalloc((void**)&d.in, ib));
+  RHIP_TRY(hipMalloc((void**)&d.out, ob));
+  RHIP_TRY(hipMemcpy(d.in, in, ib, hipMemcpyHostToDevice));
+  const unsigned grid = (unsigned)((n + kRBlock - 1) / kRBlock);
+  hipLaunchKernelGGL(salp_robot_math_probe_kernel, dim3(grid), dim3(kRBlock), 0, nullptr, function, d.in, d.out, n, steps);
+  RHIP_TRY(hipGetLastError());
+  RHIP_TRY(hipMemcpy(out, d.out, ob, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -9,7 +9,7 @@
 // Included text rather than a function for the reason given at the top of salp_robot_step_body.h.
 // No include guard: included once per kernel (per cycle loop).
   // Nozzle.solve_angles (robot.py:55-85): target = R_br^T @ -(cos yaw, sin yaw, 0) = (-0, -sin yaw, cos yaw).
-  // Every angle here is within [-pi, pi]: sincos_small (salp_device.h) is exact to < 1 ulp there.
+  // Every angle here is within [-pi, pi]: sincos_small (salp_fp64_math.h) is within 2^-52 absolute of sin / cos there.
   {
     double sy, cy;
     sincos_small(yaw, sy, cy);
@@ -63,7 +63,7 @@
   //  * quantities that depend only on the body shape (mass, inertia, drag factors and their reciprocals)
   //    are kept in registers and recomputed only on a step where some lane's shape moves or has just
   //    stopped moving; during coast / rest (most of a cycle) the whole wavefront skips that block;
-  //  * sin/cos of the Euler angles are carried from step to step (see rotate_sincos below in the loop);
+  //  * sin/cos of the Euler angles are carried from step to step (see advance_euler_sincos below in the loop);
   //  * divisions by dt, by cos(pitch) and by the mass / inertia diagonal are reciprocals (Newton-refined
   //    v_rcp_f64) times a product: a few ulp from the reference's quotient, far inside the parity
   //    tolerance, which is a tolerance already because the reference multiplies 3x3 blocks through BLAS.
@@ -76,8 +76,11 @@
   double mass = 0, inv_m = 0, kd = 0, ktc = 0, ax = 0, I0 = 0, I1 = 0, I2 = 0, iI0 = 0, iI1 = 0, iI2 = 0;
   bool settled = false;    // the previous step of this lane already had the rest shape (and prevI == I)
   // sin / cos of the three Euler angles are carried through the cycle: exact at its start, then advanced by each
-  // step's increment with rotate_sincos (increments are ~1e-3 rad; an increment above 0.25 rad anywhere in the
-  // wavefront takes the exact path for that step).  Drift over a whole cycle stays below 1e-12.
+  // step's increment with advance_euler_sincos (salp_fp64_math.h; increments are ~1e-3 rad; an increment above
+  // kRotateMaxStep = 0.125 rad anywhere in the wavefront takes the exact path for that step).  Over a whole cycle the
+  // carried pair stays within 1e-12 of sin / cos of the exact angle (start + sum of increments).  Against sin / cos
+  // of r.eul itself, which the reference takes, the rounding of `eul += d` comes on top: up to steps * ulp(|eul|) / 2,
+  // 1.3e-9 per cycle for a yaw wound up to 1e4 rad (measured 3.8e-11) — far inside parity (tests/test_robot_math.py).
   double sp, cp, st, ct, ss, cs;
   sincos_euler(r.eul[0], sp, cp);
   sincos_euler(r.eul[1], st, ct);
@@ -182,15 +185,7 @@
         const double e2 = (sp * ict) * r.om[1] + (cp * ict) * r.om[2];
         const double d0 = e0 * dt, d1 = e1 * dt, d2 = e2 * dt;
         r.eul[0] += d0; r.eul[1] += d1; r.eul[2] += d2;
-        if (__any(fabs(d0) > 0.25 || fabs(d1) > 0.25 || fabs(d2) > 0.25)) {
-          sincos_euler(r.eul[0], sp, cp);
-          sincos_euler(r.eul[1], st, ct);
-          sincos_euler(r.eul[2], ss, cs);
-        } else {
-          rotate_sincos(sp, cp, d0);
-          rotate_sincos(st, ct, d1);
-          rotate_sincos(ss, cs, d2);
-        }
+        advance_euler_sincos(r.eul[0], r.eul[1], r.eul[2], d0, d1, d2, sp, cp, st, ct, ss, cs);
       }
       {
         // R = R_z @ R_y @ R_x
