@@ -28,6 +28,7 @@
 #include "../../include/salp_robot.h"
 #include "salp_device.h"   // philox4x32_10, u53
 #include "salp_fp64_math.h"   // sincos_small, sincos_euler, advance_euler_sincos, rcp_nr, sqrt_nr
+#include "salp_host.h"        // fail, HIP_TRY, DeviceScope, check_device_id, StageBuffer, staged()
 
 using namespace salp;
 
@@ -389,44 +390,33 @@ __global__ __launch_bounds__(kRBlock) void salp_robot_math_probe_kernel(int func
   }
 }
 
-thread_local std::string g_rerr;
-int rfail(int code, const std::string& m) { g_rerr = m; return code; }
-#define RHIP_TRY(expr)                                                                              \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) return rfail(_e == hipErrorOutOfMemory ? -4 : -3, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-// Makes `device` current for the scope of one ABI call and restores the caller's device afterwards, so that the
-// library never changes the current HIP device under the caller (PyTorch keeps its own notion of it).  When the
-// caller is already on the handle's device — the usual case — this is one hipGetDevice.
-struct DeviceScope {
-  int prev = -1, changed = 0;
-  hipError_t enter(int device) {
-    hipError_t e = hipGetDevice(&prev);
-    if (e != hipSuccess) return e;
-    if (prev != device) { e = hipSetDevice(device); changed = (e == hipSuccess); }
-    return e;
-  }
-  ~DeviceScope() { if (changed) (void)hipSetDevice(prev); }
-};
-
 }  // namespace
 
+// ---- host side (fail, HIP_TRY, DeviceScope, staged(): salp_host.h) -------------------------------------------------
 struct salp_robot_vec {
   salp_robot_config_t cfg;
   RobotParams P;
   RobotState S;
   int device;
   int64_t n;
-  void* stage;
-  size_t stage_bytes;
+  StageBuffer stage;  // staging for host-pointer calls (shrinks again after a large history, see StageBuffer)
   uint32_t* bins;     // [kSchedBins]
   int32_t* order;     // [n]
   bool schedule;      // walk the envs longest cycle first (see robot_schedule_*)
-  int64_t max_steps;  // Euler steps of the longest cycle the kMaxCycleTime cut allows at this dt (0: not counted
-                      // yet, -1: more than kMaxHistorySteps); robot_max_steps
+  int64_t max_steps;  // robot_max_steps(dt), counted at create
 };
+
+// Longest cycle a history may have to hold, in Euler steps: the step kernel's own count for a cycle of kMaxCycleTime
+// (the same fp64 accumulation of dt).  -1 for a dt so small that this exceeds kMaxHistorySteps: the history and
+// trajectory calls refuse such a handle rather than count (below ~1e-17 s the sum would never reach 14.6 s).
+constexpr int64_t kMaxHistorySteps = (int64_t)1 << 24;
+static int64_t robot_max_steps(double dt) {
+  if (!(kMaxCycleTime / dt <= (double)kMaxHistorySteps)) return -1;
+  double t = 0.0;
+  int64_t k = 0;
+  while (t < kMaxCycleTime && k <= kMaxHistorySteps) { t += dt; ++k; }
+  return k > kMaxHistorySteps ? -1 : k;
+}
 
 // Below this many envs every wavefront has an execution unit to itself and the launch lasts as long as
 // its slowest env whatever the order.  SALP_ROBOT_SCHEDULE=0/1 overrides (tests run both ways).
@@ -438,7 +428,7 @@ static int launch_robot_step(salp_robot_vec* h, const float* act, float* obs, fl
   const unsigned grid = (unsigned)((h->n + kRBlock - 1) / kRBlock);
   const int32_t* order = nullptr;
   if (h->schedule) {
-    RHIP_TRY(hipMemsetAsync(h->bins, 0, kSchedBins * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(h->bins, 0, kSchedBins * sizeof(uint32_t), st));
     const unsigned sgrid = (unsigned)((h->n + kSchedBlock - 1) / kSchedBlock);
     hipLaunchKernelGGL(robot_schedule_count, dim3(sgrid), dim3(kSchedBlock), 0, st, h->P, act, h->bins);
     hipLaunchKernelGGL(robot_schedule_scan, dim3(1), dim3(kSchedBins), 0, st, h->bins);
@@ -451,16 +441,16 @@ static int launch_robot_step(salp_robot_vec* h, const float* act, float* obs, fl
   else
     hipLaunchKernelGGL(salp_robot_step_kernel, dim3(grid), dim3(kRBlock), 0, st, h->P, h->S, act, obs, reward, terminated,
                        truncated, final_obs, inner_steps, order);
-  RHIP_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
 extern "C" {
 
-const char* salp_robot_last_error(void) { return g_rerr.c_str(); }
+const char* salp_robot_last_error(void) { return g_err.c_str(); }
 
 int salp_robot_config_default(salp_robot_config_t* c) {
-  if (!c) return rfail(-1, "cfg is NULL");
+  if (!c) return fail(SALP_ERR_INVALID, "cfg is NULL");
   memset(c, 0, sizeof(*c));
   c->struct_size = (uint32_t)sizeof(*c);
   c->width = 900; c->height = 700; c->tank_margin = 50.0;
@@ -475,20 +465,20 @@ int salp_robot_vec_reset(salp_robot_vec_t* h, const uint8_t* mask, float* obs, u
 
 int salp_robot_vec_create(const salp_robot_config_t* cfg, int64_t n_envs, int device_id, uint64_t seed,
                           int64_t env_index_base, salp_robot_vec_t** out) {
-  if (!out) return rfail(-1, "out is NULL");
+  if (!out) return fail(SALP_ERR_INVALID, "out is NULL");
   *out = nullptr;
-  if (!cfg || cfg->struct_size != sizeof(salp_robot_config_t)) return rfail(-1, "salp_robot_config_t.struct_size mismatch");
-  if (n_envs <= 0 || env_index_base < 0) return rfail(-1, "n_envs / env_index_base out of range");
-  if (!(cfg->dt > 0) || !(cfg->init_width > 0) || !(cfg->nozzle_area > 0)) return rfail(-1, "dt, init_width, nozzle_area must be positive");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return rfail(-2, "no HIP device visible (this library has no CPU fallback)");
-  if (device_id < 0 || device_id >= ndev) return rfail(-2, "device_id out of range");
+  if (!cfg || cfg->struct_size != sizeof(salp_robot_config_t)) return fail(SALP_ERR_INVALID, "salp_robot_config_t.struct_size mismatch");
+  if (n_envs <= 0 || env_index_base < 0) return fail(SALP_ERR_INVALID, "n_envs / env_index_base out of range");
+  if (!(cfg->dt > 0) || !(cfg->init_width > 0) || !(cfg->nozzle_area > 0)) return fail(SALP_ERR_INVALID, "dt, init_width, nozzle_area must be positive");
+  int rc = check_device_id(device_id);
+  if (rc != SALP_OK) return rc;
   DeviceScope dev_scope;
-  RHIP_TRY(dev_scope.enter(device_id));
-  salp_robot_vec* h = new (std::nothrow) salp_robot_vec();
-  if (!h) return rfail(-4, "host allocation failed");
-  memset(h, 0, sizeof(*h));
+  HIP_TRY(dev_scope.enter(device_id));
+  salp_robot_vec* h = new (std::nothrow) salp_robot_vec();     // value-initialised: every field zero
+  if (!h) return fail(SALP_ERR_OOM, "host allocation failed");
   h->cfg = *cfg; h->device = device_id; h->n = n_envs;
+  h->stage.shrink = true;
+  h->max_steps = robot_max_steps(cfg->dt);
   RobotParams& P = h->P;
   P.dry_mass = cfg->dry_mass; P.init_length = cfg->init_length; P.init_width = cfg->init_width;
   P.max_contraction = cfg->max_contraction; P.density = cfg->density; P.dt = cfg->dt;
@@ -511,10 +501,10 @@ int salp_robot_vec_create(const salp_robot_config_t* cfg, int64_t n_envs, int de
   if (n_envs > INT32_MAX) h->schedule = false;
   if (e == hipSuccess && h->schedule) e = hipMalloc((void**)&h->bins, kSchedBins * sizeof(uint32_t));
   if (e == hipSuccess && h->schedule) e = hipMalloc((void**)&h->order, (size_t)n_envs * sizeof(int32_t));
-  if (e != hipSuccess) { std::string m = std::string("state allocation: ") + hipGetErrorString(e); salp_robot_vec_destroy(h); return rfail(-4, m); }
-  int rc = salp_robot_vec_reset(h, nullptr, nullptr, 1u, nullptr);   // train_robot.py:16 angles (0, 0) are the zeroed rows
-  if (rc == 0 && hipDeviceSynchronize() != hipSuccess) rc = rfail(-3, "initial reset failed");
-  if (rc != 0) { std::string m = g_rerr; salp_robot_vec_destroy(h); g_rerr = m; return rc; }
+  if (e != hipSuccess) { std::string m = std::string("state allocation: ") + hipGetErrorString(e); salp_robot_vec_destroy(h); return fail(SALP_ERR_OOM, m); }
+  rc = salp_robot_vec_reset(h, nullptr, nullptr, 1u, nullptr);   // train_robot.py:16 angles (0, 0) are the zeroed rows
+  if (rc == 0 && hipDeviceSynchronize() != hipSuccess) rc = fail(SALP_ERR_HIP, "initial reset failed");
+  if (rc != 0) { std::string m = g_err; salp_robot_vec_destroy(h); g_err = m; return rc; }
   *out = h;
   return 0;
 }
@@ -524,105 +514,72 @@ void salp_robot_vec_destroy(salp_robot_vec_t* h) {
   DeviceScope dev_scope;
   (void)dev_scope.enter(h->device);
   if (h->S.f) (void)hipFree(h->S.f);
-  if (h->stage) (void)hipFree(h->stage);
   if (h->bins) (void)hipFree(h->bins);
   if (h->order) (void)hipFree(h->order);
-  delete h;
+  delete h;     // the staging block goes with it
 }
 
 int64_t salp_robot_vec_num_envs(const salp_robot_vec_t* h) { return h ? h->n : 0; }
 
-static int robot_stage(salp_robot_vec* h, size_t bytes) {
-  // grows on demand; shrinks again when a call needs less than a quarter of a large buffer (a history step with host
-  // pointers can stage gigabytes, the plain step after record_history(False) a few megabytes).  Every host-pointer
-  // call ends with a stream synchronisation, so the old buffer is idle here.
-  if (bytes <= h->stage_bytes && !(h->stage_bytes > ((size_t)64 << 20) && bytes < h->stage_bytes / 4)) return 0;
-  if (h->stage) { (void)hipFree(h->stage); h->stage = nullptr; h->stage_bytes = 0; }
-  RHIP_TRY(hipMalloc(&h->stage, bytes));
-  h->stage_bytes = bytes;
-  return 0;
+int salp_robot_vec_reset(salp_robot_vec_t* h, const uint8_t* mask, float* obs, uint32_t flags, void* stream) {
+  if (!h) return fail(SALP_ERR_INVALID, "handle is NULL");
+  DeviceScope dev_scope;
+  HIP_TRY(dev_scope.enter(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  auto launch = [&](const uint8_t* d_mask, float* d_obs) {
+    hipLaunchKernelGGL(salp_robot_reset_kernel, dim3((unsigned)((h->n + kRBlock - 1) / kRBlock)), dim3(kRBlock), 0, st, h->P, h->S,
+                       d_mask, d_obs, 1);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  };
+  if (flags & 1u) return launch(mask, obs);
+  HostStream s[] = {stream_in(mask, (size_t)h->n), stream_out(obs, (size_t)h->n * 6)};
+  return staged(h->stage, st, s, [&] { return launch(s[0].as<const uint8_t>(), s[1].as<float>()); });
 }
 
-int salp_robot_vec_reset(salp_robot_vec_t* h, const uint8_t* mask, float* obs, uint32_t flags, void* stream) {
-  if (!h) return rfail(-1, "handle is NULL");
+// salp_robot_vec_step (H == NULL) and salp_robot_vec_step_history (H: the caller's range and pointers, count > 0);
+// the arguments have been checked.
+static int robot_step_impl(salp_robot_vec_t* h, const float* act, float* obs, float* reward, uint8_t* terminated,
+                           uint8_t* truncated, float* final_obs, int32_t* inner_steps, const RobotHistory* H, uint32_t flags,
+                           void* stream) {
   DeviceScope dev_scope;
-  RHIP_TRY(dev_scope.enter(h->device));
+  HIP_TRY(dev_scope.enter(h->device));
   hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((h->n + kRBlock - 1) / kRBlock);
-  if (flags & 1u) {
-    hipLaunchKernelGGL(salp_robot_reset_kernel, dim3(grid), dim3(kRBlock), 0, st, h->P, h->S, mask, obs, 1);
-    RHIP_TRY(hipGetLastError());
-    return 0;
-  }
-  const size_t ob = (size_t)h->n * 6 * sizeof(float);
-  int rc = robot_stage(h, ob + (size_t)h->n + 1024);
-  if (rc) return rc;
-  float* d_obs = (float*)h->stage;
-  uint8_t* d_mask = (uint8_t*)h->stage + ((ob + 255) / 256) * 256;
-  if (mask) RHIP_TRY(hipMemcpyAsync(d_mask, mask, (size_t)h->n, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(salp_robot_reset_kernel, dim3(grid), dim3(kRBlock), 0, st, h->P, h->S, mask ? (const uint8_t*)d_mask : nullptr,
-                     obs ? d_obs : nullptr, 1);
-  RHIP_TRY(hipGetLastError());
-  if (obs) RHIP_TRY(hipMemcpyAsync(obs, d_obs, ob, hipMemcpyDeviceToHost, st));
-  RHIP_TRY(hipStreamSynchronize(st));
+  if (flags & 1u) return launch_robot_step(h, act, obs, reward, terminated, truncated, final_obs, inner_steps, st, H);
+  // host pointers.  final_obs goes in as well as out: only the rows of ended episodes are written.  The history stays on
+  // the device until the lengths are known (they are fetched even when the caller does not want them): it goes back as
+  // `count` rows of the longest record of this call, one 2-D copy; nothing is copied in, so in rows with a shorter
+  // record the samples past history_len are overwritten with unspecified values.
+  const size_t n = (size_t)h->n, rows = H ? (size_t)H->count : 0;
+  const size_t row = H ? (size_t)H->capacity * SALP_H_COUNT * sizeof(float) : 0;
+  std::vector<int32_t> len(rows);
+  HostStream s[] = {stream_in(act, n * 3), stream_out(obs, n * 6), stream_out(final_obs, n * 6, true), stream_out(reward, n),
+                    stream_out(terminated, n), stream_out(truncated, n), stream_out(inner_steps, n),
+                    stream_out(H ? len.data() : nullptr, rows), stream_scratch(rows * row)};
+  const int rc = staged(h->stage, st, s, [&] {
+    RobotHistory D;
+    if (H) { D = *H; D.len = s[7].as<int32_t>(); D.hist = s[8].as<float>(); }
+    return launch_robot_step(h, s[0].as<const float>(), s[1].as<float>(), s[3].as<float>(), s[4].as<uint8_t>(), s[5].as<uint8_t>(),
+                             s[2].as<float>(), s[6].as<int32_t>(), st, H ? &D : nullptr);
+  });
+  if (rc != 0 || !H) return rc;
+  int32_t longest = 0;
+  for (int32_t v : len) longest = v > longest ? v : longest;
+  HIP_TRY(hipMemcpy2DAsync(H->hist, row, s[8].dev, row, (size_t)longest * SALP_H_COUNT * sizeof(float), rows,
+                           hipMemcpyDeviceToHost, st));
+  if (H->len) memcpy(H->len, len.data(), rows * sizeof(int32_t));
+  HIP_TRY(hipStreamSynchronize(st));
   return 0;
 }
 
 int salp_robot_vec_step(salp_robot_vec_t* h, const float* act, float* obs, float* reward, uint8_t* terminated,
                         uint8_t* truncated, float* final_obs, int32_t* inner_steps, uint32_t flags, void* stream) {
-  if (!h || !act) return rfail(-1, "handle / act is NULL");
-  DeviceScope dev_scope;
-  RHIP_TRY(dev_scope.enter(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  if (flags & 1u) return launch_robot_step(h, act, obs, reward, terminated, truncated, final_obs, inner_steps, st);
-  const size_t n = (size_t)h->n;
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t need = up(n * 12) + 2 * up(n * 24) + up(n * 4) + 2 * up(n) + up(n * 4) + 1024;
-  int rc = robot_stage(h, need);
-  if (rc) return rc;
-  char* b = (char*)h->stage;
-  float* d_act = (float*)b; b += up(n * 12);
-  float* d_obs = (float*)b; b += up(n * 24);
-  float* d_fin = (float*)b; b += up(n * 24);
-  float* d_rew = (float*)b; b += up(n * 4);
-  uint8_t* d_te = (uint8_t*)b; b += up(n);
-  uint8_t* d_tr = (uint8_t*)b; b += up(n);
-  int32_t* d_in = (int32_t*)b;
-  RHIP_TRY(hipMemcpyAsync(d_act, act, n * 12, hipMemcpyHostToDevice, st));
-  if (final_obs) RHIP_TRY(hipMemcpyAsync(d_fin, final_obs, n * 24, hipMemcpyHostToDevice, st));
-  rc = launch_robot_step(h, d_act, obs ? d_obs : nullptr, reward ? d_rew : nullptr, terminated ? d_te : nullptr,
-                         truncated ? d_tr : nullptr, final_obs ? d_fin : nullptr, inner_steps ? d_in : nullptr, st);
-  if (rc) return rc;
-  if (obs) RHIP_TRY(hipMemcpyAsync(obs, d_obs, n * 24, hipMemcpyDeviceToHost, st));
-  if (final_obs) RHIP_TRY(hipMemcpyAsync(final_obs, d_fin, n * 24, hipMemcpyDeviceToHost, st));
-  if (reward) RHIP_TRY(hipMemcpyAsync(reward, d_rew, n * 4, hipMemcpyDeviceToHost, st));
-  if (terminated) RHIP_TRY(hipMemcpyAsync(terminated, d_te, n, hipMemcpyDeviceToHost, st));
-  if (truncated) RHIP_TRY(hipMemcpyAsync(truncated, d_tr, n, hipMemcpyDeviceToHost, st));
-  if (inner_steps) RHIP_TRY(hipMemcpyAsync(inner_steps, d_in, n * 4, hipMemcpyDeviceToHost, st));
-  RHIP_TRY(hipStreamSynchronize(st));
-  return 0;
+  if (!h || !act) return fail(SALP_ERR_INVALID, "handle / act is NULL");
+  return robot_step_impl(h, act, obs, reward, terminated, truncated, final_obs, inner_steps, nullptr, flags, stream);
 }
 
-// Longest cycle a history may have to hold, in Euler steps: the step kernel's own count for a cycle of kMaxCycleTime
-// (the same fp64 accumulation of dt), counted on first use.  A dt so small that this exceeds kMaxHistorySteps is
-// refused by the history calls rather than counted (below ~1e-17 s the sum would never reach 14.6 s).
-constexpr int64_t kMaxHistorySteps = (int64_t)1 << 24;
-static int64_t robot_max_steps(const salp_robot_vec* h) {
-  if (h->max_steps == 0) {
-    int64_t k = -1;
-    if (kMaxCycleTime / h->P.dt <= (double)kMaxHistorySteps) {
-      double t = 0.0;
-      k = 0;
-      while (t < kMaxCycleTime && k <= kMaxHistorySteps) { t += h->P.dt; ++k; }
-      if (k > kMaxHistorySteps) k = -1;
-    }
-    const_cast<salp_robot_vec*>(h)->max_steps = k;   // the same value whichever thread counts it
-  }
-  return h->max_steps;
-}
 static int64_t history_capacity(const salp_robot_vec* h, int32_t stride) {   // ceil(T_max / stride) + 1 samples, or -1
-  const int64_t t = robot_max_steps(h);
-  return t < 0 ? -1 : (t + stride - 1) / stride + 1;
+  return h->max_steps < 0 ? -1 : (h->max_steps + stride - 1) / stride + 1;
 }
 
 int32_t salp_robot_vec_history_capacity(const salp_robot_vec_t* h, int32_t stride) {
@@ -634,173 +591,98 @@ int salp_robot_vec_step_history(salp_robot_vec_t* h, const float* act, float* ob
                                 uint8_t* truncated, float* final_obs, int32_t* inner_steps, int64_t hist_begin,
                                 int64_t hist_count, int32_t stride, int32_t capacity, float* history,
                                 int32_t* history_len, uint32_t flags, void* stream) {
-  if (!h || !act) return rfail(-1, "handle / act is NULL");
-  if (stride < 1) return rfail(-1, "history stride must be >= 1");
+  if (!h || !act) return fail(SALP_ERR_INVALID, "handle / act is NULL");
+  if (stride < 1) return fail(SALP_ERR_INVALID, "history stride must be >= 1");
   if (hist_count < 0 || hist_begin < 0 || hist_begin > h->n || hist_count > h->n - hist_begin)
-    return rfail(-1, "history env range [hist_begin, hist_begin + hist_count) is outside [0, n_envs)");
+    return fail(SALP_ERR_INVALID, "history env range [hist_begin, hist_begin + hist_count) is outside [0, n_envs)");
   if (hist_count == 0)
-    return salp_robot_vec_step(h, act, obs, reward, terminated, truncated, final_obs, inner_steps, flags, stream);
+    return robot_step_impl(h, act, obs, reward, terminated, truncated, final_obs, inner_steps, nullptr, flags, stream);
   const int64_t need_cap = history_capacity(h, stride);
-  if (need_cap < 0) return rfail(-1, "dt is too small to record a history (more than 2^24 Euler steps per cycle)");
+  if (need_cap < 0) return fail(SALP_ERR_INVALID, "dt is too small to record a history (more than 2^24 Euler steps per cycle)");
   if ((int64_t)capacity < need_cap)
-    return rfail(-1, "history capacity " + std::to_string(capacity) + " is below salp_robot_vec_history_capacity = " +
+    return fail(SALP_ERR_INVALID, "history capacity " + std::to_string(capacity) + " is below salp_robot_vec_history_capacity = " +
                      std::to_string(need_cap));
-  if (!history) return rfail(-1, "history is NULL while hist_count > 0");
-  if ((flags & 1u) && ((uintptr_t)history % 16u) != 0) return rfail(-1, "device history must be 16-byte aligned");
-  DeviceScope dev_scope;
-  RHIP_TRY(dev_scope.enter(h->device));
-  hipStream_t st = (hipStream_t)stream;
+  if (!history) return fail(SALP_ERR_INVALID, "history is NULL while hist_count > 0");
+  if ((flags & 1u) && ((uintptr_t)history % 16u) != 0) return fail(SALP_ERR_INVALID, "device history must be 16-byte aligned");
   RobotHistory H;
-  H.begin = hist_begin; H.count = hist_count; H.stride = stride; H.capacity = capacity;
-  if (flags & 1u) {
-    H.hist = history; H.len = history_len;
-    return launch_robot_step(h, act, obs, reward, terminated, truncated, final_obs, inner_steps, st, &H);
-  }
-  // host pointers: everything staged as in salp_robot_vec_step.  The history goes back as hist_count rows of the
-  // longest record of this call (one 2-D copy after the lengths are known); nothing is copied in, so in rows with
-  // a shorter record the samples past history_len are overwritten with unspecified values.
-  const size_t n = (size_t)h->n;
-  const size_t hb = (size_t)hist_count * (size_t)capacity * SALP_H_COUNT * sizeof(float);
-  const size_t lb = (size_t)hist_count * sizeof(int32_t);
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t need = up(n * 12) + 2 * up(n * 24) + up(n * 4) + 2 * up(n) + up(n * 4) + up(lb) + hb + 1024;
-  int rc = robot_stage(h, need);
-  if (rc) return rc;
-  char* b = (char*)h->stage;
-  float* d_act = (float*)b; b += up(n * 12);
-  float* d_obs = (float*)b; b += up(n * 24);
-  float* d_fin = (float*)b; b += up(n * 24);
-  float* d_rew = (float*)b; b += up(n * 4);
-  uint8_t* d_te = (uint8_t*)b; b += up(n);
-  uint8_t* d_tr = (uint8_t*)b; b += up(n);
-  int32_t* d_in = (int32_t*)b; b += up(n * 4);
-  int32_t* d_len = (int32_t*)b; b += up(lb);
-  float* d_hist = (float*)b;
-  RHIP_TRY(hipMemcpyAsync(d_act, act, n * 12, hipMemcpyHostToDevice, st));
-  if (final_obs) RHIP_TRY(hipMemcpyAsync(d_fin, final_obs, n * 24, hipMemcpyHostToDevice, st));
-  H.hist = d_hist; H.len = d_len;
-  rc = launch_robot_step(h, d_act, obs ? d_obs : nullptr, reward ? d_rew : nullptr, terminated ? d_te : nullptr,
-                         truncated ? d_tr : nullptr, final_obs ? d_fin : nullptr, inner_steps ? d_in : nullptr, st, &H);
-  if (rc) return rc;
-  if (obs) RHIP_TRY(hipMemcpyAsync(obs, d_obs, n * 24, hipMemcpyDeviceToHost, st));
-  if (final_obs) RHIP_TRY(hipMemcpyAsync(final_obs, d_fin, n * 24, hipMemcpyDeviceToHost, st));
-  if (reward) RHIP_TRY(hipMemcpyAsync(reward, d_rew, n * 4, hipMemcpyDeviceToHost, st));
-  if (terminated) RHIP_TRY(hipMemcpyAsync(terminated, d_te, n, hipMemcpyDeviceToHost, st));
-  if (truncated) RHIP_TRY(hipMemcpyAsync(truncated, d_tr, n, hipMemcpyDeviceToHost, st));
-  if (inner_steps) RHIP_TRY(hipMemcpyAsync(inner_steps, d_in, n * 4, hipMemcpyDeviceToHost, st));
-  std::vector<int32_t> len((size_t)hist_count);
-  RHIP_TRY(hipMemcpyAsync(len.data(), d_len, lb, hipMemcpyDeviceToHost, st));
-  RHIP_TRY(hipStreamSynchronize(st));
-  int32_t longest = 0;
-  for (int32_t v : len) longest = v > longest ? v : longest;
-  const size_t row = (size_t)capacity * SALP_H_COUNT * sizeof(float);
-  RHIP_TRY(hipMemcpy2DAsync(history, row, d_hist, row, (size_t)longest * SALP_H_COUNT * sizeof(float), (size_t)hist_count,
-                            hipMemcpyDeviceToHost, st));
-  if (history_len) memcpy(history_len, len.data(), lb);
-  RHIP_TRY(hipStreamSynchronize(st));
-  return 0;
+  H.hist = history; H.len = history_len; H.begin = hist_begin; H.count = hist_count; H.stride = stride; H.capacity = capacity;
+  return robot_step_impl(h, act, obs, reward, terminated, truncated, final_obs, inner_steps, &H, flags, stream);
 }
 
 int salp_robot_vec_trajectory(salp_robot_vec_t* h, const double* params, const double* actions, int32_t cycles,
                               const double* expected, double* states, double* metrics, int32_t* inner_steps,
                               uint32_t flags, void* stream) {
-  if (!h || !actions) return rfail(-1, "handle / actions is NULL");
+  if (!h || !actions) return fail(SALP_ERR_INVALID, "handle / actions is NULL");
   if (cycles < 1 || cycles > kMaxTrajectoryCycles)
-    return rfail(-1, "cycles must be in [1, " + std::to_string(kMaxTrajectoryCycles) + "]");
-  if (flags & ~(1u | (uint32_t)SALP_ROBOT_PER_ROBOT_ACTIONS)) return rfail(-1, "unknown flag bits");
-  if (metrics && !expected) return rfail(-1, "metrics need expected states");
+    return fail(SALP_ERR_INVALID, "cycles must be in [1, " + std::to_string(kMaxTrajectoryCycles) + "]");
+  if (flags & ~(1u | (uint32_t)SALP_ROBOT_PER_ROBOT_ACTIONS)) return fail(SALP_ERR_INVALID, "unknown flag bits");
+  if (metrics && !expected) return fail(SALP_ERR_INVALID, "metrics need expected states");
   // the same refusal as the history calls: with such a dt one cycle of the 14.6 s cut exceeds 2^24 Euler steps
-  if (robot_max_steps(h) < 0) return rfail(-1, "dt is too small (more than 2^24 Euler steps per cycle)");
+  if (h->max_steps < 0) return fail(SALP_ERR_INVALID, "dt is too small (more than 2^24 Euler steps per cycle)");
   DeviceScope dev_scope;
-  RHIP_TRY(dev_scope.enter(h->device));
+  HIP_TRY(dev_scope.enter(h->device));
   hipStream_t st = (hipStream_t)stream;
   const bool per_robot = (flags & SALP_ROBOT_PER_ROBOT_ACTIONS) != 0;
-  const unsigned grid = (unsigned)((h->n + kRBlock - 1) / kRBlock);
   RobotTrajectory J;
   J.cycles = cycles; J.per_robot = per_robot ? 1 : 0;
-  if (flags & 1u) {
-    J.params = params; J.actions = actions; J.expected = expected; J.states = states; J.metrics = metrics;
-    J.inner_steps = inner_steps;
-    hipLaunchKernelGGL(salp_robot_trajectory_kernel, dim3(grid), dim3(kRBlock), 0, st, h->P, J);
-    RHIP_TRY(hipGetLastError());
+  auto launch = [&](const double* d_par, const double* d_act, const double* d_exp, double* d_st, double* d_met, int32_t* d_in) {
+    J.params = d_par; J.actions = d_act; J.expected = d_exp; J.states = d_st; J.metrics = d_met; J.inner_steps = d_in;
+    hipLaunchKernelGGL(salp_robot_trajectory_kernel, dim3((unsigned)((h->n + kRBlock - 1) / kRBlock)), dim3(kRBlock), 0, st, h->P, J);
+    HIP_TRY(hipGetLastError());
     return 0;
-  }
-  // host pointers: staged and copied back like the other calls
+  };
+  if (flags & 1u) return launch(params, actions, expected, states, metrics, inner_steps);
   const size_t n = (size_t)h->n, T = (size_t)cycles;
-  const size_t pb = params ? (size_t)SALP_RP_COUNT * n * 8 : 0, ab = T * (per_robot ? n : 1) * 24;
-  const size_t xb = expected ? T * 48 : 0, sb = states ? T * n * 48 : 0, mb = metrics ? n * SALP_RM_COUNT * 8 : 0;
-  const size_t ib = inner_steps ? T * n * 4 : 0;
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  int rc = robot_stage(h, up(pb) + up(ab) + up(xb) + up(sb) + up(mb) + up(ib) + 1024);
-  if (rc) return rc;
-  char* b = (char*)h->stage;
-  double* d_par = (double*)b; b += up(pb);
-  double* d_act = (double*)b; b += up(ab);
-  double* d_exp = (double*)b; b += up(xb);
-  double* d_st = (double*)b; b += up(sb);
-  double* d_met = (double*)b; b += up(mb);
-  int32_t* d_in = (int32_t*)b;
-  if (params) RHIP_TRY(hipMemcpyAsync(d_par, params, pb, hipMemcpyHostToDevice, st));
-  RHIP_TRY(hipMemcpyAsync(d_act, actions, ab, hipMemcpyHostToDevice, st));
-  if (expected) RHIP_TRY(hipMemcpyAsync(d_exp, expected, xb, hipMemcpyHostToDevice, st));
-  J.params = params ? d_par : nullptr; J.actions = d_act; J.expected = expected ? d_exp : nullptr;
-  J.states = states ? d_st : nullptr; J.metrics = metrics ? d_met : nullptr; J.inner_steps = inner_steps ? d_in : nullptr;
-  hipLaunchKernelGGL(salp_robot_trajectory_kernel, dim3(grid), dim3(kRBlock), 0, st, h->P, J);
-  RHIP_TRY(hipGetLastError());
-  if (states) RHIP_TRY(hipMemcpyAsync(states, d_st, sb, hipMemcpyDeviceToHost, st));
-  if (metrics) RHIP_TRY(hipMemcpyAsync(metrics, d_met, mb, hipMemcpyDeviceToHost, st));
-  if (inner_steps) RHIP_TRY(hipMemcpyAsync(inner_steps, d_in, ib, hipMemcpyDeviceToHost, st));
-  RHIP_TRY(hipStreamSynchronize(st));
-  return 0;
+  HostStream s[] = {stream_in(params, (size_t)SALP_RP_COUNT * n), stream_in(actions, T * (per_robot ? n : 1) * 3),
+                    stream_in(expected, T * 6), stream_out(states, T * n * 6), stream_out(metrics, n * SALP_RM_COUNT),
+                    stream_out(inner_steps, T * n)};
+  return staged(h->stage, st, s, [&] {
+    return launch(s[0].as<const double>(), s[1].as<const double>(), s[2].as<const double>(), s[3].as<double>(), s[4].as<double>(),
+                  s[5].as<int32_t>());
+  });
 }
 
 int salp_robot_vec_get_state(salp_robot_vec_t* h, double* state, uint32_t flags, void* stream) {
-  if (!h || !state) return rfail(-1, "handle / state is NULL");
+  if (!h || !state) return fail(SALP_ERR_INVALID, "handle / state is NULL");
   DeviceScope dev_scope;
-  RHIP_TRY(dev_scope.enter(h->device));
+  HIP_TRY(dev_scope.enter(h->device));
   hipStream_t st = (hipStream_t)stream;
   // rows are [pitch] on the device and [n] in the snapshot
-  RHIP_TRY(hipMemcpy2DAsync(state, (size_t)h->n * sizeof(double), h->S.f, (size_t)h->P.pitch * sizeof(double),
+  HIP_TRY(hipMemcpy2DAsync(state, (size_t)h->n * sizeof(double), h->S.f, (size_t)h->P.pitch * sizeof(double),
                             (size_t)h->n * sizeof(double), SALP_R_COUNT,
                             (flags & 1u) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-  if (!(flags & 1u)) RHIP_TRY(hipStreamSynchronize(st));
+  if (!(flags & 1u)) HIP_TRY(hipStreamSynchronize(st));
   return 0;
 }
 
 // Test support (salp_fp64_math.h): one of the fp64 primitives over host arrays, staged like the other host-pointer calls.
 int salp_robot_math_probe(int device_id, int function, const double* in, double* out, int64_t n, int32_t steps) {
-  if (!in || !out) return rfail(-1, "in / out is NULL");
-  if (n < 1 || n > ((int64_t)1 << 24)) return rfail(-1, "n must be in [1, 2^24]");
+  if (!in || !out) return fail(SALP_ERR_INVALID, "in / out is NULL");
+  if (n < 1 || n > ((int64_t)1 << 24)) return fail(SALP_ERR_INVALID, "n must be in [1, 2^24]");
   size_t rows_in = 1, rows_out = 2;
   switch (function) {
     case SALP_MATH_SINCOS_SMALL: case SALP_MATH_SINCOS_EULER: break;
     case SALP_MATH_ROTATE: rows_in = 3; break;
     case SALP_MATH_CHAIN:
-      if (steps < 0 || steps > 65536) return rfail(-1, "steps must be in [0, 65536]");
+      if (steps < 0 || steps > 65536) return fail(SALP_ERR_INVALID, "steps must be in [0, 65536]");
       rows_in = 1 + (size_t)steps; rows_out = 3;
       break;
     case SALP_MATH_RCP_NR: case SALP_MATH_SQRT_NR: rows_out = 1; break;
-    default: return rfail(-1, "unknown function code");
+    default: return fail(SALP_ERR_INVALID, "unknown function code");
   }
-  const size_t ib = rows_in * (size_t)n * sizeof(double), ob = rows_out * (size_t)n * sizeof(double);
-  if (ib > ((size_t)1 << 31)) return rfail(-1, "input larger than 2 GiB");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return rfail(-2, "no HIP device visible (this library has no CPU fallback)");
-  if (device_id < 0 || device_id >= ndev) return rfail(-2, "device_id out of range");
+  if (rows_in * (size_t)n * sizeof(double) > ((size_t)1 << 31)) return fail(SALP_ERR_INVALID, "input larger than 2 GiB");
+  const int rc = check_device_id(device_id);
+  if (rc != SALP_OK) return rc;
   DeviceScope dev_scope;
-  RHIP_TRY(dev_scope.enter(device_id));
-  struct Buffers {
-    double *in = nullptr, *out = nullptr;
-    ~Buffers() { if (in) (void)hipFree(in); if (out) (void)hipFree(out); }
-  } d;
-  RHIP_TRY(hipMalloc((void**)&d.in, ib));
-  RHIP_TRY(hipMalloc((void**)&d.out, ob));
-  RHIP_TRY(hipMemcpy(d.in, in, ib, hipMemcpyHostToDevice));
-  const unsigned grid = (unsigned)((n + kRBlock - 1) / kRBlock);
-  hipLaunchKernelGGL(salp_robot_math_probe_kernel, dim3(grid), dim3(kRBlock), 0, nullptr, function, d.in, d.out, n, steps);
-  RHIP_TRY(hipGetLastError());
-  RHIP_TRY(hipMemcpy(out, d.out, ob, hipMemcpyDeviceToHost));
-  return 0;
+  HIP_TRY(dev_scope.enter(device_id));
+  StageBuffer stage;     // the call's own, released on return
+  HostStream s[] = {stream_in(in, rows_in * (size_t)n), stream_out(out, rows_out * (size_t)n)};
+  return staged(stage, nullptr, s, [&] {
+    hipLaunchKernelGGL(salp_robot_math_probe_kernel, dim3((unsigned)((n + kRBlock - 1) / kRBlock)), dim3(kRBlock), 0, nullptr, function,
+                       s[0].as<const double>(), s[1].as<double>(), n, steps);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  });
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include <string>
 #include <type_traits>
 
+#include "salp_host.h"
 #include "salp_rollout_kernel.h"
 
 namespace {
@@ -136,35 +137,9 @@ __global__ __launch_bounds__(kBlock) void salp_reseed_kernel(ColdBlock* cold, De
   if (i < (int64_t)SALP_STATS_REPLICAS * 16) stats[i / 16].v[i % 16] = 0ull;
 }
 
-// ------------------------------------------------------------------ host side
-thread_local std::string g_err;
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess)                                                                          \
-      return fail(_e == hipErrorOutOfMemory ? SALP_ERR_OOM : SALP_ERR_HIP,                         \
-                  std::string(#expr) + ": " + hipGetErrorString(_e));                              \
-  } while (0)
-
-
-// Makes `device` current for the scope of one ABI call and restores the caller's device afterwards, so that the
-// library never changes the current HIP device under the caller (PyTorch keeps its own notion of it).  When the
-// caller is already on the handle's device — the usual case — this is one hipGetDevice.
-struct DeviceScope {
-  int prev = -1, changed = 0;
-  hipError_t enter(int device) {
-    hipError_t e = hipGetDevice(&prev);
-    if (e != hipSuccess) return e;
-    if (prev != device) { e = hipSetDevice(device); changed = (e == hipSuccess); }
-    return e;
-  }
-  ~DeviceScope() { if (changed) (void)hipSetDevice(prev); }
-};
-
 }  // namespace
 
+// ------------------------------------------------------------------ host side (fail, HIP_TRY, DeviceScope, staged(): salp_host.h)
 struct salp_vec {
   salp_config_t cfg;
   DevParams P;
@@ -179,9 +154,7 @@ struct salp_vec {
   DevStats* stats;       // device, SALP_STATS_REPLICAS replicas
   int stats_enabled;
   ColdBlock* cold;       // device copy of P and S for the rollout kernel's rare paths
-  // staging for host-pointer calls (grown on demand)
-  void* stage;
-  size_t stage_bytes;
+  StageBuffer stage;     // staging for host-pointer calls (grown on demand)
   float* act_buf;        // device-generated actions when the caller gives no act_out
   size_t act_bytes;
   size_t nf_rows;
@@ -311,53 +284,7 @@ bool is_std(const DevParams& P) {
          P.cycle_len == C::cycle_len;
 }
 
-int ensure_stage(salp_vec* h, size_t bytes) {
-  if (bytes <= h->stage_bytes) return SALP_OK;
-  if (h->stage) { (void)hipFree(h->stage); h->stage = nullptr; h->stage_bytes = 0; }
-  HIP_TRY(hipMalloc(&h->stage, bytes));
-  h->stage_bytes = bytes;
-  return SALP_OK;
-}
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }   // workgroups of kBlock threads
-
-// One stream of a host-pointer call: `count` elements at `host` (NULL = the stream is absent), copied to the device before
-// the launch (kIn), back after it (kOut) or both.  staged() fills in `dev`, NULL for an absent stream.
-enum { kIn = 1, kOut = 2 };
-struct HostStream {
-  void* host; size_t bytes; int dir;
-  void* dev;
-  template <class T> T* as() const { return static_cast<T*>(dev); }
-};
-template <class T> HostStream stream_in(const T* p, size_t count) { return {const_cast<T*>(p), count * sizeof(T), kIn, nullptr}; }
-template <class T> HostStream stream_out(T* p, size_t count, bool also_in = false) { return {p, count * sizeof(T), also_in ? kIn | kOut : kOut, nullptr}; }
-
-// The host-pointer form of a call, synchronous: the streams that are present get 256-byte-aligned pieces of the handle's
-// staging block (grown on demand), the kIn ones are copied in, `launch` enqueues the call's kernels on the device pointers
-// — a failure there ends the call — then the kOut ones are copied out and the stream is waited for.
-template <int N, class Launch>
-int staged(salp_vec* h, hipStream_t st, HostStream (&s)[N], Launch&& launch) {
-  size_t need = 0;
-  for (const HostStream& x : s)
-    if (x.host) need = align_up(need, 256) + x.bytes;
-  int rc = ensure_stage(h, need);
-  if (rc != SALP_OK) return rc;
-  size_t off = 0;
-  for (HostStream& x : s) {
-    if (!x.host) continue;
-    off = align_up(off, 256);
-    x.dev = (char*)h->stage + off;
-    off += x.bytes;
-    if (x.dir & kIn) HIP_TRY(hipMemcpyAsync(x.dev, x.host, x.bytes, hipMemcpyHostToDevice, st));
-  }
-  rc = launch();
-  if (rc != SALP_OK) return rc;
-  for (const HostStream& x : s)
-    if (x.host && (x.dir & kOut)) HIP_TRY(hipMemcpyAsync(x.host, x.dev, x.bytes, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return SALP_OK;
-}
 
 // The part of IOPtrs that every rollout call fills in the same way; the rest starts out NULL.
 IOPtrs io_for(const salp_vec* h) {
@@ -532,16 +459,13 @@ int salp_vec_create(const salp_config_t* cfg, int64_t n_envs, int device_id, uin
   if (rc != SALP_OK) return rc;
   if (n_envs <= 0 || n_envs > ((int64_t)1 << 31) - kBlock) return fail(SALP_ERR_INVALID, "n_envs out of range");
   if (env_index_base < 0) return fail(SALP_ERR_INVALID, "env_index_base must be >= 0");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(SALP_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
-  if (device_id < 0 || device_id >= ndev) return fail(SALP_ERR_NO_DEVICE, "device_id out of range");
+  rc = check_device_id(device_id);
+  if (rc != SALP_OK) return rc;
   DeviceScope dev_scope;
   HIP_TRY(dev_scope.enter(device_id));
 
-  salp_vec* h = new (std::nothrow) salp_vec();
+  salp_vec* h = new (std::nothrow) salp_vec();     // value-initialised: every field zero
   if (!h) return fail(SALP_ERR_OOM, "host allocation failed");
-  memset(h, 0, sizeof(*h));
   h->last_sigs[0] = h->last_sigs[1] = -1;
   h->cfg = *cfg; h->device = device_id; h->n = n_envs; h->seed = seed; h->global_step = 0;
   h->F = cfg->num_food_items; h->K = cfg->max_observed_food;
@@ -605,9 +529,8 @@ void salp_vec_destroy(salp_vec_t* h) {
   if (h->S.i) (void)hipFree(h->S.i);
   if (h->stats) (void)hipFree(h->stats);
   if (h->cold) (void)hipFree(h->cold);
-  if (h->stage) (void)hipFree(h->stage);
   if (h->act_buf) (void)hipFree(h->act_buf);
-  delete h;
+  delete h;     // the staging block goes with it
 }
 
 int64_t salp_vec_num_envs(const salp_vec_t* h) { return h ? h->n : 0; }
@@ -670,7 +593,7 @@ int salp_vec_reset(salp_vec_t* h, const uint8_t* mask, float* obs, uint32_t flag
   };
   if (flags & SALP_DEVICE_PTRS) return launch(mask, obs);
   HostStream s[] = {stream_out(obs, (size_t)h->n * h->obs_dim), stream_in(mask, (size_t)h->n)};
-  return staged(h, st, s, [&] { return launch(s[1].as<const uint8_t>(), s[0].as<float>()); });
+  return staged(h->stage, st, s, [&] { return launch(s[1].as<const uint8_t>(), s[0].as<float>()); });
 }
 
 int salp_vec_observe(salp_vec_t* h, float* obs, uint32_t flags, void* stream) {
@@ -687,7 +610,7 @@ int salp_vec_observe(salp_vec_t* h, float* obs, uint32_t flags, void* stream) {
   };
   if (flags & SALP_DEVICE_PTRS) return launch(obs);
   HostStream s[] = {stream_out(obs, (size_t)h->n * h->obs_dim)};
-  return staged(h, st, s, [&] { return launch(s[0].as<float>()); });
+  return staged(h->stage, st, s, [&] { return launch(s[0].as<float>()); });
 }
 
 // Behind the launches of a sampled call: the policy's noise step goes on by the call's horizon, on the device (a replayed
@@ -755,7 +678,7 @@ static int rollout_impl(salp_vec_t* h, const float* act, int32_t H, float* obs, 
   HostStream s[] = {act ? stream_in(act, HN * h->act_dim) : stream_out(act_out, HN * h->act_dim),
                     stream_out(obs, HN * h->obs_dim), stream_out(final_obs, HN * h->obs_dim, true), stream_out(reward, HN),
                     stream_out(terminated, HN), stream_out(truncated, HN), stream_out(info, HN * SALP_INFO_COLS)};
-  return staged(h, st, s, [&] {
+  return staged(h->stage, st, s, [&] {
     io.act = s[0].as<float>();
     if (!act) {
       int rc = generate_actions(h, H, s[0].as<float>(), st, &io.act);
@@ -812,7 +735,7 @@ static int packed_impl(salp_vec_t* h, const float* act, int32_t H, float* rec, f
   const size_t HN = (size_t)H * (size_t)h->n;
   HostStream s[] = {act ? stream_in(act, HN * h->act_dim) : stream_out(act_out, HN * h->act_dim),
                     stream_out(rec, HN * (size_t)salp_vec_record_width(h, flags), with_final)};   // in: the tails of unfinished rows stay as they are
-  return staged(h, st, s, [&] { return launch(s[0].as<float>(), s[0].as<float>(), s[1].as<float>()); });
+  return staged(h->stage, st, s, [&] { return launch(s[0].as<float>(), s[0].as<float>(), s[1].as<float>()); });
 }
 
 int salp_vec_step_packed(salp_vec_t* h, const float* act, float* rec, uint32_t flags, void* stream) {
@@ -991,7 +914,7 @@ static int rollout_policy_impl(salp_vec_t* h, const salp_policy_t* pol, int32_t 
   const size_t HN = (size_t)H * (size_t)h->n;
   HostStream s[] = {stream_out(obs, HN * h->obs_dim), stream_out(reward, HN), stream_out(terminated, HN), stream_out(truncated, HN),
                     stream_out(act_out, HN * h->act_dim), stream_out(sampled ? logp_out : nullptr, HN)};
-  return staged(h, st, s, [&] {
+  return staged(h->stage, st, s, [&] {
     return launch(s[0].as<float>(), s[1].as<float>(), s[2].as<uint8_t>(), s[3].as<uint8_t>(), s[4].as<float>(), s[5].as<float>());
   });
 }
@@ -1030,7 +953,7 @@ static int evaluate_policy_impl(salp_vec_t* h, const salp_policy_t* pol, int32_t
   };
   if (flags & SALP_DEVICE_PTRS) return launch((float*)rec);
   HostStream s[] = {stream_out((int32_t*)rec, (size_t)h->n * SALP_EVAL_WORDS, accumulate)};
-  return staged(h, st, s, [&] { return launch(s[0].as<float>()); });
+  return staged(h->stage, st, s, [&] { return launch(s[0].as<float>()); });
 }
 
 int salp_vec_evaluate_policy(salp_vec_t* h, const salp_policy_t* pol, int32_t H, void* rec, uint32_t flags, void* stream) {
@@ -1054,7 +977,7 @@ int salp_vec_get_state(salp_vec_t* h, double* f64, int32_t* i32, uint32_t flags,
   };
   if (flags & SALP_DEVICE_PTRS) return launch(f64, i32);
   HostStream s[] = {stream_out(f64, (size_t)SALP_F_COUNT(h->F) * h->n), stream_out(i32, (size_t)SALP_I_COUNT * h->n)};
-  return staged(h, st, s, [&] { return launch(s[0].as<double>(), s[1].as<int32_t>()); });
+  return staged(h->stage, st, s, [&] { return launch(s[0].as<double>(), s[1].as<int32_t>()); });
 }
 
 // The ranges of include/salp_vec.h ("Ranges accepted by salp_vec_set_state"), on a host snapshot.
@@ -1106,7 +1029,7 @@ int salp_vec_set_state(salp_vec_t* h, const double* f64, const int32_t* i32, uin
   };
   if (flags & SALP_DEVICE_PTRS) return launch(f64, i32);
   HostStream s[] = {stream_in(f64, (size_t)SALP_F_COUNT(h->F) * h->n), stream_in(i32, (size_t)SALP_I_COUNT * h->n)};
-  return staged(h, st, s, [&] { return launch(s[0].as<const double>(), s[1].as<const int32_t>()); });
+  return staged(h->stage, st, s, [&] { return launch(s[0].as<const double>(), s[1].as<const int32_t>()); });
 }
 
 int salp_vec_get_stats(salp_vec_t* h, salp_stats_t* out) {

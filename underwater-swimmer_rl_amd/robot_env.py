@@ -117,11 +117,7 @@ class SalpRobotVectorEnv:
             return self._torch.empty(shape, dtype=td, device=self.device)
         return np.empty(shape, dtype)
 
-    @staticmethod
-    def _p(x):
-        if x is None:
-            return None
-        return ctypes.c_void_p(x.data_ptr()) if hasattr(x, "data_ptr") else x.ctypes.data_as(ctypes.c_void_p)
+    _p = staticmethod(_capi.SalpLib._ptr)
 
     @property
     def _flags(self):
