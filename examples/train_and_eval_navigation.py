@@ -13,7 +13,10 @@ goal in 99 of 100 trials (1766 +/- 220 steps, path ratio 1.175, straightness 0.8
 138, 1.137, 0.883); the kept checkpoint scores 100 of 100 on fresh headings with 1702 +/- 135 steps, 1.127, 0.892.
 The scripted pursuit baseline: 99 of 100, 1817 +/- 216, 1.175, 0.860.  The reference's published policy: 100 of 100,
 1774 +/- 254, 1.173, 0.863.  (The YAML's learner as is - fixed alpha 0.2, batch 256, unscaled reward - oscillates at
-this update-to-data ratio; that is the only reason for the flags above.)"""
+this update-to-data ratio; that is the only reason for the flags above.)
+Those figures were taken with `run_navigation_trials` (one kernel launch per env-step).  The evaluations now run the whole
+trial loop in one launch (`run_navigation_trials_in_kernel`, salp_vec_evaluate_navigation) whenever the actor fits
+`MLPPolicy.from_actor` (up to two hidden layers of 16-64 units), and fall back to the stepwise runner otherwise."""
 import argparse
 import json
 import os
@@ -23,7 +26,8 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import underwater_swimmer_rl_amd as salp
-from underwater_swimmer_rl_amd.navigation_eval import pursuit_policy, run_navigation_trials, summarize
+from underwater_swimmer_rl_amd.navigation_eval import (pursuit_mlp, run_navigation_trials,
+                                                       run_navigation_trials_in_kernel, summarize)
 from underwater_swimmer_rl_amd.sac import SAC, DeviceReplayBuffer, SACConfig, train_sac_graphed
 
 
@@ -51,9 +55,22 @@ def main():
     agent = SAC(env.obs_dim, env.act_dim, cfg, device=dev, seed=0,
                 act_low=env.single_action_space.low, act_high=env.single_action_space.high)
 
+    def in_kernel_policy():
+        """The actor's deterministic action as an in-kernel policy, or None when its shape does not fit one."""
+        try:
+            return salp.MLPPolicy.from_actor(agent.actor)
+        except (ValueError, AttributeError):
+            return None
+
     def evaluate(tag, heading_seed=0):
-        pol = lambda o: agent.act(o, deterministic=True)
-        m = summarize(run_navigation_trials(pol, num_trials=100, device=dev, seed=123, heading_seed=heading_seed))
+        # the whole trial loop in one kernel launch when the actor fits the in-kernel policy, else one launch per step
+        mlp = in_kernel_policy()
+        if mlp is not None:
+            trials = run_navigation_trials_in_kernel(mlp, num_trials=100, device=dev, seed=123, heading_seed=heading_seed)
+        else:
+            pol = lambda o: agent.act(o, deterministic=True)
+            trials = run_navigation_trials(pol, num_trials=100, device=dev, seed=123, heading_seed=heading_seed)
+        m = summarize(trials)
         print(json.dumps({"eval": tag, **{k: round(float(v), 4) for k, v in m.items()}}), flush=True)
         return m
 
@@ -62,7 +79,7 @@ def main():
     best, best_sd = -1.0, None
 
     print(json.dumps({"eval": "scripted pursuit baseline",
-                      **{k: round(float(v), 4) for k, v in summarize(run_navigation_trials(pursuit_policy(), num_trials=100, device=dev, seed=123)).items()}}), flush=True)
+                      **{k: round(float(v), 4) for k, v in summarize(run_navigation_trials_in_kernel(pursuit_mlp(), num_trials=100, device=dev, seed=123)).items()}}), flush=True)
     evaluate("untrained policy")
     buf = DeviceReplayBuffer(cfg.buffer_size, env.obs_dim, env.act_dim, torch.device(dev))
     t0 = time.perf_counter()

@@ -376,6 +376,50 @@ enum { SALP_EVAL_RETURN = 0,        /* words 0-1: float64 */
        SALP_EVAL_FIRST_LENGTH = 4, SALP_EVAL_FIRST_END, SALP_EVAL_EPISODES, SALP_EVAL_FOOD, SALP_EVAL_WORDS /* 8 */ };
 int salp_vec_evaluate_policy(salp_vec_t* h, const salp_policy_t* pol, int32_t horizon, void* rec, uint32_t flags, void* stream);
 
+/* Navigation evaluation: fixed start -> goal trials (the reference's eval/collect_navigation_data.py :97-114) in ONE launch —
+ * the closed loop of salp_vec_rollout_policy with a per-env stop at the goal, NO per-step output but the optional track, and
+ * one path record per env, [n_envs][SALP_NAV_WORDS] 32-bit words (80 B per env; a device block must be 16-byte aligned).
+ *   line          double [n_envs][4]: start x, start y, goal x, goal y of each env's trial (the caller has put the envs at
+ *                 their starts with salp_vec_set_state; the start here only defines the line of the lateral deviation)
+ *   goal_radius   one double for the whole call
+ * An env is RUNNING while the reached bit of its record is clear.  An env that is not running is not stepped: its state rows,
+ * draw counter, statistics and record keep every bit.  After each step a running env takes, in fp64 with IEEE sqrt and
+ * division and no contraction — a host loop reproduces every bit — with (x, y) the state position after the step (wall clamp
+ * included) and (px, py) the one before it:
+ *   path_sum += sqrt((x-px)*(x-px) + (y-py)*(y-py))
+ *   lateral_sum += fabs((x-sx)*dny - (y-sy)*dnx),  (dnx, dny) = (gx-sx, gy-sy) / (sqrt((gx-sx)^2 + (gy-sy)^2) + 1e-12)
+ *   xmin = fmin(xmin, x) ... ymax = fmax(ymax, y);  steps += 1
+ *   status |= 2 if the step collided, |= 4 if it captured the food
+ *   status |= 1 if sqrt((x-gx)*(x-gx) + (y-gy)*(y-gy)) < goal_radius: the env stops running
+ * The goal is tested after a step only: an env that starts inside the radius still takes one step.  `terminated` /
+ * `truncated` do not end a trial (the reference's loop ignores them), hence the handle must have no_autoreset.
+ *   SALP_NAV_STEPS (word 0, int32)          steps taken
+ *   SALP_NAV_STATUS (word 1, int32)         bit 0 reached, bit 1 collided on a step taken, bit 2 captured the food
+ *   SALP_NAV_PATH (words 2-3, float64)      path_sum
+ *   SALP_NAV_LATERAL (words 4-5, float64)   lateral_sum over steps 1..steps (the term of the start itself is exactly 0)
+ *   SALP_NAV_XMIN, _XMAX, _YMIN, _YMAX (words 6-13, float64)   the bounding box of the positions, the entry position included
+ *   SALP_NAV_X, SALP_NAV_Y (words 14-17, float64)              the last position (= the state's)
+ *   words 18-19                             zero
+ * A fresh record: steps, status and the sums 0, the box and the last position the entry position.  flags: SALP_DEVICE_PTRS
+ * and / or SALP_EVAL_ACCUMULATE.  With SALP_EVAL_ACCUMULATE the records are read first and continued; a record with steps == 0
+ * and status == 0 counts as fresh — a run cut into several calls, or replayed from a captured graph, yields the bits of one
+ * call.  Without it the records are overwritten.
+ * track_or_null: double [horizon][n_envs][2], the position after each step of THIS call; a stopped env repeats its last one.
+ * Which observation the first action sees (the prologue's bit-exact row), and the policy assignment for P > 1, are those of
+ * salp_vec_rollout_policy; a Gaussian policy runs its mean.  The global step grows by `horizon`; salp_stats_t counts only the
+ * steps actually taken (env_steps grows by the sum of the records' step increments).  salp_vec_last_launch reports signature
+ * 5 with action source 2.  Host pointers: synchronous; device pointers: the call only launches kernels on `stream` (capturable).
+ * SALP_ERR_INVALID, with nothing launched and the handle unchanged, for a handle without no_autoreset, num_food_items != 1,
+ * free breathing, max_observed_food != 3, a NULL rec or line, horizon < 1, a radius that is not finite and positive, a flag bit
+ * other than those two, a device rec (or device line / track) that is not 16-byte aligned, or a policy of another handle. */
+enum { SALP_NAV_STEPS = 0, SALP_NAV_STATUS = 1,
+       SALP_NAV_PATH = 2, SALP_NAV_LATERAL = 4,                                  /* float64 each */
+       SALP_NAV_XMIN = 6, SALP_NAV_XMAX = 8, SALP_NAV_YMIN = 10, SALP_NAV_YMAX = 12,
+       SALP_NAV_X = 14, SALP_NAV_Y = 16, SALP_NAV_WORDS = 20 };
+enum { SALP_NAV_REACHED = 1, SALP_NAV_COLLIDED = 2, SALP_NAV_CAPTURED = 4 };   /* bits of SALP_NAV_STATUS */
+int salp_vec_evaluate_navigation(salp_vec_t* h, const salp_policy_t* pol, int32_t horizon, const double* line,
+                                 double goal_radius, void* rec, double* track_or_null, uint32_t flags, void* stream);
+
 /* Current observation of every env without stepping. obs float [n_envs][obs_dim]. */
 int salp_vec_observe(salp_vec_t* h, float* obs, uint32_t flags, void* stream);
 
@@ -407,15 +451,17 @@ int64_t salp_vec_global_step(const salp_vec_t* h);
  * output signature the kernel was compiled for: 1 = obs, reward, terminated, truncated and nothing else, 2 = those four plus
  * final_obs and / or info, 0 = some of the four is NULL (every store tested; always 0 for the generic instantiation's unpacked calls),
  * 3 = the packed record (both halves of a split launch and the generic instantiation too), 4 = the per-env summary record and
- * no per-step output (salp_vec_evaluate_policy: both halves; always with [5] == 2), [5] 1 = actions drawn in the kernel,
+ * no per-step output (salp_vec_evaluate_policy: both halves; always with [5] == 2), 5 = the navigation record
+ * (salp_vec_evaluate_navigation: both halves, always with [5] == 2), [5] 1 = actions drawn in the kernel,
  * 2 = actions computed by a policy in the kernel (salp_vec_rollout_policy, salp_vec_evaluate_policy), 3 = actions sampled
  * from a Gaussian policy in the kernel (salp_vec_rollout_policy_sampled, salp_vec_evaluate_policy_sampled: separate instantiations),
  * [6] envs served by the unpredicated launch (whole wavefronts), [7] envs served by the predicated launch.
  * [4] is the signature of the kernel that ran: the unpredicated launch's when there was one, else the predicated launch's
- * (predicated kernels exist for signatures 1, 3, 4 and 0 only: a call with final_obs / info runs them as 0). */
+ * (predicated kernels exist for signatures 1, 3, 4, 5 and 0 only: a call with final_obs / info runs them as 0). */
 int salp_vec_last_launch(const salp_vec_t* h, int64_t info[8]);
 /* The output signature of each half of that call: sig[0] the unpredicated launch, sig[1] the predicated launch, -1 for a
- * half that was not launched (or before any call); 4 in each launched half of a salp_vec_evaluate_policy call. */
+ * half that was not launched (or before any call); 4 in each launched half of a salp_vec_evaluate_policy call, 5 of a
+ * salp_vec_evaluate_navigation call. */
 int salp_vec_last_launch_signatures(const salp_vec_t* h, int64_t sig[2]);
 /* What that kernel (the unpredicated one when both were launched) holds per workgroup of 256 threads, from the runtime
  * (hipFuncGetAttributes, hipOccupancyMaxActiveBlocksPerMultiprocessor): info[0] registers per thread (VGPRs), [1] static LDS

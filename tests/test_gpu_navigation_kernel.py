@@ -1,0 +1,460 @@
+"""salp_vec_evaluate_navigation on the GPU: fixed start -> goal trials in one launch, each env stopping at its goal, one
+80-byte path record per env (include/salp_vec.h "Navigation evaluation").  Run with `pytest -m gpu`.
+
+The yardstick is the GPU's own stepwise run from the same set_state snapshot: 640 calls of salp_vec_rollout_policy with
+horizon 1 and salp_vec_get_state after each, which gives the fp64 positions, every per-step state and the collision /
+capture flags.  The record must equal `policy.navigation_record` of those positions in every bit, the final state rows
+the stepwise state at each env's stop step, the track the positions with frozen tails.
+
+Two geometries (navigation_config(), seed 3, headings from default_rng(1), goals from the same generator after the headings,
+pursuit_mlp(3.0)): `centre` starts at (400, 300) with the goal on the circle of radius 130 (goal radius 50), `corner` starts
+at (110, 110) with the goal uniform in [180, 320]^2 (goal radius 40; some envs meet the walls)."""
+import functools
+
+import numpy as np
+import pytest
+
+import oracle_lib as ol
+from underwater_swimmer_rl_amd import _capi
+from underwater_swimmer_rl_amd._capi import SalpError, SalpLib
+from underwater_swimmer_rl_amd import policy as pol
+from underwater_swimmer_rl_amd.navigation_eval import (metrics_from_record, navigation_config, navigation_metrics, pursuit_mlp,
+                                                       run_navigation_trials_in_kernel, summarize)
+
+pytestmark = pytest.mark.gpu
+
+H = 640
+SEED = 3
+DEV, ACC = _capi.SALP_DEVICE_PTRS, _capi.EVAL_ACCUMULATE
+W = _capi.NAV_WORDS
+SENTINEL = 0xA5C3F00D
+GEOMETRY = {"centre": dict(start=(400.0, 300.0), radius=50.0), "corner": dict(start=(110.0, 110.0), radius=40.0)}
+# (geometry, envs, tank width): 192 = three full wavefronts, the unpredicated kernel; 100 and 229 = ragged counts, which at
+# 640 steps run as ONE predicated launch like their twins (n * horizon <= 2^22: launch_rollout) — the split into an unpredicated
+# and a predicated launch is test_split_launch_equals_the_predicated_kernel_in_pieces; width 900 = the kernels that read
+# their constants at run time
+RUNS = [("centre", 192, 800), ("corner", 192, 800), ("corner", 100, 800), ("centre", 229, 800), ("centre", 192, 900)]
+
+
+def snapshot(geometry, n, width):
+    cfg = navigation_config(width=width)
+    g = GEOMETRY[geometry]
+    rng = np.random.default_rng(1)
+    theta = rng.uniform(-np.pi, np.pi, n)
+    if geometry == "centre":
+        ang = rng.uniform(0.0, 2.0 * np.pi, n)
+        goal = np.stack([g["start"][0] + 130.0 * np.cos(ang), g["start"][1] + 130.0 * np.sin(ang)], axis=1)
+    else:
+        goal = rng.uniform(180.0, 320.0, (n, 2))
+    dev = SalpLib(cfg, n, device_id=0, seed=SEED)
+    f64, i32 = device_state(dev, cfg)
+    dev.close()
+    f64[_capi.F_X], f64[_capi.F_Y] = g["start"]
+    f64[_capi.F_VX] = f64[_capi.F_VY] = f64[_capi.F_OMEGA] = 0.0
+    f64[_capi.F_THETA] = theta
+    f64[_capi.F_FOOD0], f64[_capi.F_FOOD0 + 1] = goal[:, 0], goal[:, 1]
+    i32[_capi.I_STEPS_SINCE_FOOD] = 0
+    line = np.ascontiguousarray(np.concatenate([np.broadcast_to(np.array(g["start"]), (n, 2)), goal], axis=1))
+    return cfg, f64, i32, line, g["radius"]
+
+
+def device_state(dev, cfg):
+    f64 = np.empty((_capi.F_FOOD0 + 2 * cfg.num_food_items, dev.n_envs), np.float64)
+    i32 = np.empty((_capi.I_COUNT, dev.n_envs), np.int32)
+    dev.get_state(f64, i32, 0)
+    return f64, i32
+
+
+def same_state(a, b):
+    return np.array_equal(a[0], b[0], equal_nan=True) and np.array_equal(a[1], b[1])
+
+
+def started(cfg, n, f64, i32):
+    dev = SalpLib(cfg, n, device_id=0, seed=SEED)
+    dev.set_state(f64, i32, 0)
+    return dev
+
+
+def junk(n):
+    return np.full((n, W), np.int32(0x5A5A5A5A), np.int32)       # a call without ACCUMULATE overwrites it
+
+
+def record_diff(got, want):
+    """'' when the two record blocks are identical bit for bit, else which fields differ and where first."""
+    if np.array_equal(got, want):
+        return ""
+    g, w = pol.navigation_views(np.ascontiguousarray(got)), pol.navigation_views(np.ascontiguousarray(want))
+    bad = []
+    for k in ("steps", "status", "path_sum", "lateral_sum", "xmin", "xmax", "ymin", "ymax", "x", "y"):
+        ty = np.int64 if g[k].dtype == np.float64 else np.int32
+        same = g[k].view(ty) == w[k].view(ty)
+        if not same.all():
+            i = int(np.argmin(same))
+            bad.append(f"{k}: {int((~same).sum())} envs, first env {i}: {g[k][i]!r} != {w[k][i]!r}")
+    if not np.array_equal(got[:, 18:], want[:, 18:]):
+        bad.append("words 18-19")
+    return "; ".join(bad)
+
+
+def collisions_of(cfg, F):
+    """snake:219-230 on the states the steps left: the wall test with the step's own max(ellipse_a, ellipse_b)."""
+    x, y = F[:, _capi.F_X], F[:, _capi.F_Y]
+    r = np.maximum(F[:, _capi.F_ELLIPSE_A], F[:, _capi.F_ELLIPSE_B])
+    m = cfg.tank_margin
+    return (x - r <= m) | (x + r >= cfg.width - m) | (y - r <= m) | (y + r >= cfg.height - m)
+
+
+@functools.lru_cache(maxsize=None)
+def stepwise(geometry, n, width, gains=(3.0,)):
+    """The yardstick, computed once per run, shared, read-only: one step per launch with the state read back after each."""
+    import torch
+    cfg, f64, i32, line, radius = snapshot(geometry, n, width)
+    policy = pursuit_mlp(gains[0]) if len(gains) == 1 else pol.MLPPolicy.stack([pursuit_mlp(g) for g in gains])
+    dev = started(cfg, n, f64, i32)
+    ph = dev.policy_create(policy)
+    F = torch.empty((H + 1, f64.shape[0], n), dtype=torch.float64, device="cuda:0")
+    I = torch.empty((H + 1, i32.shape[0], n), dtype=torch.int32, device="cuda:0")
+    obs = torch.empty((1, n, cfg.obs_dim), dtype=torch.float32, device="cuda:0")
+    rew = torch.empty((1, n), dtype=torch.float32, device="cuda:0")
+    term = torch.empty((H, n), dtype=torch.uint8, device="cuda:0")
+    trunc = torch.empty((H, n), dtype=torch.uint8, device="cuda:0")
+    act = torch.empty((H, n, 1), dtype=torch.float32, device="cuda:0")
+    torch.cuda.synchronize()
+    dev.get_state(F[0], I[0], DEV, 0)
+    for t in range(H):
+        dev.rollout_policy(ph, 1, obs, rew, term[t], trunc[t], act[t], DEV, 0)
+        dev.get_state(F[t + 1], I[t + 1], DEV, 0)
+    torch.cuda.synchronize()
+    F, I, act = F.cpu().numpy(), I.cpu().numpy(), act.cpu().numpy()
+    stats = dev.stats()
+    ph.close()
+    dev.close()
+    assert same_state((F[0], I[0]), (f64, i32))
+    pos = np.ascontiguousarray(np.stack([F[:, _capi.F_X], F[:, _capi.F_Y]], axis=2))            # [H + 1, n, 2]
+    col = collisions_of(cfg, F[1:])
+    cap = np.diff(I[:, _capi.I_FOOD_COLLECTED], axis=0) > 0
+    assert int(col.sum()) == stats["collisions"] and int(cap.sum()) == stats["food_collected"], "the flags read off the states"
+    want = pol.navigation_record(pos, None, line, radius, collided=col, captured=cap)
+    stop = pol.navigation_views(want)["steps"].astype(np.int64)
+    tt = np.minimum(np.arange(1, H + 1)[:, None], stop[None, :])                                  # [H, n]
+    track = pos[tt, np.arange(n)[None, :]]
+    end = (F[stop, :, np.arange(n)].T.copy(), I[stop, :, np.arange(n)].T.copy())
+    out = dict(cfg=cfg, f64=f64, i32=i32, line=line, radius=radius, policy=policy, F=F, I=I, act=act, pos=pos, col=col, cap=cap,
+               want=want, stop=stop, track=track, end=end)
+    for a in (f64, i32, line, F, I, act, pos, col, cap, want, stop, track, *end):
+        a.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def one_call(geometry, n, width, gains=(3.0,)):
+    """salp_vec_evaluate_navigation, 640 steps in one call with host pointers, from the same snapshot."""
+    r = stepwise(geometry, n, width, gains)
+    dev = started(r["cfg"], n, r["f64"], r["i32"])
+    ph = dev.policy_create(r["policy"])
+    rec, track = junk(n), np.full((H, n, 2), np.nan)
+    step0, stats0 = dev.global_step, dev.stats()
+    dev.evaluate_navigation(ph, H, r["line"], r["radius"], rec, track, 0)
+    out = dict(rec=rec, track=track, state=device_state(dev, r["cfg"]), stats=dev.stats(), step=dev.global_step,
+               launch=dev.last_launch(), res=dev.last_kernel_resources())
+    ph.close()
+    dev.close()
+    assert step0 == 0 and stats0["env_steps"] == 0
+    for a in (rec, track, *out["state"]):
+        a.setflags(write=False)
+    return out
+
+
+@pytest.mark.parametrize("geometry,n,width", RUNS)
+def test_record_state_and_track_equal_the_stepwise_run(geometry, n, width):
+    r, o = stepwise(geometry, n, width), one_call(geometry, n, width)
+    v = pol.navigation_views(np.array(o["rec"]))
+    reached = (v["status"] & pol.NAV_REACHED) != 0
+    print(f"{geometry} n={n} width={width}: reached {reached.mean():.2f}, stop steps {v['steps'][reached].min() if reached.any() else '-'}"
+          f"..{v['steps'].max()}, collided {int(((v['status'] & pol.NAV_COLLIDED) != 0).sum())}, launch {o['launch']}, resources {o['res']}")
+    assert record_diff(o["rec"], r["want"]) == ""
+    assert np.array_equal(o["rec"], r["want"])                          # every word
+    assert same_state(o["state"], r["end"]), "final state rows differ from the stepwise state at the stop step"
+    assert np.array_equal(o["track"].view(np.int64), r["track"].view(np.int64)), "track"
+    # the call's bookkeeping: signature 5, the in-kernel policy, both launch forms as the env count asks
+    ll = o["launch"]
+    assert ll["full_signature"] == 5 and ll["actions_in_kernel"] == 2 and ll["food_slots"] == 1 and ll["forced"] == 1
+    assert ll["literal_constants"] == (1 if width == 800 else 0)
+    n_full = n // 64 * 64 if (n % 64 == 0 or n * H > 1 << 22) else 0      # the rule of salp_vec_rollout_policy
+    assert (ll["envs_unpredicated"], ll["envs_predicated"]) == (n_full, n - n_full)
+    assert ll["signature_unpredicated"] == (5 if n_full else -1) and ll["signature_predicated"] == (5 if n - n_full else -1)
+    assert o["step"] == H
+    assert o["stats"]["env_steps"] == int(v["steps"].sum())
+    assert o["stats"]["collisions"] == int(r["col"][np.arange(H)[:, None] < r["stop"][None, :]].sum())
+    assert o["res"]["scratch_bytes"] == 0, o["res"]                     # DESIGN.md 3.1 "Navigation signature"
+
+
+@pytest.mark.parametrize("geometry", ["centre", "corner"])
+def test_the_check_can_fail(geometry):
+    """Both kinds of env in numbers, many different stop steps, and both kinds inside one wavefront."""
+    r = stepwise(geometry, 192, 800)
+    v = pol.navigation_views(np.array(r["want"]))
+    reached = (v["status"] & pol.NAV_REACHED) != 0
+    assert reached.mean() >= 0.10 and (~reached).mean() >= 0.10, reached.mean()
+    assert len(np.unique(v["steps"][reached])) >= 8
+    assert (v["steps"][~reached] == H).all() and (v["steps"][reached] >= 1).all()
+    assert any(reached[w:w + 64].any() and not reached[w:w + 64].all() for w in range(0, 192, 64))
+    if geometry == "corner":
+        assert int(((v["status"] & pol.NAV_COLLIDED) != 0).sum()) >= 10
+
+
+@pytest.mark.parametrize("geometry,n,width", [("corner", 192, 800), ("corner", 100, 800)])    # (corner: some envs arrive before step 250)
+def test_accumulation_and_statistics(geometry, n, width):
+    r, o = stepwise(geometry, n, width), one_call(geometry, n, width)
+    A, B = 250, 390
+    dev = started(r["cfg"], n, r["f64"], r["i32"])
+    ph = dev.policy_create(r["policy"])
+    rec = np.zeros((n, W), np.int32)
+    ta, tb = np.full((A, n, 2), np.nan), np.full((B, n, 2), np.nan)
+    dev.evaluate_navigation(ph, A, r["line"], r["radius"], rec, ta, ACC)
+    mid_rec, mid_state, mid_stats = rec.copy(), device_state(dev, r["cfg"]), dev.stats()
+    want_mid = pol.navigation_record(r["pos"][:A + 1], None, r["line"], r["radius"], collided=r["col"][:A], captured=r["cap"][:A])
+    assert record_diff(mid_rec, want_mid) == ""
+    assert mid_stats["env_steps"] == int(pol.navigation_views(mid_rec)["steps"].sum())
+    dev.evaluate_navigation(ph, B, r["line"], r["radius"], rec, tb, ACC)
+    end_state = device_state(dev, r["cfg"])
+    assert record_diff(rec, o["rec"]) == "", "250 + 390 steps with SALP_EVAL_ACCUMULATE != 640 in one call"
+    assert same_state(end_state, o["state"])
+    assert np.array_equal(np.concatenate([ta, tb]).view(np.int64), o["track"].view(np.int64))
+    # an env that had reached its goal in the first call: nothing of it moves in the second (draw counter included)
+    done = (pol.navigation_views(mid_rec)["status"] & pol.NAV_REACHED) != 0
+    assert done.sum() >= 1 and (~done).sum() >= 1
+    assert np.array_equal(end_state[0][:, done], mid_state[0][:, done], equal_nan=True)
+    assert np.array_equal(end_state[1][:, done], mid_state[1][:, done])
+    assert np.array_equal(rec[done], mid_rec[done])
+    assert dev.stats()["env_steps"] == int(pol.navigation_views(rec)["steps"].sum()) == o["stats"]["env_steps"]
+    # every count is that of the one call; the reward total is a sum of per-wavefront, per-call sums each rounded to 2^-20
+    # (SALP_FIXED_SCALE), so the two runs may differ by one such unit per wavefront sum: (n + 63) // 64 wavefronts x 3 calls
+    got, one = dev.stats(), o["stats"]
+    assert {k: v for k, v in got.items() if k != "reward_sum"} == {k: v for k, v in one.items() if k != "reward_sum"}
+    assert abs(got["reward_sum"] - one["reward_sum"]) <= 3 * ((n + 63) // 64) * 2.0 ** -20
+    assert dev.global_step == H
+    ph.close()
+    dev.close()
+
+
+def test_split_launch_equals_the_predicated_kernel_in_pieces():
+    """6629 envs x 640 steps is past the size up to which a ragged batch runs as one predicated launch: 6592 envs go to the
+    unpredicated kernel, 37 to the predicated one, both writing one record block and one track.  The same run cut into
+    320 + 320 steps is two predicated launches over all envs: every word must agree."""
+    n, A = 6629, 320
+    assert n * H > 1 << 22 >= n * A
+    cfg, f64, i32, line, radius = snapshot("corner", n, 800)
+    policy = pursuit_mlp(3.0)
+    whole, pieces = started(cfg, n, f64, i32), started(cfg, n, f64, i32)
+    ph_w, ph_p = whole.policy_create(policy), pieces.policy_create(policy)
+    rec_w, rec_p = junk(n), np.zeros((n, W), np.int32)
+    tr_w, tr_a, tr_b = np.full((H, n, 2), np.nan), np.full((A, n, 2), np.nan), np.full((H - A, n, 2), np.nan)
+    whole.evaluate_navigation(ph_w, H, line, radius, rec_w, tr_w, 0)
+    ll = whole.last_launch()
+    assert (ll["envs_unpredicated"], ll["envs_predicated"]) == (6592, 37)
+    assert (ll["signature_unpredicated"], ll["signature_predicated"]) == (5, 5)
+    pieces.evaluate_navigation(ph_p, A, line, radius, rec_p, tr_a, ACC)
+    first = pieces.last_launch()
+    assert (first["envs_unpredicated"], first["envs_predicated"]) == (0, n)
+    pieces.evaluate_navigation(ph_p, H - A, line, radius, rec_p, tr_b, ACC)
+    assert record_diff(rec_w, rec_p) == ""
+    assert np.array_equal(tr_w.view(np.int64), np.concatenate([tr_a, tr_b]).view(np.int64))
+    assert same_state(device_state(whole, cfg), device_state(pieces, cfg))
+    v = pol.navigation_views(rec_w)
+    reached = (v["status"] & pol.NAV_REACHED) != 0
+    assert 0.1 <= reached.mean() <= 0.9 and reached[6592:].any() and not reached[6592:].all()
+    sw, sp = whole.stats(), pieces.stats()          # (the reward total: one 2^-20 unit per wavefront sum, as above)
+    assert {k: x for k, x in sw.items() if k != "reward_sum"} == {k: x for k, x in sp.items() if k != "reward_sum"}
+    assert abs(sw["reward_sum"] - sp["reward_sum"]) <= 3 * ((n + 63) // 64) * 2.0 ** -20
+    assert sw["env_steps"] == int(v["steps"].sum())
+    for h in (ph_w, ph_p):
+        h.close()
+    for d in (whole, pieces):
+        d.close()
+
+
+def test_populations():
+    """P = 3 over 192 envs: group k is a single-policy run of policy k on those envs."""
+    gains = (3.0, 1.5, 6.0)
+    o = one_call("corner", 192, 800, gains)
+    r = stepwise("corner", 192, 800, gains)
+    assert record_diff(o["rec"], r["want"]) == "" and same_state(o["state"], r["end"])
+    differ = 0
+    for k, g in enumerate(gains):
+        single = one_call("corner", 192, 800, (g,))
+        sl = slice(64 * k, 64 * (k + 1))
+        assert record_diff(o["rec"][sl], single["rec"][sl]) == "", f"group {k}"
+        assert np.array_equal(o["track"][:, sl].view(np.int64), single["track"][:, sl].view(np.int64))
+        assert np.array_equal(o["state"][0][:, sl], single["state"][0][:, sl], equal_nan=True)
+        assert np.array_equal(o["state"][1][:, sl], single["state"][1][:, sl])
+        other = one_call("corner", 192, 800, (gains[(k + 1) % 3],))
+        differ += int(not np.array_equal(o["rec"][sl], other["rec"][sl]))
+    assert differ == 3, "the three policies must not be interchangeable on these envs"
+
+
+@pytest.mark.parametrize("geometry", ["centre", "corner"])
+def test_metrics_against_the_oracle(geometry):
+    """The CPU oracle stepped on the actions the stepwise run took; navigation_metrics of its fp64 positions."""
+    n = 192
+    r, o = stepwise(geometry, n, 800), one_call(geometry, n, 800)
+    orc = ol.OracleVec(r["cfg"], n, seed=SEED)
+    orc.set_state(r["f64"], r["i32"])
+    pos = np.empty((H + 1, n, 2))
+    pos[0] = r["pos"][0]
+    for t in range(H):
+        orc.rollout(r["act"][t:t + 1], light=True)
+        s = orc.get_state()[0]
+        pos[t + 1, :, 0], pos[t + 1, :, 1] = s[_capi.F_X], s[_capi.F_Y]
+    orc.close()
+    goal = r["line"][:, 2:]
+    dist = np.linalg.norm(pos[1:] - goal[None], axis=2)                  # [H, n]
+    inside = dist < r["radius"]
+    steps = np.where(inside.any(axis=0), inside.argmax(axis=0) + 1, H)
+    taken = np.arange(H)[:, None] < steps[None, :]
+    unclear = (np.abs(dist - r["radius"]) < 1e-6) & taken
+    keep = ~unclear.any(axis=0)
+    assert (~keep).sum() <= n // 100, "at most 1 % of the envs may be left out"
+    m = metrics_from_record(pol.navigation_views(np.array(o["rec"])), r["line"], r["radius"])
+    frozen = pos[np.minimum(np.arange(H + 1)[:, None], steps[None, :]), np.arange(n)[None, :]]
+    worst = {}
+    for i in np.flatnonzero(keep):
+        ref = navigation_metrics(frozen[:, i:i + 1], steps[i:i + 1], r["line"][i, :2], goal[i], r["radius"])
+        assert m["steps"][i] == ref["steps"][0] and m["success"][i] == ref["success"][0], i
+        for k in ("path_length", "lateral_deviation", "x_range", "y_range", "final_distance"):
+            err = abs(m[k][i] - ref[k][0]) / max(abs(ref[k][0]), 1e-300) if ref[k][0] != 0 else abs(m[k][i])
+            worst[k] = max(worst.get(k, 0.0), err)
+    print(f"{geometry}: left out {int((~keep).sum())}, worst relative differences {worst}")
+    for k, e in worst.items():
+        assert e <= 1e-9, (k, e)
+
+
+def test_device_pointers_guard_words_and_graph_replays():
+    import torch
+    geometry, n = "centre", 192
+    r, o = stepwise(geometry, n, 800), one_call(geometry, n, 800)
+    sent = int(np.uint32(SENTINEL).view(np.int32))
+    G = 64                                                       # guard words (256 B: alignment kept)
+    dev = started(r["cfg"], n, r["f64"], r["i32"])
+    ph = dev.policy_create(r["policy"])
+    block = torch.full((G + n * W + G,), sent, dtype=torch.int32, device="cuda:0")
+    tblock = torch.full((G + H * n * 2 + G,), -7.25, dtype=torch.float64, device="cuda:0")
+    rec, track = block[G:G + n * W], tblock[G:G + H * n * 2]
+    line = torch.tensor(r["line"], device="cuda:0")
+    assert rec.data_ptr() % 16 == 0 and track.data_ptr() % 16 == 0
+    torch.cuda.synchronize()
+    dev.evaluate_navigation(ph, H, line, r["radius"], rec, track, DEV, 0)
+    torch.cuda.synchronize()
+    host, thost = block.cpu().numpy(), tblock.cpu().numpy()
+    assert (host[:G].view(np.uint32) == SENTINEL).all() and (host[G + n * W:].view(np.uint32) == SENTINEL).all(), "rec guard words written"
+    assert (thost[:G] == -7.25).all() and (thost[G + H * n * 2:] == -7.25).all(), "track guard words written"
+    assert record_diff(host[G:G + n * W].reshape(n, W), o["rec"]) == ""
+    assert np.array_equal(thost[G:G + H * n * 2].reshape(H, n, 2).view(np.int64), o["track"].view(np.int64))
+    assert same_state(device_state(dev, r["cfg"]), o["state"])
+    ph.close()
+    dev.close()
+    # a captured graph of one 160-step accumulate call, replayed four times
+    K = 160
+    assert 4 * K == H
+    graphed = started(r["cfg"], n, r["f64"], r["i32"])
+    ph_g = graphed.policy_create(r["policy"])
+    grec = torch.zeros((n, W), dtype=torch.int32, device="cuda:0")
+    gtrack = torch.zeros((K, n, 2), dtype=torch.float64, device="cuda:0")
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        graphed.evaluate_navigation(ph_g, K, line, r["radius"], grec, gtrack, DEV | ACC, int(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    assert same_state(device_state(graphed, r["cfg"]), (r["f64"], r["i32"])), "capture must not execute"
+    assert not grec.any() and graphed.global_step == K
+    for _ in range(4):
+        g.replay()
+    torch.cuda.synchronize()
+    assert record_diff(grec.cpu().numpy(), o["rec"]) == "", "four replays of 160 steps != one call of 640"
+    assert same_state(device_state(graphed, r["cfg"]), o["state"])
+    assert np.array_equal(gtrack.cpu().numpy().view(np.int64), o["track"][3 * K:].view(np.int64))    # the last replay's rows
+    assert graphed.stats()["env_steps"] == o["stats"]["env_steps"]
+    ph_g.close()
+    graphed.close()
+
+
+def test_refusals_leave_the_handle_unchanged():
+    import torch
+    n = 128
+    cfg, f64, i32, line, radius = snapshot("centre", n, 800)
+    dev = started(cfg, n, f64, i32)
+    policy = pursuit_mlp(3.0)
+    ph = dev.policy_create(policy)
+    sent = int(np.uint32(SENTINEL).view(np.int32))
+    block = torch.full((n * W + 8,), sent, dtype=torch.int32, device="cuda:0")
+    drec = block[:n * W]
+    dline = torch.tensor(line, device="cuda:0")
+    torch.cuda.synchronize()
+    rec = np.zeros((n, W), np.int32)
+    before, step0, stats0 = device_state(dev, cfg), dev.global_step, dev.stats()
+
+    def unchanged(d=dev, c=cfg, b=before, s=step0, st=stats0):
+        return same_state(device_state(d, c), b) and d.global_step == s and d.stats() == st
+
+    good = dict(handle=ph, horizon=2, line=line, goal_radius=radius, rec=rec, track=None, flags=0)
+    refusals = [
+        ("NULL rec", dict(rec=None)), ("NULL rec (device)", dict(rec=None, line=dline, flags=DEV)), ("NULL line", dict(line=None)),
+        ("horizon 0", dict(horizon=0)), ("negative horizon", dict(horizon=-5, flags=ACC)),
+        ("zero radius", dict(goal_radius=0.0)), ("negative radius", dict(goal_radius=-50.0)),
+        ("infinite radius", dict(goal_radius=float("inf"))), ("NaN radius", dict(goal_radius=float("nan"))),
+        ("the packed record's flag", dict(flags=_capi.REC_FINAL_OBS)), ("an unknown flag", dict(flags=8)),
+        ("an unknown flag next to the known ones", dict(rec=drec, line=dline, flags=DEV | ACC | 0x100)),
+        ("misaligned device rec (4 B)", dict(rec=drec.data_ptr() + 4, line=dline, flags=DEV)),
+        ("misaligned device rec (8 B)", dict(rec=drec.data_ptr() + 8, line=dline, flags=DEV | ACC)),
+    ]
+    for label, kw in refusals:
+        with pytest.raises(SalpError, match=r"\(-1\)"):
+            dev.evaluate_navigation(**{**good, **kw})
+        assert unchanged(), label
+    # a policy of another handle, and the handles the call does not serve — each with a policy of its own where one can exist
+    twin = SalpLib(cfg, n, device_id=0, seed=1)
+    ph_twin = twin.policy_create(policy)
+    with pytest.raises(SalpError, match=r"\(-1\)"):
+        dev.evaluate_navigation(**{**good, "handle": ph_twin})
+    assert unchanged(), "policy of another handle"
+    two_d = pol.MLPPolicy.linear(np.zeros((2, 24), np.float32), None, out="clip")
+    others = [("autoreset", navigation_config(no_autoreset=False), policy), ("two foods", navigation_config(num_food_items=2), policy),
+              ("no food", navigation_config(num_food_items=0), policy), ("free breathing", navigation_config(forced_breathing=False), two_d),
+              ("max_observed_food 2", navigation_config(max_observed_food=2), None)]
+    for label, c, p in others:
+        d = SalpLib(c, n, device_id=0, seed=1)
+        h = d.policy_create(p) if p is not None else ph_twin     # (no policy can be made on a handle that observes 2 foods)
+        b, s, st = device_state(d, c), d.global_step, d.stats()
+        with pytest.raises(SalpError, match=r"\(-1\)"):
+            d.evaluate_navigation(h, 2, line, radius, rec, None, 0)
+        assert unchanged(d, c, b, s, st), label
+        if p is not None:
+            h.close()
+        d.close()
+    torch.cuda.synchronize()
+    assert (block.cpu().numpy().view(np.uint32) == SENTINEL).all() and not rec.any()
+    # a misaligned HOST record is fine (it is staged), and the handle still works
+    raw = np.zeros(n * W + 1, np.int32)
+    dev.evaluate_navigation(ph, 2, line, radius, raw[1:].reshape(n, W), None, 0)
+    assert dev.global_step == step0 + 2 and (pol.navigation_views(raw[1:].reshape(n, W).copy())["steps"] == 2).all()
+    assert dev.stats()["env_steps"] == 2 * n
+    ph.close()
+    ph_twin.close()
+    dev.close()
+    twin.close()
+
+
+def test_whole_protocol_in_one_launch():
+    from underwater_swimmer_rl_amd import SalpVectorEnv
+    env = SalpVectorEnv(navigation_config(), 256, device="cuda:0", seed=3)
+    m = run_navigation_trials_in_kernel(pursuit_mlp(), num_trials=256, max_steps=3000, heading_seed=1, env=env)
+    s = summarize(m)
+    print("pursuit baseline, in kernel:", {k: round(v, 3) if isinstance(v, float) else v for k, v in s.items()})
+    assert s["success_rate"] > 0.5, s
+    assert np.isfinite(m["path_ratio"]).all() and (m["path_ratio"][m["success"]] >= 0.89).all()
+    assert (m["steps"] <= 3000).all() and (m["steps"][m["success"]] < 3000).all()
+    assert np.isfinite(m["spline_path_ratio"][m["success"]]).all() and m["collided"].dtype == bool
+    ll = env._lib.last_launch()
+    assert ll["full_signature"] == 5 and ll["actions_in_kernel"] == 2
+    assert env._lib.stats()["env_steps"] == int(m["steps"].sum())
+    env.close()

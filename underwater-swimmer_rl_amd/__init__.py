@@ -22,7 +22,8 @@ def __getattr__(name):  # lazy: the pieces below need torch / the HIP library
     if name in ("record_width", "unpack_record", "pack_record"):
         from . import records
         return getattr(records, name)
-    if name in ("MLPPolicy", "GaussianPolicy", "pursuit_policy", "summarize_rollout", "evaluation_views"):
+    if name in ("MLPPolicy", "GaussianPolicy", "pursuit_policy", "summarize_rollout", "evaluation_views", "navigation_views",
+                "navigation_record"):
         from . import policy
         return getattr(policy, name)
     if name in ("SalpLib", "load_library", "SalpError", "PolicyHandle"):

@@ -23,6 +23,10 @@ REC_REWARD, REC_FLAGS, REC_FOOD_COLLECTED, REC_STEPS_SINCE_FOOD, REC_EXTRA_COLS 
 # per-env summary record of salp_vec_evaluate_policy (include/salp_vec.h "Policy evaluation"; views: policy.evaluation_views)
 EVAL_ACCUMULATE = 4         # call flag next to SALP_DEVICE_PTRS
 EVAL_RETURN, EVAL_FIRST_RETURN, EVAL_FIRST_LENGTH, EVAL_FIRST_END, EVAL_EPISODES, EVAL_FOOD, EVAL_WORDS = 0, 2, 4, 5, 6, 7, 8
+# per-env navigation record of salp_vec_evaluate_navigation (include/salp_vec.h "Navigation evaluation"; views: policy.navigation_views)
+(NAV_STEPS, NAV_STATUS, NAV_PATH, NAV_LATERAL, NAV_XMIN, NAV_XMAX, NAV_YMIN, NAV_YMAX, NAV_X, NAV_Y,
+ NAV_WORDS) = 0, 1, 2, 4, 6, 8, 10, 12, 14, 16, 20
+NAV_REACHED, NAV_COLLIDED, NAV_CAPTURED = 1, 2, 4     # bits of NAV_STATUS
 # snapshot rows (include/salp_vec.h)
 F_X, F_Y, F_VX, F_VY, F_THETA, F_OMEGA, F_NOZZLE, F_WATER, F_ELLIPSE_A, F_ELLIPSE_B, F_FOOD0 = range(11)
 (I_PHASE, I_TIMER, I_EXHALE_DUR, I_SHAPE_HOLD, I_STEPS_SINCE_FOOD, I_FOOD_COLLECTED, I_RNG_COUNTER,
@@ -37,7 +41,7 @@ EXPORTS = (
     "salp_vec_reseed", "salp_vec_last_launch", "salp_vec_last_kernel_resources", "salp_vec_last_launch_signatures",
     "salp_vec_record_width", "salp_vec_step_packed", "salp_vec_rollout_packed",
     "salp_policy_words", "salp_policy_create", "salp_policy_update", "salp_policy_destroy", "salp_vec_rollout_policy",
-    "salp_vec_evaluate_policy",
+    "salp_vec_evaluate_policy", "salp_vec_evaluate_navigation",
     "salp_policy_words_gaussian", "salp_policy_create_gaussian", "salp_policy_set_noise_step", "salp_policy_noise_step",
     "salp_vec_rollout_policy_sampled", "salp_vec_evaluate_policy_sampled",
 )
@@ -121,6 +125,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         L.salp_vec_rollout_policy.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, u32, vp]
     if path is None or hasattr(L, "salp_vec_evaluate_policy"):
         L.salp_vec_evaluate_policy.argtypes = [vp, vp, i32, vp, u32, vp]
+    if path is None or hasattr(L, "salp_vec_evaluate_navigation"):
+        L.salp_vec_evaluate_navigation.argtypes = [vp, vp, i32, vp, ctypes.c_double, vp, vp, u32, vp]
     if path is None or hasattr(L, "salp_vec_rollout_policy_sampled"):
         from .policy import CPolicyDesc
         L.salp_policy_words_gaussian.argtypes = [vp, ctypes.POINTER(CPolicyDesc)]
@@ -261,6 +267,13 @@ class SalpLib:
         check(self.lib, self.lib.salp_vec_evaluate_policy(self._h, handle._p, int(horizon), self._ptr(rec), flags,
                                                           ctypes.c_void_p(stream)), "salp_vec_evaluate_policy")
 
+    def evaluate_navigation(self, handle: "PolicyHandle", horizon, line, goal_radius, rec, track, flags, stream=0):
+        """salp_vec_evaluate_navigation: line float64 [n, 4] (start x, y, goal x, y), rec int32 [n, NAV_WORDS], track float64
+        [horizon, n, 2] or None; flags: SALP_DEVICE_PTRS and / or EVAL_ACCUMULATE (continue the records in `rec`)."""
+        check(self.lib, self.lib.salp_vec_evaluate_navigation(self._h, handle._p, int(horizon), self._ptr(line), float(goal_radius),
+                                                              self._ptr(rec), self._ptr(track), flags, ctypes.c_void_p(stream)),
+              "salp_vec_evaluate_navigation")
+
     def rollout_policy_sampled(self, handle: "PolicyHandle", horizon, obs, reward, term, trunc, act_out, logp_out, flags, stream=0):
         """salp_vec_rollout_policy_sampled: a Gaussian policy's sampled actions; act_out and logp_out may be None."""
         check(self.lib, self.lib.salp_vec_rollout_policy_sampled(self._h, handle._p, int(horizon), self._ptr(obs), self._ptr(reward),
@@ -298,7 +311,8 @@ class SalpLib:
     def last_launch(self) -> dict:
         """The kernel instantiation of the most recent step / rollout call (salp_vec_last_launch).  `full_signature`: 1 = the four
         main outputs only, 2 = the four plus final_obs / info, 3 = the packed record (step_packed / rollout_packed, every
-        instantiation), 4 = the per-env summary record and no per-step output (evaluate_policy), 0 = every store tested (some main output absent, the generic instantiation, or a predicated launch
+        instantiation), 4 = the per-env summary record and no per-step output (evaluate_policy),
+        5 = the navigation record (evaluate_navigation), 0 = every store tested (some main output absent, the generic instantiation, or a predicated launch
         asked for final_obs / info) — of the kernel that ran: the unpredicated launch's
         when there was one, else the predicated launch's.  `signature_unpredicated` / `signature_predicated`: each half's own,
         -1 for a half that was not launched (salp_vec_last_launch_signatures)."""

@@ -13,7 +13,7 @@
 // No MFMA: there is no dense contraction on this path; the bound is HBM write bandwidth.
 //
 // The template is instantiated implicitly, by the small salp_rollout_*.hip units next to this file: one per food-slot count
-// and literal / run-time constants for K = 3, one for the generic-K kernels, so that the 356 instantiations compile in
+// and literal / run-time constants for K = 3, one for the generic-K kernels, so that the 360 instantiations compile in
 // parallel.  Each unit defines the rollout_unit_fn of its handle class (the generic unit: of its two); salp_vec.hip (the
 // service kernels and the C ABI of include/salp_vec.h) reaches the kernels only through those.  No instantiation may be
 // named in two units.
@@ -85,6 +85,9 @@ constexpr int waves_per_simd(int fmax, int kmax, bool std_consts, bool ragged, i
   // it sat at 255-256 VGPRs with 12-132 B of scratch, its twin holds 0-12 B; at 1 258-272 registers, 2-16 of them AGPRs, none).
   // From the code-object metadata of all 40: profiles/r06/eval_kernel_resources.txt.
   if (policy && sig == 4 && fmax == 4 && !std_consts && !ragged) return 1;
+  // The navigation kernels (sig 5, one food): 1 — the record and the trial's line are 26 more registers across the loop than the
+  // summary kernel's 224; at 2 the unpredicated kernel with literal constants held 136 B of scratch (33 VGPRs spilled).
+  if (policy && sig == 5) return 1;
   if (policy) return (ragged || fmax >= 8) ? 1 : 2;
   if (sig == 3 && ragged && kmax == 3 && fmax == 8) return 3;
   return fmax <= 1 ? 4 : (kmax != 3 ? (fmax <= 12 ? 2 : 1) : (fmax <= 8 ? 4 : (fmax <= 12 ? 3 : ((std_consts && !ragged) ? 3 : 2))));
@@ -104,7 +107,10 @@ __device__ __forceinline__ int wave_sum(int v) {
 struct IOPtrs {
   const float* act;       // [H][n][act_dim] or null (device-generated); ACT_POLICY: the policy's device block (salp_policy.h)
   float* obs;             // [H][n][obs_dim]
-  float* reward;          // [H][n]
+  union {
+    float* reward;        // [H][n]
+    const double* nav_line;   // kSigNav: [n][4] start x, start y, goal x, goal y
+  };
   uint8_t* terminated;    // [H][n]
   uint8_t* truncated;     // [H][n]
   float* final_obs;       // [H][n][obs_dim] rows of finished envs only
@@ -112,9 +118,15 @@ struct IOPtrs {
     int32_t* info;        // [H][n][3]
     float* logp_out;      // ACT_POLICY_SAMPLED (whose signatures have no info): [H][n] or null
   };
-  float* act_out;         // [H][n][act_dim]
+  union {
+    float* act_out;       // [H][n][act_dim]
+    double* nav_track;    // kSigNav: [H][n][2] position after each step of the call, or null
+  };
   DevStats* stats;        // [SALP_STATS_REPLICAS] or null
-  int64_t global_step;    // step index of t = 0 (device-generated actions)
+  union {
+    int64_t global_step;  // step index of t = 0 (device-generated actions)
+    double nav_radius;    // kSigNav (no generated actions): the goal radius
+  };
 };
 
 #ifdef SALP_EXP_STAMPS
@@ -164,9 +176,15 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
   // (SALP_EVAL_ACCUMULATE).  The observation is formed in registers for the policy alone: no tile write, no flush, no
   // reward / flag / action store; the record leaves next to the state write-back.  The LDS layout is that of the twin policy
   // kernel (the rare paths still borrow the tile's bytes, the mirror sits behind it): LDS limits none of these kernels.
-  constexpr bool SUMMARY = SIG == 4;
-  static_assert(!POLICY || ((SIG == 1 || SIG == 4) && KMAX == 3), "policy kernels: the main-only and the summary signature, K = 3");
+  // SIG 5 (kSigNav): the summary kernel's loop with a per-env `running` predicate and a navigation record — salp_vec_evaluate_navigation.
+  // io.obs is the block of records ([n][SALP_NAV_WORDS] words), io.final_obs non-NULL = SALP_EVAL_ACCUMULATE, io.nav_line the
+  // trials' start / goal, io.nav_radius the goal radius, io.nav_track the optional positions.  A lane that is not running is not
+  // stepped: nothing of its state, statistics or record moves; a wavefront with no running lane leaves the step loop.
+  constexpr bool NAV = SIG == 5;
+  constexpr bool SUMMARY = SIG == 4 || NAV;     // everything the two share: no per-step output, no tile write
+  static_assert(!POLICY || ((SIG == 1 || SIG == 4 || SIG == 5) && KMAX == 3), "policy kernels: the main-only, the summary and the navigation signature, K = 3");
   static_assert(!SUMMARY || POLICY, "the summary signature exists for the in-kernel policy only");
+  static_assert(!NAV || (FMAX == 1 && FORCED && ACT == ACT_POLICY), "the navigation signature: one food, forced breathing, the deterministic policy");
   // (the summary kernels the other way round — by value with 4 / 8 slots, the device copy with 16: with no store in the step loop
   // the twins' choice left 300-560 scalar registers spilled and 68-196 B of scratch reserved in four of them; so chosen, none
   // of the 40 holds scratch where its twin holds none, profiles/r06/eval_kernel_resources.txt)
@@ -340,7 +358,38 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
   double ev_ret = 0.0, ev_first_ret = 0.0;
   int ev_first_len = 0, ev_first_end = 0, ev_episodes = 0, ev_food = 0;
   int4* const ev_lds = reinterpret_cast<int4*>(tile + WAVE_FLOATS - EV_FLOATS) + lane;
-  if constexpr (SUMMARY) {
+  // NAV: the env's record (include/salp_vec.h SALP_NAV_*) in registers, with the trial's line; `running` = the lane is stepped
+  [[maybe_unused]] double nv_path = 0.0, nv_lat = 0.0, nv_xmin = 0.0, nv_xmax = 0.0, nv_ymin = 0.0, nv_ymax = 0.0;
+  [[maybe_unused]] double nv_sx = 0.0, nv_sy = 0.0, nv_gx = 0.0, nv_gy = 0.0, nv_dnx = 0.0, nv_dny = 0.0;
+  [[maybe_unused]] int nv_steps = 0, nv_status = 0, nv_steps0 = 0;
+  [[maybe_unused]] bool running = true;
+  if constexpr (NAV) {
+    nv_xmin = nv_xmax = e.x; nv_ymin = nv_ymax = e.y;     // a fresh record: the box is the entry position
+    if (rows > 0) {
+      const double2* const lp2 = reinterpret_cast<const double2*>(io.nav_line) + envc * 2;
+      const double2 s2 = lp2[0], g2 = lp2[1];
+      nv_sx = s2.x; nv_sy = s2.y; nv_gx = g2.x; nv_gy = g2.y;
+      const double dx = nv_gx - nv_sx, dy = nv_gy - nv_sy;
+      const double L = sqrt(dx * dx + dy * dy) + 1e-12;
+      nv_dnx = dx / L; nv_dny = dy / L;
+      if (io.final_obs) {     // SALP_EVAL_ACCUMULATE: continue the caller's record unless it is a fresh one (steps == 0 && status == 0)
+        const int4* const rp = reinterpret_cast<const int4*>(io.obs) + envc * (SALP_NAV_WORDS / 4);
+        const int4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3];
+        if (r0.x != 0 || r0.y != 0) {
+          nv_steps = r0.x; nv_status = r0.y;
+          nv_path = __hiloint2double(r0.w, r0.z);
+          nv_lat = __hiloint2double(r1.y, r1.x);
+          nv_xmin = __hiloint2double(r1.w, r1.z);
+          nv_xmax = __hiloint2double(r2.y, r2.x);
+          nv_ymin = __hiloint2double(r2.w, r2.z);
+          nv_ymax = __hiloint2double(r3.y, r3.x);
+        }
+      }
+    }
+    nv_steps0 = nv_steps;
+    running = active && rows > 0 && (nv_status & 1) == 0;
+  }
+  if constexpr (SUMMARY && !NAV) {
     int4 ra = make_int4(0, 0, 0, 0), rb = make_int4(0, 0, 0, 0);
     if (io.final_obs && rows > 0) {     // SALP_EVAL_ACCUMULATE: continue the caller's record (complete at the vmcnt(0) below)
       const int4* const rp = reinterpret_cast<const int4*>(io.obs) + envc * 2;
@@ -431,6 +480,16 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
   for (int t = 0; t < Hrun; ++t) {
     const int64_t rowbase = (int64_t)t * P.n;
     float c0 = a0, c1 = a1;
+    if constexpr (NAV) {
+      if (!__any(running)) {     // every trial of the wavefront has ended: the remaining track rows repeat the last positions
+        if (io.nav_track && active) {
+#pragma unroll 1
+          for (int u = t; u < Hrun; ++u) reinterpret_cast<double2*>(io.nav_track)[(int64_t)u * P.n + env] = make_double2(e.x, e.y);
+        }
+        break;
+      }
+    }
+    [[maybe_unused]] const double nv_px = e.x, nv_py = e.y;     // NAV: the position before the step
     if (GEN) {
       // device action stream (include/salp_vec.h "Randomness"): word ts & 3 of block ts >> 2
       const uint32_t ts = (uint32_t)(io.global_step + t);
@@ -479,6 +538,19 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
       o = step_env_reg<FMAX, KMAX, FORCED, STD>(e, ff, mir, P, genv, c0, c1, K, fq, nlive, order_cache, &cold->P);
 #endif
     }
+    else if constexpr (NAV) {
+      // only the running lanes are stepped; for the others `o` says that nothing happened, so the rare-event region below
+      // (statistics, respawn) passes them by and their state keeps every bit
+      o.rmax = 0.0; o.reward = 0.f; o.rel = 0.f; o.rel_valid = false;
+      o.terminated = o.truncated = o.collision = o.collected = false;
+      if (running) {
+#ifdef SALP_EXP_STAMPS
+        o = step_env<FMAX, FORCED, STD>(e, P, genv, c0, c1, &stamps);
+#else
+        o = step_env<FMAX, FORCED, STD>(e, P, genv, c0, c1);
+#endif
+      }
+    }
     else {
 #ifdef SALP_EXP_STAMPS
       { StampAcc* stamps_ = &stamps; SALP_STAMP(0); }
@@ -515,6 +587,24 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
       }
     }
     st_reward += (double)o.reward;
+    if constexpr (NAV) {
+      // the record of the step just taken, in fp64 with IEEE sqrt (include/salp_vec.h "Navigation evaluation": a host loop
+      // reproduces every bit); a lane that reaches the goal stops running behind this step
+      if (running) {
+        const double x = e.x, y = e.y;
+        const double sx_ = x - nv_px, sy_ = y - nv_py;
+        nv_path += sqrt(sx_ * sx_ + sy_ * sy_);
+        nv_lat += fabs((x - nv_sx) * nv_dny - (y - nv_sy) * nv_dnx);
+        nv_xmin = fmin(nv_xmin, x); nv_xmax = fmax(nv_xmax, x);
+        nv_ymin = fmin(nv_ymin, y); nv_ymax = fmax(nv_ymax, y);
+        nv_steps += 1;
+        nv_status |= (o.collision ? 2 : 0) | (o.collected ? 4 : 0);
+        const double gx_ = x - nv_gx, gy_ = y - nv_gy;
+        if (sqrt(gx_ * gx_ + gy_ * gy_) < io.nav_radius) { nv_status |= 1; running = false; }
+      }
+      // one 16-byte store per lane, 1 KB contiguous per wavefront; a stopped env repeats its last position
+      if (io.nav_track && active) reinterpret_cast<double2*>(io.nav_track)[rowbase + env] = make_double2(e.x, e.y);
+    } else
     if constexpr (SUMMARY) {    // the float32 reward a rollout would have stored, added in step order in fp64; nothing below changes these
       const double r64 = (double)o.reward;
       const int end_now = o.terminated ? 1 : (o.truncated ? 2 : 0);     // terminated wins, as in the statistics below
@@ -808,6 +898,14 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
     } else {
       store_env(e, CS, C, env);
     }
+    if constexpr (NAV) {         // the env's record: five 16-byte stores (a lane that took no step writes back what it read)
+      int4* const rp = reinterpret_cast<int4*>(io.obs) + env * (SALP_NAV_WORDS / 4);
+      rp[0] = make_int4(nv_steps, nv_status, __double2loint(nv_path), __double2hiint(nv_path));
+      rp[1] = make_int4(__double2loint(nv_lat), __double2hiint(nv_lat), __double2loint(nv_xmin), __double2hiint(nv_xmin));
+      rp[2] = make_int4(__double2loint(nv_xmax), __double2hiint(nv_xmax), __double2loint(nv_ymin), __double2hiint(nv_ymin));
+      rp[3] = make_int4(__double2loint(nv_ymax), __double2hiint(nv_ymax), __double2loint(e.x), __double2hiint(e.x));
+      rp[4] = make_int4(__double2loint(e.y), __double2hiint(e.y), 0, 0);
+    } else
     if constexpr (SUMMARY) {     // the env's record: two 16-byte stores
       int4* const rp = reinterpret_cast<int4*>(io.obs) + env * 2;
       if constexpr (EVLDS) {
@@ -826,12 +924,13 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(FMAX, KMAX, STD, RAGGED, SIG
     // 8192 atomics on a 14-us launch, profiles/r03/ab_notes.md session 10)
     if (!active || rows == 0) st_reward = 0.0;
     const double wr = wave_sum(st_reward);
-    const int wact = wave_sum((active && rows > 0) ? 1 : 0);
+    // NAV: the steps the lanes actually took (a stopped env takes none)
+    const int wact = wave_sum((active && rows > 0) ? (NAV ? nv_steps - nv_steps0 : 1) : 0);
     unsigned long long* const blk = reinterpret_cast<unsigned long long*>(lds);
     __syncthreads();                               // every wavefront is past its last tile flush
     if (lane == 0) {
       blk[2 * wave] = (unsigned long long)__double2ll_rn(wr * SALP_FIXED_SCALE);
-      blk[2 * wave + 1] = (unsigned long long)((long long)wact * H);
+      blk[2 * wave + 1] = (unsigned long long)((long long)wact * (NAV ? 1 : H));
     }
     __syncthreads();
     if (tid < 2) {
@@ -855,7 +954,10 @@ typedef void (*rollout_fn)(DevParams, DevState, IOPtrs, int, int64_t, int64_t, c
 // info stores at all; unpredicated and predicated, K = 3 and generic K; no in-kernel action generation.
 // kSigSummary = NO per-step output: one record of SALP_EVAL_WORDS words per env at the end of the launch
 // (salp_vec_evaluate_policy); exists for the in-kernel policy and K = 3 only, unpredicated and predicated.
-enum { kSigPartial = 0, kSigMain = 1, kSigExtras = 2, kSigPacked = 3, kSigSummary = 4 };
+// kSigNav = the summary kernel's loop with a per-env stop at a goal and one navigation record of SALP_NAV_WORDS words per env
+// (salp_vec_evaluate_navigation); exists for one food, K = 3, forced breathing and the deterministic in-kernel policy only —
+// four kernels, in the two one-food units.  Asked of anything else the choice is empty (fn NULL): the host refuses first.
+enum { kSigPartial = 0, kSigMain = 1, kSigExtras = 2, kSigPacked = 3, kSigSummary = 4, kSigNav = 5 };
 #ifdef SALP_EXP_STAMPS
 // experiment build only: the per-wavefront phase cycle sums of this unit's last rollout launches (16 words per wavefront)
 int exp_read_stamps(uint32_t* dst, int words) {
@@ -884,6 +986,10 @@ RolloutPick picked() {
 template <int FMAX, int KMAX, bool FORCED, bool STD, bool RAGGED, int ACT>
 RolloutPick pick_sig(int sig) {
   if constexpr (ACT == ACT_POLICY || ACT == ACT_POLICY_SAMPLED) {
+    if (sig == kSigNav) {
+      if constexpr (ACT == ACT_POLICY && FMAX == 1 && KMAX == 3 && FORCED) return picked<FMAX, KMAX, FORCED, STD, kSigNav, RAGGED, ACT>();
+      else return RolloutPick{nullptr, -1};
+    }
     if (sig == kSigSummary) return picked<FMAX, KMAX, FORCED, STD, kSigSummary, RAGGED, ACT>();
     return picked<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, ACT>();
   } else if constexpr (ACT != ACT_READ) return picked<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, ACT>();
@@ -900,7 +1006,7 @@ template <int FMAX, int KMAX, bool STD, bool RAGGED>
 RolloutPick pick_rollout(bool forced, int sig, int act) {
   if ((sig == kSigMain || sig == kSigSummary) && act == ACT_POLICY_SAMPLED)   // the same two signatures, sampling
     return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, ACT_POLICY_SAMPLED>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, ACT_POLICY_SAMPLED>(sig);
-  if ((sig == kSigMain || sig == kSigSummary) && act == ACT_POLICY)   // the in-kernel policy exists for the main-only output signature and for the summary
+  if ((sig == kSigMain || sig == kSigSummary || sig == kSigNav) && act == ACT_POLICY)   // the in-kernel policy exists for the main-only output signature and for the summary
     return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, ACT_POLICY>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, ACT_POLICY>(sig);
   if (sig == kSigMain && act == ACT_GEN)
     return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, ACT_GEN>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, ACT_GEN>(sig);

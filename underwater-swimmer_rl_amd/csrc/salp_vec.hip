@@ -304,11 +304,13 @@ int (*g_read_counters)(unsigned long long*) = exp_read_counters;
 // What a rollout launch writes and where its actions come from.
 //   out: kOutStreams — the per-step streams of io, the signature follows from which are present;  kOutPacked — io.obs is a
 //        record block (kSigPacked), io.final_obs non-NULL asks for the terminal-observation tail;  kOutSummary — io.obs is the
-//        block of summary records (kSigSummary; policy only), io.final_obs non-NULL = SALP_EVAL_ACCUMULATE
+//        block of summary records (kSigSummary; policy only), io.final_obs non-NULL = SALP_EVAL_ACCUMULATE;  kOutNav — io.obs is
+//        the block of navigation records (kSigNav; deterministic policy, one food, forced breathing: the caller has checked),
+//        io.final_obs as for the summary, io.nav_line / nav_radius / nav_track the trial lines, the goal radius and the track
 //   act: ACT_READ — io.act, or generated in the kernel when that is NULL (only reached when can_generate_in_kernel());
 //        ACT_POLICY / ACT_POLICY_SAMPLED — io.act is a policy's device block (the caller has checked K = 3 and the four main
 //        outputs; ACT_POLICY_SAMPLED: a Gaussian policy, io.logp_out may be set)
-enum { kOutStreams = 0, kOutPacked = 1, kOutSummary = 2 };
+enum { kOutStreams = 0, kOutPacked = 1, kOutSummary = 2, kOutNav = 3 };
 struct RolloutKind { int out, act; };
 
 int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, RolloutKind kind) {
@@ -316,9 +318,10 @@ int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, Rollout
   const bool main_outputs = io.obs && io.reward && io.terminated && io.truncated;
   // (policy: final_obs / info do not exist — io.final_obs is the summary's accumulate flag, io.info's slot holds logp_out)
   const bool extras = !policy && (io.final_obs || io.info);
-  const int sig = kind.out == kOutSummary ? kSigSummary : kind.out == kOutPacked ? kSigPacked
+  const int sig = kind.out == kOutNav ? kSigNav : kind.out == kOutSummary ? kSigSummary : kind.out == kOutPacked ? kSigPacked
                 : (!main_outputs ? kSigPartial : (extras ? kSigExtras : kSigMain));
-  if (policy && sig != kSigMain && sig != kSigSummary) return fail(SALP_ERR_INVALID, "policy kernels exist for the main-only and the summary signature");
+  if (policy && sig != kSigMain && sig != kSigSummary && sig != kSigNav)
+    return fail(SALP_ERR_INVALID, "policy kernels exist for the main-only, the summary and the navigation signature");
   const int gen = policy ? kind.act : (io.act == nullptr ? ACT_GEN : ACT_READ);
   // envs in full wavefronts: unpredicated kernel
   int64_t n_full = h->n / kWave * kWave;
@@ -332,6 +335,8 @@ int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, Rollout
   const RolloutPick full = (n_full > 0) ? unit(false, forced, sig, gen) : none;
   const RolloutPick ragged = (n_full < h->n) ? unit(true, forced, sig, gen) : none;
   const RolloutPick& first = (n_full > 0) ? full : ragged;
+  if ((n_full > 0 && !full.fn) || (n_full < h->n && !ragged.fn))      // (kSigNav asked of a handle class that has no such kernel)
+    return fail(SALP_ERR_INVALID, "no kernel of this output signature exists for this handle");
   h->last_sigs[0] = full.sig;
   h->last_sigs[1] = ragged.sig;
   h->last_launch[0] = h->fmax; h->last_launch[1] = h->kmax; h->last_launch[2] = (h->kmax == 3) ? h->std_consts : 0;
@@ -962,6 +967,41 @@ int salp_vec_evaluate_policy(salp_vec_t* h, const salp_policy_t* pol, int32_t H,
 
 int salp_vec_evaluate_policy_sampled(salp_vec_t* h, const salp_policy_t* pol, int32_t H, void* rec, uint32_t flags, void* stream) {
   return evaluate_policy_impl(h, pol, H, rec, flags, stream, true);
+}
+
+// salp_vec_evaluate_navigation: the kSigNav kernels.  Everything is checked before anything is launched.
+int salp_vec_evaluate_navigation(salp_vec_t* h, const salp_policy_t* pol, int32_t H, const double* line, double goal_radius,
+                                 void* rec, double* track, uint32_t flags, void* stream) {
+  int rc = check_policy_call(h, pol, false);
+  if (rc != SALP_OK) return rc;
+  if (h->P.autoreset) return fail(SALP_ERR_INVALID, "navigation trials need a handle with no_autoreset (nothing ends a trial but the goal)");
+  if (h->cfg.num_food_items != 1 || h->fmax != 1) return fail(SALP_ERR_INVALID, "navigation trials need num_food_items == 1 (the goal)");
+  if (!h->P.forced) return fail(SALP_ERR_INVALID, "navigation trials need forced breathing");
+  if (!rec || !line) return fail(SALP_ERR_INVALID, "rec/line is NULL");
+  if (H <= 0) return fail(SALP_ERR_INVALID, "horizon must be >= 1");
+  if (!(goal_radius > 0.0) || !(goal_radius <= 1.7976931348623157e308)) return fail(SALP_ERR_INVALID, "goal_radius must be finite and positive");
+  if (flags & ~(uint32_t)(SALP_DEVICE_PTRS | SALP_EVAL_ACCUMULATE))
+    return fail(SALP_ERR_INVALID, "unknown flag bits (SALP_DEVICE_PTRS and SALP_EVAL_ACCUMULATE are defined)");
+  if ((flags & SALP_DEVICE_PTRS) && ((uintptr_t)rec & 15u))
+    return fail(SALP_ERR_INVALID, "rec must be 16-byte aligned (a record is written as five 16-byte stores)");
+  if ((flags & SALP_DEVICE_PTRS) && ((((uintptr_t)line) | ((uintptr_t)track)) & 15u))
+    return fail(SALP_ERR_INVALID, "line and track must be 16-byte aligned (read / written 16 bytes at a time)");
+  DeviceScope dev_scope;
+  HIP_TRY(dev_scope.enter(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  h->last_stream = st;
+  const bool accumulate = (flags & SALP_EVAL_ACCUMULATE) != 0;
+  IOPtrs io = io_for(h);
+  io.act = pol->block;
+  io.nav_radius = goal_radius;       // (shares its bytes with global_step, which only generated actions read)
+  auto launch = [&](const double* d_line, float* d_rec, double* d_track) {
+    io.nav_line = d_line; io.obs = d_rec; io.final_obs = accumulate ? d_rec : nullptr; io.nav_track = d_track;
+    return run_rollout(h, io, H, st, {kOutNav, ACT_POLICY}, pol);
+  };
+  if (flags & SALP_DEVICE_PTRS) return launch(line, (float*)rec, track);
+  HostStream s[] = {stream_in(line, (size_t)h->n * 4), stream_out((int32_t*)rec, (size_t)h->n * SALP_NAV_WORDS, accumulate),
+                    stream_out(track, (size_t)H * (size_t)h->n * 2)};
+  return staged(h->stage, st, s, [&] { return launch(s[0].as<const double>(), s[1].as<float>(), s[2].as<double>()); });
 }
 
 int salp_vec_get_state(salp_vec_t* h, double* f64, int32_t* i32, uint32_t flags, void* stream) {

@@ -10,7 +10,9 @@ Restates the protocol and metrics of the reference's eval/collect_navigation_dat
   * metrics (:117-196): path length (+ final distance to the goal), success (final distance < 50),
     path ratio, straightness, mean lateral deviation from the start-goal line, bounding-box area and
     area ratio, x / y range, and the spline-smoothed path ratio (:138-165, `spline_path_length`).
-All trials run at once: trial i is env i.  The only published numbers for this protocol are in
+All trials run at once: trial i is env i.  `run_navigation_trials` steps the env once per kernel launch under any
+callable policy; `run_navigation_trials_in_kernel` runs the whole loop of an `MLPPolicy` in one launch
+(salp_vec_evaluate_navigation) and reads 80 B per trial.  The only published numbers for this protocol are in
 eval/results/navigation_stats_20251207_165158.json (a trained SB3 policy: success 1.00,
 1773.78 +/- 253.8 steps, path ratio 1.173, straightness 0.863).
 """
@@ -91,6 +93,99 @@ def run_navigation_trials(policy: Callable, num_trials: int = 100, start_pos=(15
     steps_h = steps.cpu().numpy()
     out = navigation_metrics(pos_h, steps_h, np.asarray(start_pos, float), np.asarray(goal_pos, float), goal_radius)
     out["collided"] = collided.cpu().numpy()
+    if own:
+        env.close()
+    return out
+
+
+def pursuit_mlp(gain: float = 3.0):
+    """`pursuit_policy` as an in-kernel policy (`MLPPolicy.linear(..., out="clip")`): clip(-gain * obs[13], -1, 1)."""
+    from .policy import pursuit_policy as linear_pursuit
+    return linear_pursuit(gain)
+
+
+def _pairs(p, n: int, what: str) -> np.ndarray:
+    """One (x, y) pair for every trial, or [n, 2]: float64 [n, 2]."""
+    a = np.asarray(p, np.float64)
+    if a.shape == (2,):
+        a = np.broadcast_to(a, (n, 2))
+    if a.shape != (n, 2) or not np.isfinite(a).all():
+        raise ValueError(f"{what} must be one finite (x, y) pair or [{n}, 2]")
+    return np.ascontiguousarray(a)
+
+
+def _host(a) -> np.ndarray:
+    return a if isinstance(a, np.ndarray) else a.detach().cpu().numpy()
+
+
+def metrics_from_record(views, line, goal_radius: float = 50.0, track=None) -> Dict[str, np.ndarray]:
+    """The keys of `navigation_metrics` from the navigation records of `SalpVectorEnv.evaluate_navigation`
+    (`policy.navigation_views`): path_length = path_sum + final_distance, lateral_deviation = lateral_sum / (steps + 1) —
+    the mean over the start and every step taken, the start's own term being 0.  `line`: [4] or [N, 4] (start x, start y,
+    goal x, goal y).  `track`: [T, N, 2] positions after each step (T >= every env's steps) for the spline fields, which
+    are NaN without it."""
+    from .policy import navigation_line
+    steps = _host(views["steps"]).astype(np.int64)
+    n = len(steps)
+    ln = navigation_line(line, n)
+    start, goal = ln[:, :2], ln[:, 2:]
+    final = np.stack([_host(views["x"]), _host(views["y"])], axis=1).astype(np.float64)
+    optimal = np.linalg.norm(goal - start, axis=1)
+    final_distance = np.linalg.norm(final - goal, axis=1)
+    path_length = _host(views["path_sum"]) + final_distance
+    xr = _host(views["xmax"]) - _host(views["xmin"])
+    yr = _host(views["ymax"]) - _host(views["ymin"])
+    area = xr * yr
+    spline_len = np.full(n, np.nan)
+    if track is not None:
+        trk = _host(track)
+        if trk.ndim != 3 or trk.shape[1:] != (n, 2) or trk.shape[0] < steps.max(initial=0):
+            raise ValueError(f"track must be [T, {n}, 2] with T >= the steps of every env")
+        spline_len = np.array([spline_path_length(np.vstack([start[i:i + 1], trk[: steps[i], i]]), goal[i]) for i in range(n)])
+    return {
+        "steps": steps, "path_length": path_length, "final_distance": final_distance,
+        "success": final_distance < goal_radius, "path_ratio": path_length / optimal,
+        "straightness": optimal / np.maximum(path_length, 1e-12),
+        "lateral_deviation": _host(views["lateral_sum"]) / (steps + 1),
+        "area_covered": area, "area_ratio": area / (optimal * goal_radius * 2), "x_range": xr, "y_range": yr,
+        "optimal_distance": optimal, "spline_path_length": spline_len, "spline_path_ratio": spline_len / optimal,
+    }
+
+
+def run_navigation_trials_in_kernel(policy, num_trials: int = 100, start_pos=(150.0, 300.0), goal_pos=(650.0, 300.0),
+                                    max_steps: int = 3000, goal_radius: float = 50.0, device="cuda:0", seed: int = 0,
+                                    heading_seed: int = 0, env: Optional[SalpVectorEnv] = None, track: bool = True) -> Dict[str, np.ndarray]:
+    """`run_navigation_trials` with the whole trial loop in ONE kernel launch (`SalpVectorEnv.evaluate_navigation`): the
+    same set-up through `set_state`, the policy an `MLPPolicy` (`pursuit_mlp`, `MLPPolicy.from_actor`) or a handle of
+    `env.make_policy`, positions taken from the fp64 state as the reference takes `env.robot_pos`.  `start_pos` /
+    `goal_pos`: one pair, or [N, 2] for a trial line per env.  Returns the dict of `run_navigation_trials` (the spline
+    fields NaN with `track=False`, which leaves 80 B per trial as the only output)."""
+    from . import policy as _policy
+    cfg = navigation_config()
+    own = env is None
+    n = int(num_trials) if own else env.num_envs
+    if int(max_steps) < 1:
+        raise ValueError("max_steps must be >= 1")
+    start, goal = _pairs(start_pos, n, "start_pos"), _pairs(goal_pos, n, "goal_pos")
+    if not isinstance(policy, (_policy.MLPPolicy, _capi.PolicyHandle)):
+        raise TypeError("the in-kernel trials take an MLPPolicy (pursuit_mlp, MLPPolicy.from_actor) or a policy handle; "
+                        "run_navigation_trials takes any callable")
+    env = env or SalpVectorEnv(cfg, n, device=device, seed=seed)
+    env.reset()
+    f64, i32 = env.get_state()
+    rng = np.random.default_rng(heading_seed)
+    f64[_capi.F_X], f64[_capi.F_Y] = start[:, 0], start[:, 1]
+    f64[_capi.F_VX] = 0.0
+    f64[_capi.F_VY] = 0.0
+    f64[_capi.F_THETA] = rng.uniform(-np.pi, np.pi, n)       # np.random.uniform(-pi, pi), :82
+    f64[_capi.F_OMEGA] = 0.0
+    f64[_capi.F_FOOD0], f64[_capi.F_FOOD0 + 1] = goal[:, 0], goal[:, 1]
+    i32[_capi.I_STEPS_SINCE_FOOD] = 0
+    env.set_state(f64, i32)
+    line = np.concatenate([start, goal], axis=1)
+    v = env.evaluate_navigation(policy, int(max_steps), line, goal_radius, track=bool(track))
+    out = metrics_from_record(v, line, goal_radius, v.get("track"))
+    out["collided"] = (_host(v["status"]) & _policy.NAV_COLLIDED) != 0
     if own:
         env.close()
     return out

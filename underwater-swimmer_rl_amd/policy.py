@@ -506,6 +506,98 @@ def summarize_rollout(reward, terminated, truncated, captured=None, record=None)
     return rec
 
 
+# ---------------------------------------------------------------------- navigation records (salp_vec_evaluate_navigation)
+(NAV_STEPS, NAV_STATUS, NAV_PATH, NAV_LATERAL, NAV_XMIN, NAV_XMAX, NAV_YMIN, NAV_YMAX, NAV_X, NAV_Y,
+ NAV_WORDS) = 0, 1, 2, 4, 6, 8, 10, 12, 14, 16, 20
+NAV_REACHED, NAV_COLLIDED, NAV_CAPTURED = 1, 2, 4
+
+
+def navigation_views(record) -> dict:
+    """Typed views (no copy) of a block of navigation records, int32 [N, 20] (numpy array or torch tensor, contiguous):
+    `record` itself, `steps` and `status` int32 [N] (status bits NAV_REACHED / NAV_COLLIDED / NAV_CAPTURED), `path_sum`,
+    `lateral_sum`, `xmin`, `xmax`, `ymin`, `ymax`, `x`, `y` float64 [N] (include/salp_vec.h SALP_NAV_*)."""
+    if isinstance(record, np.ndarray):
+        if record.dtype != np.int32 or record.ndim != 2 or record.shape[1] != NAV_WORDS or not record.flags.c_contiguous:
+            raise ValueError("record must be a contiguous int32 [N, 20] block")
+        f64 = record.view(np.float64)                       # [N, 10]
+    else:
+        import torch
+        if record.dtype != torch.int32 or record.dim() != 2 or record.shape[1] != NAV_WORDS or not record.is_contiguous():
+            raise ValueError("record must be a contiguous int32 [N, 20] block")
+        f64 = record.view(torch.float64)
+    return dict(record=record, steps=record[:, NAV_STEPS], status=record[:, NAV_STATUS], path_sum=f64[:, NAV_PATH // 2],
+                lateral_sum=f64[:, NAV_LATERAL // 2], xmin=f64[:, NAV_XMIN // 2], xmax=f64[:, NAV_XMAX // 2],
+                ymin=f64[:, NAV_YMIN // 2], ymax=f64[:, NAV_YMAX // 2], x=f64[:, NAV_X // 2], y=f64[:, NAV_Y // 2])
+
+
+def navigation_line(line, n: int) -> np.ndarray:
+    """`line` as float64 [n, 4] (start x, start y, goal x, goal y): one line for every env or one per env."""
+    ln = np.asarray(line, np.float64)
+    if ln.shape == (4,):
+        ln = np.broadcast_to(ln, (n, 4))
+    if ln.shape != (n, 4):
+        raise ValueError(f"line must be [4] or [{n}, 4] (start x, start y, goal x, goal y)")
+    if not np.isfinite(ln).all():
+        raise ValueError("line must be finite")
+    return np.ascontiguousarray(ln)
+
+
+def navigation_record(pos, steps, line, goal_radius, collided=None, captured=None, record=None) -> np.ndarray:
+    """The navigation records of a path — the numpy statement of what salp_vec_evaluate_navigation leaves: pos float64
+    [T + 1, N, 2], pos[0] the position at entry and pos[t] the one after step t; steps [N] (or None = T): the most steps an
+    env takes over this piece; line [4] or [N, 4]; collided / captured [T, N] (that step collided / captured; None: no bit).
+    An env takes step t while t <= steps and it has not been within `goal_radius` of its goal after a step.  Returns int32
+    [N, 20].  The sums are sequential float64 additions in step order, with sqrt and division correctly rounded.
+    `record`: records to continue (SALP_EVAL_ACCUMULATE; not modified) — one with steps == 0 and status == 0 is a fresh one,
+    one that has reached its goal is returned unchanged."""
+    pos = np.asarray(pos)
+    if pos.dtype != np.float64 or pos.ndim != 3 or pos.shape[2] != 2 or pos.shape[0] < 1:
+        raise ValueError("pos must be float64 [T + 1, N, 2]")
+    T, N = pos.shape[0] - 1, pos.shape[1]
+    radius = float(goal_radius)
+    if not (np.isfinite(radius) and radius > 0.0):
+        raise ValueError("goal_radius must be finite and positive")
+    ln = navigation_line(line, N)
+    cap = np.full(N, T, np.int64) if steps is None else np.asarray(steps).astype(np.int64).reshape(N)
+    if (cap < 0).any() or (cap > T).any():
+        raise ValueError("steps must be within 0..T")
+    col = np.zeros((T, N), bool) if collided is None else np.asarray(collided).astype(bool).reshape(T, N)
+    got = np.zeros((T, N), bool) if captured is None else np.asarray(captured).astype(bool).reshape(T, N)
+    rec = np.zeros((N, NAV_WORDS), np.int32) if record is None else np.array(record, dtype=np.int32, order="C").reshape(N, NAV_WORDS)
+    v = navigation_views(rec)
+    fresh = (v["steps"] == 0) & (v["status"] == 0)
+    for k, src in (("xmin", pos[0, :, 0]), ("xmax", pos[0, :, 0]), ("ymin", pos[0, :, 1]), ("ymax", pos[0, :, 1]),
+                   ("x", pos[0, :, 0]), ("y", pos[0, :, 1]), ("path_sum", 0.0), ("lateral_sum", 0.0)):
+        v[k][:] = np.where(fresh, src, v[k])
+    rec[:, NAV_WORDS - 2:] = np.where(fresh[:, None], 0, rec[:, NAV_WORDS - 2:])
+    sx, sy, gx, gy = ln[:, 0], ln[:, 1], ln[:, 2], ln[:, 3]
+    dx, dy = gx - sx, gy - sy
+    L = np.sqrt(dx * dx + dy * dy) + 1e-12
+    dnx, dny = dx / L, dy / L
+    nsteps, status = v["steps"].copy(), v["status"].copy()
+    path, lat = v["path_sum"].copy(), v["lateral_sum"].copy()
+    xmin, xmax, ymin, ymax = v["xmin"].copy(), v["xmax"].copy(), v["ymin"].copy(), v["ymax"].copy()
+    lx, ly = v["x"].copy(), v["y"].copy()
+    for t in range(1, T + 1):
+        run = ((status & NAV_REACHED) == 0) & (t <= cap)
+        if not run.any():
+            break
+        x, y, px, py = pos[t, :, 0], pos[t, :, 1], pos[t - 1, :, 0], pos[t - 1, :, 1]
+        seg = np.sqrt((x - px) * (x - px) + (y - py) * (y - py))
+        path = np.where(run, path + seg, path)
+        lat = np.where(run, lat + np.abs((x - sx) * dny - (y - sy) * dnx), lat)
+        xmin, xmax = np.where(run, np.minimum(xmin, x), xmin), np.where(run, np.maximum(xmax, x), xmax)
+        ymin, ymax = np.where(run, np.minimum(ymin, y), ymin), np.where(run, np.maximum(ymax, y), ymax)
+        nsteps = nsteps + run.astype(np.int32)
+        reached = np.sqrt((x - gx) * (x - gx) + (y - gy) * (y - gy)) < radius
+        bits = np.where(col[t - 1], NAV_COLLIDED, 0) | np.where(got[t - 1], NAV_CAPTURED, 0) | np.where(reached, NAV_REACHED, 0)
+        status = np.where(run, status | bits, status).astype(np.int32)
+        lx, ly = np.where(run, x, lx), np.where(run, y, ly)
+    v["steps"][:], v["status"][:], v["path_sum"][:], v["lateral_sum"][:] = nsteps, status, path, lat
+    v["xmin"][:], v["xmax"][:], v["ymin"][:], v["ymax"][:], v["x"][:], v["y"][:] = xmin, xmax, ymin, ymax, lx, ly
+    return rec
+
+
 def pursuit_policy(gain: float = 3.0, obs_dim: int = 24) -> MLPPolicy:
     """`navigation_eval.pursuit_policy` as an in-kernel policy: clip(-gain * obs[13], -1, 1)."""
     W = np.zeros((1, obs_dim), np.float32)

@@ -392,6 +392,74 @@ class SalpVectorEnv:
         call(policy, H, rec, self._flags | (_capi.EVAL_ACCUMULATE if accumulate else 0), self._stream)
         return views
 
+    def evaluate_navigation(self, policy, horizon: int, line, goal_radius: float = 50.0, out=None, accumulate: bool = False,
+                            track: bool = False) -> dict:
+        """Fixed start -> goal trials in one kernel launch (salp_vec_evaluate_navigation): up to `horizon` closed-loop steps
+        of `rollout_policy`, every env stopping — not stepped any further — once it is within `goal_radius` of its goal.
+        `line`: [4] or [N, 4] float64 (start x, start y, goal x, goal y); the envs are expected at their starts
+        (`set_state`).  Needs one food, forced breathing and `no_autoreset` (`navigation_eval.navigation_config`).  Returns
+        typed views of one int32 [N, 20] block (`policy.navigation_views`): `record`, `steps`, `status` (bit 0 reached, bit 1
+        collided, bit 2 captured the food), `path_sum`, `lateral_sum`, `xmin`, `xmax`, `ymin`, `ymax`, `x`, `y` (float64
+        [N]) — and with `track=True` also `track`, float64 [horizon, N, 2]: the position after each step of this call, a
+        stopped env repeating its last one (`track` may also be the block to write into).  `out` / `accumulate` as in `evaluate_policy`: a run cut into several calls
+        gives the bits of one call."""
+        from .policy import NAV_WORDS, navigation_line, navigation_views
+        H, n = int(horizon), self.num_envs
+        if H < 1:
+            raise ValueError("horizon must be >= 1")
+        radius = float(goal_radius)
+        if not (np.isfinite(radius) and radius > 0.0):
+            raise ValueError("goal_radius must be finite and positive")
+        if accumulate and out is None:
+            raise ValueError("accumulate=True continues the records in `out`: pass the block of the call before")
+        t = self._torch
+        # a float64 [N, 4] tensor on this GPU is taken as it is (nothing is copied or allocated for it: capturable)
+        on_device = t is not None and isinstance(line, t.Tensor) and line.device == self.device
+        if on_device:
+            if line.dtype != t.float64 or tuple(line.shape) != (n, 4) or not line.is_contiguous():
+                raise ValueError(f"a device line must be a contiguous float64 [{n}, 4] tensor")
+            ln = line
+        else:
+            ln = navigation_line(line.cpu().numpy() if t is not None and isinstance(line, t.Tensor) else line, n)
+        cfg = self.cfg
+        if cfg.num_food_items != 1 or not cfg.forced_breathing or not cfg.no_autoreset or cfg.max_observed_food != 3:
+            raise ValueError("evaluate_navigation needs num_food_items == 1, forced breathing, max_observed_food == 3 and no_autoreset")
+        if not isinstance(policy, _capi.PolicyHandle):
+            cache = self.__dict__.setdefault("_policy_cache", {})
+            if id(policy) not in cache:
+                cache[id(policy)] = (policy, self.make_policy(policy))
+            policy = cache[id(policy)][1]
+        rec = out["record"] if isinstance(out, dict) else out
+        if rec is None:
+            rec = (t.empty((n, NAV_WORDS), dtype=t.int32, device=self.device) if t is not None else np.empty((n, NAV_WORDS), np.int32))
+        if t is not None:        # the pointer goes to the kernel as a device pointer: it must be one, on this GPU
+            if not isinstance(rec, t.Tensor) or rec.device != self.device:
+                raise ValueError(f"out must be a torch tensor on {self.device}")
+        elif not isinstance(rec, np.ndarray):
+            raise ValueError("out must be a numpy array (this env returns host arrays)")
+        if tuple(rec.shape) != (n, NAV_WORDS):
+            raise ValueError(f"out must be an int32 [{n}, {NAV_WORDS}] block")
+        views = navigation_views(rec)       # checks dtype and contiguity
+        want_track = track is not None and track is not False
+        given = want_track and track is not True       # a block to write into: float64 [H, N, 2], on this GPU for a torch env
+        if t is not None:
+            if not on_device:
+                ln = t.from_numpy(ln).to(self.device)
+            if given and (not isinstance(track, t.Tensor) or track.device != self.device or track.dtype != t.float64 or
+                          tuple(track.shape) != (H, n, 2) or not track.is_contiguous()):
+                raise ValueError(f"a track block must be a contiguous float64 [{H}, {n}, 2] tensor on {self.device}")
+            trk = track if given else (t.empty((H, n, 2), dtype=t.float64, device=self.device) if want_track else None)
+        else:
+            if given and (not isinstance(track, np.ndarray) or track.dtype != np.float64 or track.shape != (H, n, 2) or
+                          not track.flags.c_contiguous):
+                raise ValueError(f"a track block must be a contiguous float64 [{H}, {n}, 2] array")
+            trk = track if given else (np.empty((H, n, 2), np.float64) if want_track else None)
+        self._lib.evaluate_navigation(policy, H, ln, radius, rec, trk, self._flags | (_capi.EVAL_ACCUMULATE if accumulate else 0),
+                                      self._stream)
+        if want_track:
+            views["track"] = trk
+        return views
+
     def observe(self):
         obs = self._buf("obs", (self.num_envs, self.obs_dim), np.float32)
         self._lib.observe(obs, self._flags, self._stream)
