@@ -3,7 +3,8 @@
 (a) csrc/salp_device.h step_head(): `p = timer / duration` of the breathing cycle (legacy:212-213, :240-246) is computed as
     y = RN(1/den), q0 = RN(t y), p = RN(q0 + RN_fma(t - den q0) y) instead of the IEEE division sequence, and is claimed
     to equal the correctly rounded quotient for every duration 1..255 and timer 1..257.  Checked here in exact rationals.
-(b) csrc/salp_vec.hip: the observation tile (96-B rows, float4 column XOR bit 2 of the row) is claimed conflict-free for
+(b) csrc/salp_rollout_traits.h (SWZ, PITCH) and csrc/salp_rollout_kernel.h (the tile writes and the flush plan): the
+    observation tile (96-B rows, float4 column XOR bit 2 of the row) is claimed conflict-free for
     both the row writes (ds_write_b128) and the flush reads (ds_read_b128) under the banking table of
     MI355X_MICROARCH.md §LDS; profiles/isa_lds_model.py is that table as code.
 """
@@ -48,7 +49,7 @@ def test_swizzled_observation_tile_is_conflict_free():
     assert (w, rd) == (8 * m.Q, 4 * m.Q)                 # one LDS cycle per lane group: no conflict anywhere
     w1, rd1 = m.model(m.layouts['112-B padded pitch (round 1)'])
     assert w1 == 8 * m.Q and rd1 == 2 * 4 * m.Q          # round 1: writes clean, flush reads 2-way (63.5 M conflict cycles measured)
-    # the kernel's own formulas (salp_vec.hip: lds_off, myrow_even / myrow_odd) are this layout
+    # the kernel's own formulas (salp_rollout_kernel.h: lds_off, myrow_even / myrow_odd) are this layout
     f = m.layouts[m.SHIPPED]
     for lane in range(64):
         swz = (lane >> 2) & 1

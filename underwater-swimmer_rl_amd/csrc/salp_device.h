@@ -43,6 +43,14 @@ __device__ unsigned long long salp_exp_counter[8];
 #define SALP_COUNT(i, cond) do {} while (0)
 #endif
 
+// The wavefront's LDS hand-over: what every lane wrote before is visible to every lane after, and the compiler moves no LDS
+// access across it (a wavefront runs in lockstep: the barrier itself is no instruction).
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // ---- packed breathing word: phase[1:0] | timer[9:2] | exhale_dur[17:10] | shape_hold[20:18]
 __host__ __device__ inline uint32_t pack_breath(int phase, int timer, int dur, int hold) {
   return (uint32_t)(phase & 3) | ((uint32_t)(timer & 255) << 2) | ((uint32_t)(dur & 255) << 10) |

@@ -575,9 +575,7 @@ __device__ __forceinline__ void place_food_coop_reg(Env<FMAX>& e, FoodF32<FMAX, 
       consumed += (uint32_t)j;
       present |= filled;
       if (filled) {                                // wave-uniform: lane L takes this batch's points (a later batch tests against them)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
 #pragma unroll
         for (int k = 0; k < FMAX; ++k) {
           if ((filled >> k) & 1u) {                // wave-uniform
@@ -585,9 +583,7 @@ __device__ __forceinline__ void place_food_coop_reg(Env<FMAX>& e, FoodF32<FMAX, 
             if (lane == L) { e.fx[k] = v.x; e.fy[k] = v.y; ff.set(k, v.x, v.y); m.set(k, v.x, v.y); }
           }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
       }
     }
     if (lane == L) e.rng = rng0 + consumed;

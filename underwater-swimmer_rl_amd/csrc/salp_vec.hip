@@ -302,21 +302,22 @@ int (*g_read_counters)(unsigned long long*) = exp_read_counters;
 #endif
 
 // What a rollout launch writes and where its actions come from.
-//   out: kOutStreams — the per-step streams of io, the signature follows from which are present;  kOutPacked — io.obs is a
-//        record block (kSigPacked), io.final_obs non-NULL asks for the terminal-observation tail;  kOutSummary — io.obs is the
-//        block of summary records (kSigSummary; policy only), io.final_obs non-NULL = SALP_EVAL_ACCUMULATE;  kOutNav — io.obs is
-//        the block of navigation records (kSigNav; deterministic policy, one food, forced breathing: the caller has checked),
-//        io.final_obs as for the summary, io.nav_line / nav_radius / nav_track the trial lines, the goal radius and the track
+//   out: kOutStreams — the per-step streams of io, the signature follows from which are present;  kOutPacked — record_block(io)
+//        holds transition records (kSigPacked), packed_has_final(io) asks for the terminal-observation tail;  kOutSummary —
+//        record_block(io) holds summary records (kSigSummary; policy only), accumulate(io) = SALP_EVAL_ACCUMULATE;  kOutNav —
+//        record_block(io) holds navigation records (kSigNav; deterministic policy, one food, forced breathing: the caller has
+//        checked), accumulate(io) as for the summary, io.nav_line / nav_radius / nav_track the trial lines, the goal radius and
+//        the track.  (set_record_block / set_policy_block and the readers: salp_rollout_traits.h, next to IOPtrs.)
 //   act: ACT_READ — io.act, or generated in the kernel when that is NULL (only reached when can_generate_in_kernel());
-//        ACT_POLICY / ACT_POLICY_SAMPLED — io.act is a policy's device block (the caller has checked K = 3 and the four main
-//        outputs; ACT_POLICY_SAMPLED: a Gaussian policy, io.logp_out may be set)
+//        ACT_POLICY / ACT_POLICY_SAMPLED — io.act is a policy's device block (set_policy_block) (the caller has checked K = 3 and the
+//        four main outputs; ACT_POLICY_SAMPLED: a Gaussian policy, io.logp_out may be set)
 enum { kOutStreams = 0, kOutPacked = 1, kOutSummary = 2, kOutNav = 3 };
 struct RolloutKind { int out, act; };
 
 int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, RolloutKind kind) {
   const bool policy = kind.act >= ACT_POLICY;
   const bool main_outputs = io.obs && io.reward && io.terminated && io.truncated;
-  // (policy: final_obs / info do not exist — io.final_obs is the summary's accumulate flag, io.info's slot holds logp_out)
+  // (policy: final_obs / info do not exist — io.final_obs is accumulate(io), io.info's slot holds logp_out)
   const bool extras = !policy && (io.final_obs || io.info);
   const int sig = kind.out == kOutNav ? kSigNav : kind.out == kOutSummary ? kSigSummary : kind.out == kOutPacked ? kSigPacked
                 : (!main_outputs ? kSigPartial : (extras ? kSigExtras : kSigMain));
@@ -726,10 +727,9 @@ static int packed_impl(salp_vec_t* h, const float* act, int32_t H, float* rec, f
   hipStream_t st = (hipStream_t)stream;
   h->last_stream = st;
   const bool with_final = (flags & SALP_REC_FINAL_OBS) != 0;
-  const int W = h->obs_dim + SALP_REC_EXTRA_COLS;
   IOPtrs io = io_for(h);
   auto launch = [&](const float* d_act, float* d_gen, float* d_rec) {   // d_gen: where generated actions go (NULL: the handle's buffer)
-    io.act = d_act; io.obs = d_rec; io.final_obs = with_final ? d_rec + W : nullptr;
+    io.act = d_act; set_record_block(io, d_rec, with_final);
     if (!act) {
       int rc = generate_actions(h, H, d_gen, st, &io.act);
       if (rc != SALP_OK) return rc;
@@ -909,7 +909,7 @@ static int rollout_policy_impl(salp_vec_t* h, const salp_policy_t* pol, int32_t 
   hipStream_t st = (hipStream_t)stream;
   h->last_stream = st;
   IOPtrs io = io_for(h);
-  io.act = pol->block;
+  set_policy_block(io, pol->block);
   auto launch = [&](float* d_obs, float* d_rew, uint8_t* d_term, uint8_t* d_trunc, float* d_aout, float* d_logp) {
     io.obs = d_obs; io.reward = d_rew; io.terminated = d_term; io.truncated = d_trunc; io.act_out = d_aout;
     if (sampled) io.logp_out = d_logp;
@@ -951,9 +951,9 @@ static int evaluate_policy_impl(salp_vec_t* h, const salp_policy_t* pol, int32_t
   h->last_stream = st;
   const bool accumulate = (flags & SALP_EVAL_ACCUMULATE) != 0;
   IOPtrs io = io_for(h);
-  io.act = pol->block;
+  set_policy_block(io, pol->block);
   auto launch = [&](float* d_rec) {
-    io.obs = d_rec; io.final_obs = accumulate ? d_rec : nullptr;
+    set_record_block(io, d_rec, accumulate);
     return run_rollout(h, io, H, st, {kOutSummary, sampled ? ACT_POLICY_SAMPLED : ACT_POLICY}, pol);
   };
   if (flags & SALP_DEVICE_PTRS) return launch((float*)rec);
@@ -992,10 +992,10 @@ int salp_vec_evaluate_navigation(salp_vec_t* h, const salp_policy_t* pol, int32_
   h->last_stream = st;
   const bool accumulate = (flags & SALP_EVAL_ACCUMULATE) != 0;
   IOPtrs io = io_for(h);
-  io.act = pol->block;
+  set_policy_block(io, pol->block);
   io.nav_radius = goal_radius;       // (shares its bytes with global_step, which only generated actions read)
   auto launch = [&](const double* d_line, float* d_rec, double* d_track) {
-    io.nav_line = d_line; io.obs = d_rec; io.final_obs = accumulate ? d_rec : nullptr; io.nav_track = d_track;
+    io.nav_line = d_line; set_record_block(io, d_rec, accumulate); io.nav_track = d_track;
     return run_rollout(h, io, H, st, {kOutNav, ACT_POLICY}, pol);
   };
   if (flags & SALP_DEVICE_PTRS) return launch(line, (float*)rec, track);
