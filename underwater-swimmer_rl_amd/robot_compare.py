@@ -14,7 +14,8 @@ from __future__ import annotations
 import ctypes
 import threading
 
-from .robot_env import CRobotConfig, SalpRobotVectorEnv, _check, _lib
+from . import _capi
+from .robot_env import CRobotConfig, SalpRobotVectorEnv
 
 # rows of the parameter table, SALP_RP_* of include/salp_robot.h (names = salp_robot_config_t fields)
 ROBOT_PARAM_NAMES = ("dry_mass", "init_length", "init_width", "max_contraction", "density", "drag_coefficient_min",
@@ -27,9 +28,8 @@ MAX_TRAJECTORY_CYCLES = 1024   # SALP_ROBOT_MAX_TRAJECTORY_CYCLES
 
 
 def _default_config() -> CRobotConfig:
-    L = _lib()
     cfg = CRobotConfig()
-    _check(L, L.salp_robot_config_default(ctypes.byref(cfg)), "salp_robot_config_default")
+    _capi.call(_capi.load_library(), "salp_robot_config_default", ctypes.byref(cfg))
     return cfg
 
 
@@ -145,10 +145,8 @@ def compare_actions_with_states(actions, expected_states=None, params=None, *, n
     states = None if metrics_only else torch.empty((T, n, 6), dtype=torch.float64, device=dev)
     inner = None if metrics_only else torch.empty((T, n), dtype=torch.int32, device=dev)
     metrics = None if x is None else torch.empty((n, len(METRIC_NAMES)), dtype=torch.float64, device=dev)
-    p = SalpRobotVectorEnv._p
     flags = 1 | (PER_ROBOT_ACTIONS if per_robot else 0)
-    _check(env.L, env.L.salp_robot_vec_trajectory(env._h, p(params), p(a), int(T), p(x), p(states), p(metrics), p(inner),
-                                                   flags, env._stream), "salp_robot_vec_trajectory")
+    _capi.call(env.L, "salp_robot_vec_trajectory", env._h, params, a, int(T), x, states, metrics, inner, flags, env._stream)
     out = {}
     if states is not None:
         out["actual_states"] = states.transpose(0, 1)

@@ -25,12 +25,14 @@ C ABI.  If the HIP library or a GPU is missing the constructor raises — there 
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Any, Dict, Optional, Sequence, Union
 
 import numpy as np
 
 from . import _capi
-from ._capi import SALP_DEVICE_PTRS, SalpLib
+from ._arrays import ArrayBackend, device_index
+from ._capi import SalpLib
 from .config import SalpSnakeConfig, load_env_config
 from .spaces import batch_space, single_action_space, single_observation_space
 
@@ -45,7 +47,7 @@ def _as_config(cfg: ConfigLike, **overrides) -> SalpSnakeConfig:
     return SalpSnakeConfig(**{**cfg, **overrides})
 
 
-class SalpVectorEnv:
+class SalpVectorEnv(ArrayBackend):
     metadata = {"render_modes": [], "autoreset_mode": "same-step"}
 
     def __init__(self, config: ConfigLike = "single_food", num_envs: int = 4096, device: Union[str, int] = "cuda:0",
@@ -55,8 +57,7 @@ class SalpVectorEnv:
         self.output = output
         if output not in ("torch", "numpy"):
             raise ValueError("output must be 'torch' or 'numpy'")
-        self._device_index = int(str(device).split(":")[1]) if isinstance(device, str) and ":" in str(device) else (
-            int(device) if not isinstance(device, str) else 0)
+        self._device_index = device_index(device)
         self.seed_value = int(seed)
         self.env_index_base = int(env_index_base)
         self._lib = SalpLib(self.cfg, self.num_envs, self._device_index, self.seed_value, self.env_index_base)
@@ -65,49 +66,64 @@ class SalpVectorEnv:
         self.single_action_space = single_action_space(self.cfg)
         self.observation_space = batch_space(self.single_observation_space, self.num_envs)
         self.action_space = batch_space(self.single_action_space, self.num_envs)
-        self._torch = None
-        if output == "torch":
-            import torch
-            if not torch.cuda.is_available():
-                raise _capi.SalpError("output='torch' needs a ROCm GPU visible to PyTorch")
-            self._torch = torch
-            self.device = torch.device("cuda", self._device_index)
-        else:
-            self.device = None
+        self._init_arrays(output, self._device_index)
         self._bufs: Dict[str, Any] = {}
+        self._reset_caches()
+
+    def _reset_caches(self):
+        self._step_cache = None       # _prepare_step: the step outputs and their raw pointers
+        self._packed_cache = {}       # with_final -> the same for step_packed
+        self._policy_cache = {}       # id(policy object) -> (policy object, its handle)
 
     # ------------------------------------------------------------------ buffers
     def _buf(self, name, shape, dtype):
         b = self._bufs.get(name)
         if b is None or tuple(b.shape) != tuple(shape):
-            if self._torch is not None:
-                td = {np.float32: self._torch.float32, np.uint8: self._torch.uint8, np.int32: self._torch.int32,
-                      np.float64: self._torch.float64}[dtype]
-                b = self._torch.empty(shape, dtype=td, device=self.device)
-            else:
-                b = np.empty(shape, dtype=dtype)
-            self._bufs[name] = b
+            b = self._bufs[name] = self._empty(shape, dtype)
         return b
 
-    @property
-    def _flags(self):
-        return SALP_DEVICE_PTRS if self._torch is not None else 0
+    def _out(self, out, key, shape, dtype):
+        """The caller's `out[key]` (None included) if it gave one, else the env-owned rollout buffer of that name."""
+        return out[key] if out and key in out else self._buf("r_" + key, shape, dtype)
 
-    @property
-    def _stream(self):
-        if self._torch is None:
-            return 0
-        return int(self._torch.cuda.current_stream(self.device).cuda_stream)
+    def _main_outputs(self, out, H, want_obs=True):
+        n = self.num_envs
+        obs = self._out(out, "obs", (H, n, self.obs_dim), np.float32) if want_obs or (out and "obs" in out) else None
+        return (obs, self._out(out, "reward", (H, n), np.float32), self._out(out, "terminated", (H, n), np.uint8),
+                self._out(out, "truncated", (H, n), np.uint8))
 
-    def _actions_in(self, actions, lead_shape):
-        shape = tuple(lead_shape) + (self.act_dim,)
-        if self._torch is not None:
-            t = self._torch
-            if not isinstance(actions, t.Tensor):
-                actions = t.as_tensor(np.asarray(actions, dtype=np.float32))
-            a = actions.to(device=self.device, dtype=t.float32).reshape(shape).contiguous()
-            return a
-        return np.ascontiguousarray(np.asarray(actions, dtype=np.float32).reshape(shape))
+    def _step_actions(self, actions):
+        """(the action block, its address, the current stream) for the direct ctypes call of `step` / `step_packed`: a
+        contiguous float32 tensor on this GPU is taken as it is, anything else is converted."""
+        t = self._torch
+        if t is not None and isinstance(actions, t.Tensor) and actions.is_cuda and actions.device == self.device \
+                and actions.dtype == t.float32 and actions.is_contiguous() \
+                and actions.numel() == self.num_envs * self.act_dim:
+            return actions, actions.data_ptr(), t.cuda.current_stream(self.device).cuda_stream
+        a = self._actions_in(actions, (self.num_envs, self.act_dim))
+        return a, _capi.address(a), self._stream
+
+    def _rollout_actions(self, actions, horizon):
+        """(actions in, the buffer for device-generated actions, H) of an open-loop rollout: one of the first two is None."""
+        if actions is not None:
+            H = int(actions.shape[0]) if hasattr(actions, "shape") else len(actions)
+            return self._actions_in(actions, (H, self.num_envs, self.act_dim)), None, H
+        if horizon is None:
+            raise ValueError("horizon is required when actions is None")
+        H = int(horizon)
+        return None, self._buf("r_actions", (H, self.num_envs, self.act_dim), np.float32), H
+
+    def _policy_handle(self, policy):
+        """`policy` if it is a handle, else the handle made for that policy object at its first use (kept until close())."""
+        if isinstance(policy, _capi.PolicyHandle):
+            return policy
+        if id(policy) not in self._policy_cache:
+            self._policy_cache[id(policy)] = (policy, self.make_policy(policy))
+        return self._policy_cache[id(policy)][1]
+
+    def _record_block(self, out, words):
+        """The int32 [N, words] block of an evaluation call: `out` (a block, or the dict returned earlier) or a new one."""
+        return self._out_block(out["record"] if isinstance(out, dict) else out, (self.num_envs, words), np.int32)
 
     # ------------------------------------------------------------------ Gymnasium surface
     def reset(self, *, seed: Optional[int] = None, options: Optional[dict] = None, mask=None):
@@ -117,28 +133,20 @@ class SalpVectorEnv:
         destroyed and re-created the handle: a hipGraph captured earlier then replayed into freed memory), so graphs from
         `capture_policy_steps` / `train_sac_graphed` stay valid across `reset(seed=...)`; a poked base_num_food_items
         survives.  A seed restarts EVERY env's stream, so it cannot be combined with a partial `mask`."""
+        obs = self._buf("obs", (self.num_envs, self.obs_dim), np.float32)
         if seed is not None:      # any explicit seed restarts the draw streams: reset(seed=s) twice gives the same episodes
             if mask is not None and not bool(np.all(np.asarray(mask.cpu() if hasattr(mask, "cpu") else mask))):
                 raise ValueError("reset(seed=..., mask=...) with a partial mask: a seed re-keys the draw streams of ALL envs; "
                                  "reseed with mask=None, or reset the subset without a seed")
             self.seed_value = int(seed)
-            obs = self._buf("obs", (self.num_envs, self.obs_dim), np.float32)
             self._lib.reseed(self.seed_value, obs, self._flags, self._stream)
-            return obs, {}
-        obs = self._buf("obs", (self.num_envs, self.obs_dim), np.float32)
-        m = None
-        if mask is not None:
-            if self._torch is not None:
-                m = self._torch.as_tensor(mask).to(device=self.device, dtype=self._torch.uint8).contiguous()
-            else:
-                m = np.ascontiguousarray(np.asarray(mask, dtype=np.uint8))
-        self._lib.reset(m, obs, self._flags, self._stream)
+        else:
+            self._lib.reset(self._mask_in(mask), obs, self._flags, self._stream)
         return obs, {}
 
     def _prepare_step(self):
         """Allocates the step outputs once and caches their raw pointers (the per-call cost of
         `step` is then one ctypes call: at H = 1 the host, not the kernel, is the bottleneck)."""
-        import ctypes
         n = self.num_envs
         obs = self._buf("obs", (n, self.obs_dim), np.float32)
         rew = self._buf("reward", (n,), np.float32)
@@ -146,59 +154,35 @@ class SalpVectorEnv:
         trunc = self._buf("truncated", (n,), np.uint8)
         info_i = self._buf("info", (n, _capi.INFO_COLS), np.int32)
         fin = self._buf("final_obs", (n, self.obs_dim), np.float32)
-        ptr = (lambda t: ctypes.c_void_p(t.data_ptr())) if self._torch is not None else \
-              (lambda a: a.ctypes.data_as(ctypes.c_void_p))
-        if self._torch is not None:
-            term_b, trunc_b = term.view(self._torch.bool), trunc.view(self._torch.bool)   # zero-copy 0/1 bytes
-            done = self._torch.empty((n,), dtype=self._torch.bool, device=self.device)
-        else:
-            term_b, trunc_b = term.view(np.bool_), trunc.view(np.bool_)
-            done = np.empty((n,), dtype=np.bool_)
+        done = self._empty((n,), np.bool_)
         info = {"food_collected": info_i[:, 0], "steps_since_food": info_i[:, 1], "collision": info_i[:, 2],
                 "final_observation": fin, "_final_observation": done}
-        self._step_cache = dict(obs=obs, rew=rew, term=term_b, trunc=trunc_b, info=info, done=done,
+        ptr = lambda x: ctypes.c_void_p(_capi.address(x))
+        self._step_cache = dict(obs=obs, rew=rew, term=self._bool_view(term), trunc=self._bool_view(trunc), info=info, done=done,
                                 p_obs=ptr(obs), p_rew=ptr(rew), p_term=ptr(term), p_trunc=ptr(trunc),
                                 p_fin=ptr(fin), p_info=ptr(info_i), fn=self._lib.lib.salp_vec_step, h=self._lib._h,
-                                flags=self._flags, vp=ctypes.c_void_p)
+                                flags=self._flags, logical_or=(self._torch or np).logical_or)
+        return self._step_cache
 
     def step(self, actions, want_final_observation: bool = True):
         """One step of every env.  The returned tensors are the env's own output buffers: they are
         overwritten by the next call (clone what must be kept).  `info["score"]` of the reference
         (snake:196) is `info["food_collected"] * food_reward`."""
-        c = getattr(self, "_step_cache", None)
-        if c is None:
-            self._prepare_step()
-            c = self._step_cache
-        t = self._torch
-        if t is not None and isinstance(actions, t.Tensor) and actions.is_cuda and actions.device == self.device \
-                and actions.dtype == t.float32 and actions.is_contiguous() \
-                and actions.numel() == self.num_envs * self.act_dim:
-            a = actions
-            p_act = c["vp"](a.data_ptr())
-            stream = c["vp"](t.cuda.current_stream(self.device).cuda_stream)
-        else:
-            a = self._actions_in(actions, (self.num_envs,))
-            p_act = self._lib._ptr(a)
-            stream = c["vp"](self._stream)
+        c = self._step_cache or self._prepare_step()
+        a, p_act, stream = self._step_actions(actions)
         rc = c["fn"](c["h"], p_act, c["p_obs"], c["p_rew"], c["p_term"], c["p_trunc"],
                      c["p_fin"] if want_final_observation else None, c["p_info"], c["flags"], stream)
         if rc != 0:
             _capi.check(self._lib.lib, rc, "salp_vec_step")
         if want_final_observation:
-            if t is not None:
-                t.logical_or(c["term"], c["trunc"], out=c["done"])
-            else:
-                np.logical_or(c["term"], c["trunc"], out=c["done"])
+            c["logical_or"](c["term"], c["trunc"], out=c["done"])
         return c["obs"], c["rew"], c["term"], c["trunc"], c["info"]
 
     def _prepare_step_packed(self, with_final: bool):
-        import ctypes
         rec = self._buf("rec_final" if with_final else "rec", (self.num_envs, self._lib.record_width(with_final)), np.float32)
-        p_rec = ctypes.c_void_p(rec.data_ptr()) if self._torch is not None else rec.ctypes.data_as(ctypes.c_void_p)
-        c = dict(rec=rec, p_rec=p_rec, fn=self._lib.lib.salp_vec_step_packed, h=self._lib._h, vp=ctypes.c_void_p,
-                 flags=self._flags | (_capi.REC_FINAL_OBS if with_final else 0))
-        self._packed_cache = getattr(self, "_packed_cache", None) or {}
-        self._packed_cache[with_final] = c
+        c = self._packed_cache[with_final] = dict(
+            rec=rec, p_rec=ctypes.c_void_p(_capi.address(rec)), fn=self._lib.lib.salp_vec_step_packed, h=self._lib._h,
+            flags=self._flags | (_capi.REC_FINAL_OBS if with_final else 0))
         return c
 
     def step_packed(self, actions, want_final_observation: bool = True):
@@ -207,18 +191,8 @@ class SalpVectorEnv:
         2 obs_dim + 4 with terminal observations (the tail of an unfinished env's row is not written).  The block is the
         env's own buffer, overwritten by the next call; the per-call cost is one ctypes call, as in `step`."""
         with_final = bool(want_final_observation)
-        c = (getattr(self, "_packed_cache", None) or {}).get(with_final) or self._prepare_step_packed(with_final)
-        t = self._torch
-        if t is not None and isinstance(actions, t.Tensor) and actions.is_cuda and actions.device == self.device \
-                and actions.dtype == t.float32 and actions.is_contiguous() \
-                and actions.numel() == self.num_envs * self.act_dim:
-            a = actions
-            p_act = c["vp"](a.data_ptr())
-            stream = c["vp"](t.cuda.current_stream(self.device).cuda_stream)
-        else:
-            a = self._actions_in(actions, (self.num_envs,))
-            p_act = self._lib._ptr(a)
-            stream = c["vp"](self._stream)
+        c = self._packed_cache.get(with_final) or self._prepare_step_packed(with_final)
+        a, p_act, stream = self._step_actions(actions)
         rc = c["fn"](c["h"], p_act, c["p_rec"], c["flags"], stream)
         if rc != 0:
             _capi.check(self._lib.lib, rc, "salp_vec_step_packed")
@@ -229,19 +203,9 @@ class SalpVectorEnv:
         """`horizon` steps in one kernel launch with the packed records as the only output: dict(record=[H, N, width],
         actions=...).  actions: [H, N, act_dim] or None (device-generated).  `out`: a float32 [H, N, width] block to write
         into (its width must match `want_final_observation`); default an env-owned buffer."""
-        n = self.num_envs
-        if actions is not None:
-            horizon = int(actions.shape[0]) if hasattr(actions, "shape") else len(actions)
-            a = self._actions_in(actions, (horizon, n))
-            aout = None
-        else:
-            if horizon is None:
-                raise ValueError("horizon is required when actions is None")
-            a = None
-            aout = self._buf("r_act", (horizon, n, self.act_dim), np.float32)
-        H = int(horizon)
+        a, aout, H = self._rollout_actions(actions, horizon)
         with_final = bool(want_final_observation)
-        shape = (H, n, self._lib.record_width(with_final))
+        shape = (H, self.num_envs, self._lib.record_width(with_final))
         rec = out if out is not None else self._buf("r_rec_final" if with_final else "r_rec", shape, np.float32)
         if tuple(rec.shape) != shape:
             raise ValueError(f"out has shape {tuple(rec.shape)}; expected {shape}")
@@ -262,10 +226,7 @@ class SalpVectorEnv:
         t = self._torch
         if t is None:
             raise _capi.SalpError("capture_policy_steps needs output='torch'")
-        if getattr(self, "_step_cache", None) is None:
-            self._prepare_step()
-        c = self._step_cache
-        obs = c["obs"]
+        obs = (self._step_cache or self._prepare_step())["obs"]
 
         def body():
             for k in range(int(n_steps)):
@@ -295,26 +256,9 @@ class SalpVectorEnv:
     def rollout(self, actions=None, horizon: Optional[int] = None, want_obs: bool = True,
                 want_final_observation: bool = False, out: Optional[dict] = None) -> dict:
         """`horizon` steps in one kernel launch.  actions: [H, N, act_dim] or None (device-generated)."""
-        n = self.num_envs
-        if actions is not None:
-            if hasattr(actions, "shape"):
-                horizon = int(actions.shape[0])
-            else:
-                horizon = len(actions)
-            a = self._actions_in(actions, (horizon, n))
-            aout = None
-        else:
-            if horizon is None:
-                raise ValueError("horizon is required when actions is None")
-            a = None
-            aout = self._buf("r_act", (horizon, n, self.act_dim), np.float32)
-        H = int(horizon)
-        out = out or {}
-        obs = out.get("obs") if "obs" in out else (self._buf("r_obs", (H, n, self.obs_dim), np.float32) if want_obs else None)
-        rew = out.get("reward") if "reward" in out else self._buf("r_reward", (H, n), np.float32)
-        term = out.get("terminated") if "terminated" in out else self._buf("r_term", (H, n), np.uint8)
-        trunc = out.get("truncated") if "truncated" in out else self._buf("r_trunc", (H, n), np.uint8)
-        fin = self._buf("r_final", (H, n, self.obs_dim), np.float32) if want_final_observation else None
+        a, aout, H = self._rollout_actions(actions, horizon)
+        obs, rew, term, trunc = self._main_outputs(out, H, want_obs)
+        fin = self._buf("r_final", (H, self.num_envs, self.obs_dim), np.float32) if want_final_observation else None
         self._lib.rollout(a, H, obs, rew, term, trunc, fin, aout, self._flags, self._stream)
         return dict(obs=obs, reward=rew, terminated=term, truncated=trunc, final_obs=fin,
                     actions=a if a is not None else aout)
@@ -335,22 +279,14 @@ class SalpVectorEnv:
         ([H, N, act_dim], None without `want_actions`).  `sample=True` (a `GaussianPolicy`): the actions are sampled in
         the kernel (tanh-Gaussian, the policy's noise stream) and the dict gains `logp` [H, N]; with `sample=False` a
         Gaussian policy runs its mean."""
-        if not isinstance(policy, _capi.PolicyHandle):
-            cache = self.__dict__.setdefault("_policy_cache", {})
-            if id(policy) not in cache:
-                cache[id(policy)] = (policy, self.make_policy(policy))
-            policy = cache[id(policy)][1]
+        policy = self._policy_handle(policy)
         H, n = int(horizon), self.num_envs
         if H < 1:
             raise ValueError("horizon must be >= 1")
-        out = out or {}
-        obs = out.get("obs") if "obs" in out else self._buf("r_obs", (H, n, self.obs_dim), np.float32)
-        rew = out.get("reward") if "reward" in out else self._buf("r_reward", (H, n), np.float32)
-        term = out.get("terminated") if "terminated" in out else self._buf("r_term", (H, n), np.uint8)
-        trunc = out.get("truncated") if "truncated" in out else self._buf("r_trunc", (H, n), np.uint8)
-        aout = (out.get("actions") if "actions" in out else self._buf("r_act", (H, n, self.act_dim), np.float32)) if want_actions else None
+        obs, rew, term, trunc = self._main_outputs(out, H)
+        aout = self._out(out, "actions", (H, n, self.act_dim), np.float32) if want_actions else None
         if sample:
-            logp = out.get("logp") if "logp" in out else self._buf("r_logp", (H, n), np.float32)
+            logp = self._out(out, "logp", (H, n), np.float32)
             self._lib.rollout_policy_sampled(policy, H, obs, rew, term, trunc, aout, logp, self._flags, self._stream)
             return dict(obs=obs, reward=rew, terminated=term, truncated=trunc, final_obs=None, actions=aout, logp=logp)
         self._lib.rollout_policy(policy, H, obs, rew, term, trunc, aout, self._flags, self._stream)
@@ -366,27 +302,13 @@ class SalpVectorEnv:
         the bits of one call.  A policy's score: `return_sum.view(P, E).mean(1)`.  `sample=True` (a `GaussianPolicy`):
         the run takes the policy's sampled actions, as `rollout_policy(..., sample=True)` would."""
         from .policy import EVAL_WORDS, evaluation_views
-        if not isinstance(policy, _capi.PolicyHandle):
-            cache = self.__dict__.setdefault("_policy_cache", {})
-            if id(policy) not in cache:
-                cache[id(policy)] = (policy, self.make_policy(policy))
-            policy = cache[id(policy)][1]
-        H, n = int(horizon), self.num_envs
+        policy = self._policy_handle(policy)
+        H = int(horizon)
         if H < 1:
             raise ValueError("horizon must be >= 1")
         if accumulate and out is None:
             raise ValueError("accumulate=True continues the records in `out`: pass the block of the call before")
-        rec = out["record"] if isinstance(out, dict) else out
-        if rec is None:
-            rec = (self._torch.empty((n, EVAL_WORDS), dtype=self._torch.int32, device=self.device) if self._torch is not None
-                   else np.empty((n, EVAL_WORDS), np.int32))
-        if self._torch is not None:        # the pointer goes to the kernel as a device pointer: it must be one, on this GPU
-            if not isinstance(rec, self._torch.Tensor) or rec.device != self.device:
-                raise ValueError(f"out must be a torch tensor on {self.device}")
-        elif not isinstance(rec, np.ndarray):
-            raise ValueError("out must be a numpy array (this env returns host arrays)")
-        if tuple(rec.shape) != (n, EVAL_WORDS):
-            raise ValueError(f"out must be an int32 [{n}, {EVAL_WORDS}] block")
+        rec = self._record_block(out, EVAL_WORDS)
         views = evaluation_views(rec)       # checks dtype and contiguity
         call = self._lib.evaluate_policy_sampled if sample else self._lib.evaluate_policy
         call(policy, H, rec, self._flags | (_capi.EVAL_ACCUMULATE if accumulate else 0), self._stream)
@@ -416,7 +338,7 @@ class SalpVectorEnv:
         # a float64 [N, 4] tensor on this GPU is taken as it is (nothing is copied or allocated for it: capturable)
         on_device = t is not None and isinstance(line, t.Tensor) and line.device == self.device
         if on_device:
-            if line.dtype != t.float64 or tuple(line.shape) != (n, 4) or not line.is_contiguous():
+            if not self._is_block(line, (n, 4), np.float64):
                 raise ValueError(f"a device line must be a contiguous float64 [{n}, 4] tensor")
             ln = line
         else:
@@ -424,36 +346,17 @@ class SalpVectorEnv:
         cfg = self.cfg
         if cfg.num_food_items != 1 or not cfg.forced_breathing or not cfg.no_autoreset or cfg.max_observed_food != 3:
             raise ValueError("evaluate_navigation needs num_food_items == 1, forced breathing, max_observed_food == 3 and no_autoreset")
-        if not isinstance(policy, _capi.PolicyHandle):
-            cache = self.__dict__.setdefault("_policy_cache", {})
-            if id(policy) not in cache:
-                cache[id(policy)] = (policy, self.make_policy(policy))
-            policy = cache[id(policy)][1]
-        rec = out["record"] if isinstance(out, dict) else out
-        if rec is None:
-            rec = (t.empty((n, NAV_WORDS), dtype=t.int32, device=self.device) if t is not None else np.empty((n, NAV_WORDS), np.int32))
-        if t is not None:        # the pointer goes to the kernel as a device pointer: it must be one, on this GPU
-            if not isinstance(rec, t.Tensor) or rec.device != self.device:
-                raise ValueError(f"out must be a torch tensor on {self.device}")
-        elif not isinstance(rec, np.ndarray):
-            raise ValueError("out must be a numpy array (this env returns host arrays)")
-        if tuple(rec.shape) != (n, NAV_WORDS):
-            raise ValueError(f"out must be an int32 [{n}, {NAV_WORDS}] block")
+        policy = self._policy_handle(policy)
+        rec = self._record_block(out, NAV_WORDS)
         views = navigation_views(rec)       # checks dtype and contiguity
         want_track = track is not None and track is not False
         given = want_track and track is not True       # a block to write into: float64 [H, N, 2], on this GPU for a torch env
-        if t is not None:
-            if not on_device:
-                ln = t.from_numpy(ln).to(self.device)
-            if given and (not isinstance(track, t.Tensor) or track.device != self.device or track.dtype != t.float64 or
-                          tuple(track.shape) != (H, n, 2) or not track.is_contiguous()):
-                raise ValueError(f"a track block must be a contiguous float64 [{H}, {n}, 2] tensor on {self.device}")
-            trk = track if given else (t.empty((H, n, 2), dtype=t.float64, device=self.device) if want_track else None)
-        else:
-            if given and (not isinstance(track, np.ndarray) or track.dtype != np.float64 or track.shape != (H, n, 2) or
-                          not track.flags.c_contiguous):
-                raise ValueError(f"a track block must be a contiguous float64 [{H}, {n}, 2] array")
-            trk = track if given else (np.empty((H, n, 2), np.float64) if want_track else None)
+        if t is not None and not on_device:
+            ln = t.from_numpy(ln).to(self.device)
+        if given and not self._is_block(track, (H, n, 2), np.float64):
+            raise ValueError(f"a track block must be a contiguous float64 [{H}, {n}, 2] " +
+                             ("array" if t is None else f"tensor on {self.device}"))
+        trk = track if given else (self._empty((H, n, 2), np.float64) if want_track else None)
         self._lib.evaluate_navigation(policy, H, ln, radius, rec, trk, self._flags | (_capi.EVAL_ACCUMULATE if accumulate else 0),
                                       self._stream)
         if want_track:
@@ -466,11 +369,9 @@ class SalpVectorEnv:
         return obs
 
     def close(self):
-        self.__dict__.pop("_policy_cache", None)
         self._lib.close()
         self._bufs.clear()
-        self._step_cache = None
-        self._packed_cache = None
+        self._reset_caches()
 
     # ------------------------------------------------------------------ state access
     def get_state(self):
