@@ -8,6 +8,7 @@ the oracle until every case ends episodes by wall and by truncation in mixed wav
 actions beyond +-0.9 and keeps `error_bound` below 1e-4 (tests/test_policy_rollout.py asserts all of it).
 """
 import functools
+import sys
 
 import numpy as np
 
@@ -72,26 +73,58 @@ def squashed(policy, actions):
     return (np.asarray(actions, np.float64) - policy.shift.astype(np.float64)[0]) / policy.scale.astype(np.float64)[0]
 
 
+def start_snapshot(name, cases=None):
+    """c, cfg, policy and the injected start state of a case of the table `cases` (a module with CASES, case_cfg and
+    case_policy; default: this one)."""
+    cases = cases or sys.modules[__name__]
+    c, cfg = cases.CASES[name], cases.case_cfg(name)
+    orc, f64, i32 = pc.start_oracle(cfg, c["n"], pc.ENV_SEED)
+    orc.close()
+    return c, cfg, cases.case_policy(name), f64, i32
+
+
+def separated_population(P):
+    """P policies 24 -> 16 -> 1 whose outputs are far apart on every observation: small weights, output biases spread over
+    [-0.9, 0.9] (|W h| stays below 0.15, so two policies' pre-activations differ by at least 0.3)."""
+    ps = []
+    for k in range(P):
+        p = random_policy(24, 1, (16,), "tanh", 200 + k, 0.5, 0.1)
+        (W0, b0), (W1, b1) = p.layers
+        b1 = np.full_like(b1, -0.9 + 1.8 * k / max(P - 1, 1))
+        ps.append(MLPPolicy([(W0, b0), (W1, b1)], p.scale, p.shift, "tanh"))
+    return ps
+
+
+def drive_oracle(orc, horizon, act_fn):
+    """Steps the oracle closed-loop: act_fn(t, obs) -> (float32 actions [n, act_dim], anything to keep for step t).
+    Returns obs_in [horizon, n, OD] (what each action saw), actions, the oracle's outputs with `info`, and the list of
+    what act_fn kept."""
+    n = orc.n
+    obs_in = np.empty((horizon, n, orc.obs_dim), np.float32)
+    actions = np.empty((horizon, n, orc.act_dim), np.float32)
+    outs = dict(obs=np.empty((horizon, n, orc.obs_dim), np.float32), terminated=np.empty((horizon, n), np.uint8),
+                truncated=np.empty((horizon, n), np.uint8), info=np.empty((horizon, n, 3), np.int32))
+    extras = []
+    o = orc.observe()
+    for t in range(horizon):
+        obs_in[t] = o
+        actions[t], extra = act_fn(t, o)
+        extras.append(extra)
+        s = orc.step(actions[t])
+        for k in outs:
+            outs[k][t] = s[k]
+        o = s["obs"]
+    return obs_in, actions, outs, extras
+
+
 @functools.lru_cache(maxsize=None)
 def oracle_closed_loop(name):
     """The oracle stepped closed-loop under `reference()` (rounded to float32) from the injected start state: computed
     once, shared, read-only.  Returns cfg, policy, start snapshot, and the run: obs_in [H, n, OD] (what each action saw),
     actions, and the oracle's outputs with `info`."""
     c, cfg, policy = CASES[name], case_cfg(name), case_policy(name)
-    n = c["n"]
-    orc, f64, i32 = pc.start_oracle(cfg, n, pc.ENV_SEED)
-    obs_in = np.empty((H, n, cfg.obs_dim), np.float32)
-    actions = np.empty((H, n, cfg.act_dim), np.float32)
-    outs = dict(obs=np.empty((H, n, cfg.obs_dim), np.float32), terminated=np.empty((H, n), np.uint8),
-                truncated=np.empty((H, n), np.uint8), info=np.empty((H, n, 3), np.int32))
-    o = orc.observe()
-    for t in range(H):
-        obs_in[t] = o
-        actions[t] = policy.reference(o).astype(np.float32)
-        s = orc.step(actions[t])
-        for k in outs:
-            outs[k][t] = s[k]
-        o = s["obs"]
+    orc, f64, i32 = pc.start_oracle(cfg, c["n"], pc.ENV_SEED)
+    obs_in, actions, outs, _ = drive_oracle(orc, H, lambda t, o: (policy.reference(o).astype(np.float32), None))
     orc.close()
     for a in (f64, i32, obs_in, actions, *outs.values()):
         a.setflags(write=False)

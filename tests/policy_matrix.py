@@ -20,6 +20,7 @@ import numpy as np
 
 import oracle_lib as ol
 import parity_cases as pc
+from policy_cases import drive_oracle
 from underwater_swimmer_rl_amd.policy import MLPPolicy, U
 
 H = 64                      # compared steps per entry (on the GPU behind one call of horizon 1, tests/test_gpu_policy_matrix.py)
@@ -198,20 +199,12 @@ def oracle_closed_loop(name):
     policy, n = entry_policy(name), e["n"]
     orc = ol.OracleVec(cfg, n, seed=pc.ENV_SEED)
     orc.set_state(f64, i32)
-    obs_in = np.empty((H, n, cfg.obs_dim), np.float32)
-    u = np.empty((H, n, cfg.act_dim), np.float32)
-    a = np.empty_like(u)
-    outs = dict(obs=np.empty((H, n, cfg.obs_dim), np.float32), terminated=np.empty((H, n), np.uint8),
-                truncated=np.empty((H, n), np.uint8), info=np.empty((H, n, 3), np.int32))
-    o, subnormals = orc.observe(), 0
-    for t in range(H):
-        obs_in[t] = o
-        u[t], a[t], sub = ol.policy_forward(policy, o)
-        subnormals += sub
-        s = orc.step(a[t])
-        for k in outs:
-            outs[k][t] = s[k]
-        o = s["obs"]
+
+    def act(t, o):
+        u, a, sub = ol.policy_forward(policy, o)
+        return a, (u, sub)
+    obs_in, a, outs, kept = drive_oracle(orc, H, act)
+    u, subnormals = np.stack([k[0] for k in kept]), sum(k[1] for k in kept)
     orc.close()
     for arr in (f64, i32, obs_in, u, a, *outs.values()):
         arr.setflags(write=False)

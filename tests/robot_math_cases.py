@@ -146,3 +146,16 @@ def mixed_group_inputs(limit, steps=40, groups=3, lane=17, group=1):
     big = plain.copy()
     big[steps, 64 * group + lane] = 1.2 * limit
     return plain, big
+
+
+def random_robot_params(rng, n):
+    """[12, n] robot parameter columns: the defaults scaled by uniform(0.5, 1.5), kept consistent (drag min < max, the
+    contraction at most half the length) — the random parameter box of the trajectory tests."""
+    from underwater_swimmer_rl_amd.robot_compare import ROBOT_PARAM_NAMES, robot_params
+    d = robot_params(1, "cpu").numpy()[:, 0]
+    P = d[:, None] * rng.uniform(0.5, 1.5, (12, n))
+    j = {name: i for i, name in enumerate(ROBOT_PARAM_NAMES)}
+    lo, hi = np.minimum(P[j["drag_coefficient_min"]], P[j["drag_coefficient_max"]]), np.maximum(P[j["drag_coefficient_min"]], P[j["drag_coefficient_max"]])
+    P[j["drag_coefficient_min"]], P[j["drag_coefficient_max"]] = lo, hi + 1e-3
+    P[j["max_contraction"]] = np.minimum(P[j["max_contraction"]], 0.5 * P[j["init_length"]])
+    return P

@@ -4,6 +4,7 @@ import ctypes
 import numpy as np
 
 import oracle_lib as ol
+from oracle_lib import _p
 
 R_POS, R_VEL, R_EULER, R_OMEGA, R_VEL_WORLD, R_PREV_I, R_TARGET, R_PREV_DIST, R_VOLUME, R_ANGLE1, R_ANGLE2, R_TIME, \
     R_CYCLE, R_RNG, R_COUNT = 0, 3, 6, 9, 12, 15, 18, 20, 21, 22, 23, 24, 25, 26, 27
@@ -28,10 +29,6 @@ def default_robot_config() -> CRobotConfig:
     c.nozzle_length1 = c.nozzle_length2 = c.nozzle_length3 = 0.05
     c.nozzle_area, c.nozzle_mass, c.nozzle_gamma, c.max_cycles = 0.00016, 1.0, np.pi / 4, 500
     return c
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 class RobotOracleVec:

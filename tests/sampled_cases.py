@@ -95,20 +95,12 @@ def oracle_closed_loop(name):
     n = c["n"]
     z = case_noise(policy, n)
     orc, f64, i32 = pc.start_oracle(cfg, n, pc.ENV_SEED)
-    obs_in = np.empty((H, n, cfg.obs_dim), np.float32)
-    actions = np.empty((H, n, cfg.act_dim), np.float32)
-    logp = np.empty((H, n), np.float64)
-    outs = dict(obs=np.empty((H, n, cfg.obs_dim), np.float32), terminated=np.empty((H, n), np.uint8),
-                truncated=np.empty((H, n), np.uint8), info=np.empty((H, n, 3), np.int32))
-    o = orc.observe()
-    for t in range(H):
-        obs_in[t] = o
+
+    def act(t, o):
         a, lp = policy.reference(o, z[t])
-        actions[t], logp[t] = a.astype(np.float32), lp
-        s = orc.step(actions[t])
-        for k in outs:
-            outs[k][t] = s[k]
-        o = s["obs"]
+        return a.astype(np.float32), lp
+    obs_in, actions, outs, logp = dc.drive_oracle(orc, H, act)
+    logp = np.array(logp, np.float64)
     orc.close()
     for a in (f64, i32, z, obs_in, actions, logp, *outs.values()):
         a.setflags(write=False)

@@ -7,13 +7,14 @@ Layout under test (include/salp_vec.h "Packed transition record"): [obs | reward
 steps_since_food | terminal observation of finished envs], flags bytes = terminated, truncated, collision, 0."""
 import functools
 import os
-import socket
 
 import numpy as np
 import pytest
 
 import oracle_lib as ol
 import parity_cases as pc
+from gpu_support import OBS_TOL, REW_TOL, assert_state_parity, device_state, started
+from support import bits, free_port, obs_diff
 import underwater_swimmer_rl_amd as pkg
 from underwater_swimmer_rl_amd import _capi
 from underwater_swimmer_rl_amd._capi import SalpLib
@@ -21,39 +22,8 @@ from underwater_swimmer_rl_amd.records import record_width, unpack_record
 
 pytestmark = pytest.mark.gpu
 
-OBS_TOL = 1e-5
-REW_TOL = 1e-5
-STATE_TOL = 1e-9
 SENTINEL = 0xA5C3F00D          # guard words behind the block (an unlikely float: -1.7e-16)
 DEV = _capi.SALP_DEVICE_PTRS
-
-
-def obs_diff(cfg, a, b):
-    """|a - b| with the columns that hold an angle / pi compared on the circle (tests/test_gpu_parity.py)."""
-    d = np.abs(a.astype(np.float64) - b.astype(np.float64))
-    for c in [4] + [10 + 4 * s + 3 for s in range(cfg.max_observed_food)]:
-        d[..., c] = np.minimum(d[..., c], 2.0 - d[..., c])
-    return d
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def device_state(dev, cfg):
-    f64 = np.empty((_capi.F_FOOD0 + 2 * cfg.num_food_items, dev.n_envs), np.float64)
-    i32 = np.empty((_capi.I_COUNT, dev.n_envs), np.int32)
-    dev.get_state(f64, i32, 0)
-    return f64, i32
-
-
-def assert_state_parity(cfg, dev, state, label):
-    f_d, i_d = device_state(dev, cfg)
-    f_o, i_o = state
-    assert np.array_equal(i_d, i_o), f"{label}: integer state differs in rows {np.unique(np.nonzero(i_d != i_o)[0])}"
-    assert np.array_equal(np.isnan(f_d), np.isnan(f_o)), f"{label}: food None-pattern differs"
-    d = np.where(np.isnan(f_o), 0.0, np.abs(f_d - f_o))
-    assert d.max() <= STATE_TOL, f"{label}: fp64 state diff {d.max()}"
 
 
 @functools.lru_cache(maxsize=None)
@@ -68,12 +38,6 @@ def reference(name, n, H=pc.HORIZON, cfg_key=None):
     for a in (f64, i32, act, *state, *(v for v in ref.values() if v is not None)):
         a.setflags(write=False)
     return cfg, f64, i32, act, ref, state
-
-
-def started(cfg, n, f64, i32):
-    dev = SalpLib(cfg, n, device_id=0, seed=pc.ENV_SEED)
-    dev.set_state(f64, i32, 0)
-    return dev
 
 
 def run_packed_device(dev, cfg, act, with_final):
@@ -413,14 +377,6 @@ def test_step_packed_is_graph_capturable():
     twin.close()
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 @pytest.mark.parametrize("gather_final", [True, False])
 def test_sharded_step_gathers_the_kernels_records(gather_final):
     """ShardedSalpVectorEnv.step over RCCL (world size 1, shard 1 of 2): the engine's packed records are the collective's
@@ -429,7 +385,7 @@ def test_sharded_step_gathers_the_kernels_records(gather_final):
     import torch.distributed as dist
     from underwater_swimmer_rl_amd.sharded import ShardedSalpVectorEnv
     os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(_free_port())
+    os.environ["MASTER_PORT"] = str(free_port())
     dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
     try:
         n = ENV_N

@@ -7,94 +7,23 @@ Tolerances (north_star: "within 1e-5 fp32"):
     i.e. modulo 2, because -1 and +1 are the same heading — snake:403-407 wraps to [-pi, pi]);
   * reward: |diff| <= 1e-5 * max(1, |reward|);
   * fp64 state snapshot: |diff| <= 1e-9 (only device sin/cos and d^2-vs-sqrt predicates differ).
+The helpers and the tolerances live in tests/gpu_support.py; they are imported by name because the soak scripts reach
+them through this module.
 """
 import numpy as np
 import pytest
 
 import oracle_lib as ol
 import parity_cases as pc
+from gpu_support import (OBS_TOL, REW_TOL, assert_final_obs, assert_parity, assert_state_parity, device_state,   # noqa: F401
+                         run_device, start_pair)
 from parity_cases import CASES, EXPECT_KERNEL, make_actions, make_cfg   # noqa: F401  (the soak scripts reach them through this module)
+from support import obs_diff
 import underwater_swimmer_rl_amd as pkg
 from underwater_swimmer_rl_amd import _capi
 from underwater_swimmer_rl_amd._capi import SalpLib
 
 pytestmark = pytest.mark.gpu
-
-OBS_TOL = 1e-5
-REW_TOL = 1e-5
-STATE_TOL = 1e-9
-
-
-def angle_cols(cfg):
-    return [4] + [10 + 4 * s + 3 for s in range(cfg.max_observed_food)]
-
-
-def obs_diff(cfg, a, b):
-    d = np.abs(a.astype(np.float64) - b.astype(np.float64))
-    for c in angle_cols(cfg):
-        d[..., c] = np.minimum(d[..., c], 2.0 - d[..., c])
-    return d
-
-
-def run_device(cfg, n, act=None, horizon=None, seed=0, base=0, want_final=False, dev=None):
-    own = dev is None
-    if own:
-        dev = SalpLib(cfg, n, device_id=0, seed=seed, env_index_base=base)
-    H = act.shape[0] if act is not None else horizon
-    obs = np.empty((H, n, cfg.obs_dim), np.float32)
-    rew = np.empty((H, n), np.float32)
-    term = np.empty((H, n), np.uint8)
-    trunc = np.empty((H, n), np.uint8)
-    fin = np.full((H, n, cfg.obs_dim), np.nan, np.float32) if want_final else None
-    aout = np.empty((H, n, cfg.act_dim), np.float32) if act is None else None
-    dev.rollout(act, H, obs, rew, term, trunc, fin, aout, 0)
-    out = dict(obs=obs, reward=rew, terminated=term, truncated=trunc, final_obs=fin, actions=aout)
-    return (out, dev) if not own else (out, dev)
-
-
-def get_state(dev, cfg):
-    f64 = np.empty((_capi.F_FOOD0 + 2 * cfg.num_food_items, dev.n_envs), np.float64)
-    i32 = np.empty((_capi.I_COUNT, dev.n_envs), np.int32)
-    dev.get_state(f64, i32, 0)
-    return f64, i32
-
-
-def assert_parity(cfg, got, ref, label=""):
-    assert np.array_equal(got["terminated"], ref["terminated"]), f"{label}: terminated flags differ"
-    assert np.array_equal(got["truncated"], ref["truncated"]), f"{label}: truncated flags differ"
-    d = obs_diff(cfg, got["obs"], ref["obs"])
-    assert d.max() <= OBS_TOL, f"{label}: obs diff {d.max()} at {np.unravel_index(d.argmax(), d.shape)}"
-    rd = np.abs(got["reward"].astype(np.float64) - ref["reward64"]) / np.maximum(1.0, np.abs(ref["reward64"]))
-    assert rd.max() <= REW_TOL, f"{label}: reward diff {rd.max()}"
-    return float(d.max()), float(rd.max())
-
-
-def assert_state_parity(cfg, dev, orc, label=""):
-    f_d, i_d = get_state(dev, cfg)
-    f_o, i_o = orc.get_state()
-    assert np.array_equal(i_d, i_o), f"{label}: integer state differs in rows {np.unique(np.nonzero(i_d != i_o)[0])}"
-    both_nan = np.isnan(f_d) & np.isnan(f_o)
-    assert np.array_equal(np.isnan(f_d), np.isnan(f_o)), f"{label}: food None-pattern differs"
-    d = np.where(both_nan, 0.0, np.abs(f_d - f_o))
-    assert d.max() <= STATE_TOL, f"{label}: fp64 state diff {d.max()} in row {np.unravel_index(d.argmax(), d.shape)}"
-
-
-def start_pair(cfg, n, seed, **kw):
-    """Device and oracle in the shared injected start state (tests/parity_cases.py), set through set_state on both."""
-    orc, f64, i32 = pc.start_oracle(cfg, n, seed, **kw)
-    dev = SalpLib(cfg, n, device_id=0, seed=seed)
-    dev.set_state(f64, i32, 0)
-    return dev, orc
-
-
-def assert_final_obs(cfg, got_fin, ref, label=""):
-    """Terminal observations are delivered for finished envs, and only for them, with the oracle's values."""
-    done = (ref["terminated"] | ref["truncated"]).astype(bool)
-    assert done.any(), f"{label}: no episode ends: the terminal branch is not tested"
-    assert np.array_equal(np.isnan(got_fin[..., 0]), ~done), f"{label}: final_obs rows written do not match the finished envs"
-    d = obs_diff(cfg, got_fin[done], ref["final_obs"][done])
-    assert d.max() <= OBS_TOL, f"{label}: final_obs diff {d.max()}"
-    return float(d.max())
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -321,7 +250,7 @@ def test_set_state_injection_eval_style():
     n, seed = 256, 1
     dev = SalpLib(cfg, n, device_id=0, seed=seed)
     orc = ol.OracleVec(cfg, n, seed=seed)
-    f64, i32 = get_state(dev, cfg)
+    f64, i32 = device_state(dev, cfg)
     rng = np.random.default_rng(2)
     f64[_capi.F_X] = 150.0
     f64[_capi.F_Y] = 300.0
@@ -390,11 +319,11 @@ def compare_edge(cfg, dev, orc, act, label, kernel):
 
 def refused(dev, f64, i32, word):
     """set_state refuses the snapshot with SALP_ERR_INVALID and a message naming the quantity; nothing is written."""
-    before = get_state(dev, dev.cfg)
+    before = device_state(dev, dev.cfg)
     with pytest.raises(_capi.SalpError, match=word) as e:
         dev.set_state(f64, i32, 0)
     assert "(-1)" in str(e.value)
-    after = get_state(dev, dev.cfg)
+    after = device_state(dev, dev.cfg)
     assert np.array_equal(before[0], after[0], equal_nan=True) and np.array_equal(before[1], after[1])
 
 
@@ -449,13 +378,13 @@ def test_injected_water_level_out_of_range_is_refused(name, water):
     kernels take ellipse_a for the radius, so set_state refuses a level outside [0, 1] instead of diverging."""
     cfg = make_cfg(WATER_CONFIGS[name][0])
     dev = SalpLib(cfg, EDGE_N, device_id=0, seed=3)
-    f64, i32 = get_state(dev, cfg)
+    f64, i32 = device_state(dev, cfg)
     i32[_capi.I_PHASE, 70], i32[_capi.I_TIMER, 70], i32[_capi.I_SHAPE_HOLD, 70] = 1, 60, 0
     f64[_capi.F_WATER, 70] = water
     refused(dev, f64, i32, "water")
     f64[_capi.F_WATER, 70] = 1.0           # the same snapshot with the level in range is taken
     dev.set_state(f64, i32, 0)
-    assert get_state(dev, cfg)[0][_capi.F_WATER, 70] == 1.0
+    assert device_state(dev, cfg)[0][_capi.F_WATER, 70] == 1.0
     dev.close()
 
 
@@ -464,7 +393,7 @@ def test_breathing_integers_out_of_range_are_refused():
     cfg = pkg.load_env_config("single_food")
     dev = SalpLib(cfg, EDGE_N, device_id=0, seed=3)
     for row, bad in ((_capi.I_EXHALE_DUR, 375), (_capi.I_TIMER, 256), (_capi.I_PHASE, 3), (_capi.I_SHAPE_HOLD, 8), (_capi.I_TIMER, -1)):
-        f64, i32 = get_state(dev, cfg)
+        f64, i32 = device_state(dev, cfg)
         i32[row, 129] = bad
         refused(dev, f64, i32, "exhale duration")
     dev.close()
@@ -510,7 +439,7 @@ def test_injected_heading_beyond_the_documented_range_is_refused(row, value):
     (|theta|, |omega| <= SALP_SET_STATE_MAX_ANGLE = 100)."""
     cfg = pkg.load_env_config("single_food")
     dev = SalpLib(cfg, EDGE_N, device_id=0, seed=5)
-    f64, i32 = get_state(dev, cfg)
+    f64, i32 = device_state(dev, cfg)
     f64[row, 200] = value
     refused(dev, f64, i32, "theta")
     dev.close()
@@ -695,7 +624,7 @@ def test_food_next_to_the_swimmer_keeps_the_reward_exact():
     n, H = 128, 3
     dev = SalpLib(cfg, n, device_id=0, seed=21)
     orc = ol.OracleVec(cfg, n, seed=21)
-    f64, i32 = get_state(dev, cfg)
+    f64, i32 = device_state(dev, cfg)
     rng = np.random.default_rng(4)
     ang = rng.uniform(-np.pi, np.pi, size=(2, n))
     F = cfg.num_food_items
@@ -823,7 +752,7 @@ def test_near_tie_food_order_matches_oracle_across_scales(foods):
     n, H, seed = 4096, 20, 77
     dev = SalpLib(cfg, n, device_id=0, seed=seed)
     orc = ol.OracleVec(cfg, n, seed=seed, threads=8)
-    f64, i32 = get_state(dev, cfg)
+    f64, i32 = device_state(dev, cfg)
     rng = np.random.default_rng(5)
     x = rng.uniform(380, 420, n); y = rng.uniform(280, 320, n)
     f64[_capi.F_X], f64[_capi.F_Y] = x, y

@@ -15,6 +15,8 @@ import pytest
 import evaluate_cases as ec
 import parity_cases as pc
 import policy_cases as cases
+from gpu_support import device_state, run_policy, started
+from support import fields_diff, same_state
 from underwater_swimmer_rl_amd import _capi
 from underwater_swimmer_rl_amd._capi import SalpError, SalpLib
 from underwater_swimmer_rl_amd.policy import MLPPolicy, evaluation_views, summarize_rollout
@@ -27,55 +29,12 @@ W = _capi.EVAL_WORDS
 H, CUT = cases.H, ec.CUT
 
 
-def device_state(dev, cfg):
-    f64 = np.empty((_capi.F_FOOD0 + 2 * cfg.num_food_items, dev.n_envs), np.float64)
-    i32 = np.empty((_capi.I_COUNT, dev.n_envs), np.int32)
-    dev.get_state(f64, i32, 0)
-    return f64, i32
-
-
-def same_state(a, b):
-    return np.array_equal(a[0], b[0], equal_nan=True) and np.array_equal(a[1], b[1])
-
-
-def started(cfg, n, f64, i32):
-    dev = SalpLib(cfg, n, device_id=0, seed=pc.ENV_SEED)
-    dev.set_state(f64, i32, 0)
-    return dev
-
-
-def rollout_outputs(dev, ph, cfg, horizon):
-    n = dev.n_envs
-    o = dict(obs=np.full((horizon, n, cfg.obs_dim), np.nan, np.float32), reward=np.full((horizon, n), np.nan, np.float32),
-             terminated=np.full((horizon, n), 7, np.uint8), truncated=np.full((horizon, n), 7, np.uint8),
-             actions=np.full((horizon, n, cfg.act_dim), np.nan, np.float32))
-    dev.rollout_policy(ph, horizon, o["obs"], o["reward"], o["terminated"], o["truncated"], o["actions"], 0)
-    return o
-
-
 def fresh_record(n, fill=0x5A):
     return np.full((n, W), np.int32(fill * 0x01010101), np.int32)        # junk: a call without ACCUMULATE overwrites it
 
 
-def start_snapshot(name):
-    c, cfg = cases.CASES[name], cases.case_cfg(name)
-    orc, f64, i32 = pc.start_oracle(cfg, c["n"], pc.ENV_SEED)
-    orc.close()
-    return c, cfg, cases.case_policy(name), f64, i32
-
-
 def record_diff(got, want):
-    """'' when the two record blocks are identical bit for bit, else which fields differ and where first."""
-    if np.array_equal(got, want):
-        return ""
-    g, w = evaluation_views(np.ascontiguousarray(got)), evaluation_views(np.ascontiguousarray(want))
-    bad = []
-    for k in ("return_sum", "first_return", "first_length", "first_end", "episodes", "food"):
-        same = g[k].view(np.int64 if g[k].dtype == np.float64 else np.int32) == w[k].view(np.int64 if w[k].dtype == np.float64 else np.int32)
-        if not same.all():
-            i = int(np.argmin(same))
-            bad.append(f"{k}: {int((~same).sum())} envs, first env {i}: {g[k][i]!r} != {w[k][i]!r}")
-    return "; ".join(bad)
+    return fields_diff(got, want, evaluation_views, ("return_sum", "first_return", "first_length", "first_end", "episodes", "food"))
 
 
 @functools.lru_cache(maxsize=None)
@@ -83,11 +42,11 @@ def device_run(name):
     """A case on the GPU, computed once, shared, read-only: salp_vec_rollout_policy on one handle, salp_vec_evaluate_policy on
     a twin handle put into the same injected start state with set_state (a fresh handle, not the first one set back: the
     running episode return behind `episode_return_sum` is not part of a snapshot)."""
-    c, cfg, policy, f64, i32 = start_snapshot(name)
+    c, cfg, policy, f64, i32 = cases.start_snapshot(name)
     n = c["n"]
     roll = started(cfg, n, f64, i32)
     ph_r = roll.policy_create(policy)
-    out = rollout_outputs(roll, ph_r, cfg, H)
+    out = run_policy(roll, ph_r, cfg, H)
     roll_end = dict(state=device_state(roll, cfg), stats=roll.stats(), step=roll.global_step, launch=roll.last_launch(),
                     res=roll.last_kernel_resources())
     ph_r.close()
@@ -267,7 +226,7 @@ def test_other_constant_sets_and_launch_forms(case, n):
     policy = cases.random_policy(cfg.obs_dim, cfg.act_dim, (16,), "tanh", 102, 1.5, 4.0, free_breathing=not cfg.forced_breathing)
     roll = started(cfg, n, f64, i32)
     ph = roll.policy_create(policy)
-    out = rollout_outputs(roll, ph, cfg, HP)
+    out = run_policy(roll, ph, cfg, HP)
     state, stats, twin = device_state(roll, cfg), roll.stats(), roll.last_launch()
     ph.close()
     roll.close()
@@ -295,28 +254,16 @@ def test_other_constant_sets_and_launch_forms(case, n):
     dev.close()
 
 
-def _separated_population(P):
-    """The population of tests/test_gpu_policy_rollout.py: P policies 24 -> 16 -> 1 whose outputs are far apart on every
-    observation (output biases spread over [-0.9, 0.9], small weights)."""
-    ps = []
-    for k in range(P):
-        p = cases.random_policy(24, 1, (16,), "tanh", 200 + k, 0.5, 0.1)
-        (W0, b0), (W1, b1) = p.layers
-        b1 = np.full_like(b1, -0.9 + 1.8 * k / max(P - 1, 1))
-        ps.append(MLPPolicy([(W0, b0), (W1, b1)], p.scale, p.shift, "tanh"))
-    return ps
-
-
 @pytest.mark.parametrize("P,group", [(4, 64), (2, 128)])
 def test_population_records_are_those_of_the_rollout(P, group):
     cfg = pc.case_cfg("single_food")
     n, HP = P * group, 96
     orc, f64, i32 = pc.start_oracle(cfg, n, pc.ENV_SEED)
     orc.close()
-    pop = MLPPolicy.stack(_separated_population(P))
+    pop = MLPPolicy.stack(cases.separated_population(P))
     roll = started(cfg, n, f64, i32)
     ph = roll.policy_create(pop)
-    out = rollout_outputs(roll, ph, cfg, HP)
+    out = run_policy(roll, ph, cfg, HP)
     state = device_state(roll, cfg)
     # the groups do take different actions: the records below are not those of one policy for all
     first = out["actions"][0, :, 0].reshape(P, group)
@@ -348,7 +295,7 @@ def test_no_autoreset_counts_every_flagged_step(case):
     policy = cases.case_policy(name)
     roll = started(cfg, n, f64, i32)
     ph = roll.policy_create(policy)
-    out = rollout_outputs(roll, ph, cfg, HP)
+    out = run_policy(roll, ph, cfg, HP)
     state = device_state(roll, cfg)
     ph.close()
     roll.close()

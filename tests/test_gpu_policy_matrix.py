@@ -15,10 +15,10 @@ import functools
 import numpy as np
 import pytest
 
-import parity_cases as pc
 import policy_matrix as pm
+from gpu_support import device_state, host_outputs, run_policy, started
+from support import bits, same_state
 from underwater_swimmer_rl_amd import _capi
-from underwater_swimmer_rl_amd._capi import SalpLib
 from underwater_swimmer_rl_amd.policy import evaluation_views, summarize_rollout
 
 pytestmark = pytest.mark.gpu
@@ -26,39 +26,6 @@ pytestmark = pytest.mark.gpu
 DEV = _capi.SALP_DEVICE_PTRS
 H, HU = pm.H, pm.UPDATE_STEPS
 NAMES = list(pm.ENTRIES)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def device_state(dev, cfg):
-    f64 = np.empty((_capi.F_FOOD0 + 2 * cfg.num_food_items, dev.n_envs), np.float64)
-    i32 = np.empty((_capi.I_COUNT, dev.n_envs), np.int32)
-    dev.get_state(f64, i32, 0)
-    return f64, i32
-
-
-def same_state(a, b):
-    return np.array_equal(a[0], b[0], equal_nan=True) and np.array_equal(a[1], b[1])
-
-
-def started(cfg, n, f64, i32):
-    dev = SalpLib(cfg, n, device_id=0, seed=pc.ENV_SEED)
-    dev.set_state(f64, i32, 0)
-    return dev
-
-
-def host_outputs(cfg, horizon, n):
-    return dict(obs=np.full((horizon, n, cfg.obs_dim), np.nan, np.float32), reward=np.full((horizon, n), np.nan, np.float32),
-                terminated=np.full((horizon, n), 7, np.uint8), truncated=np.full((horizon, n), 7, np.uint8),
-                actions=np.full((horizon, n, cfg.act_dim), np.nan, np.float32))
-
-
-def run_policy(dev, ph, cfg, horizon):
-    o = host_outputs(cfg, horizon, dev.n_envs)
-    dev.rollout_policy(ph, horizon, o["obs"], o["reward"], o["terminated"], o["truncated"], o["actions"], 0)
-    return o
 
 
 def first_step_then_run(dev, ph, cfg):

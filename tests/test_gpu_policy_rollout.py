@@ -13,73 +13,23 @@ import pytest
 
 import parity_cases as pc
 import policy_cases as cases
+from gpu_support import OBS_TOL, REW_TOL, STATE_TOL, device_state, host_outputs, run_policy, started
+from support import bits, obs_diff, same_state
 from underwater_swimmer_rl_amd import _capi
 from underwater_swimmer_rl_amd._capi import SalpError, SalpLib
 from underwater_swimmer_rl_amd.policy import MLPPolicy
 
 pytestmark = pytest.mark.gpu
 
-OBS_TOL = 1e-5
-REW_TOL = 1e-5
-STATE_TOL = 1e-9
 SENTINEL = 0xA5C3F00D
 DEV = _capi.SALP_DEVICE_PTRS
 H = cases.H
 
 
-def obs_diff(cfg, a, b):
-    """|a - b| with the columns that hold an angle / pi compared on the circle (tests/test_gpu_parity.py)."""
-    d = np.abs(a.astype(np.float64) - b.astype(np.float64))
-    for c in [4] + [10 + 4 * s + 3 for s in range(cfg.max_observed_food)]:
-        d[..., c] = np.minimum(d[..., c], 2.0 - d[..., c])
-    return d
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def device_state(dev, cfg):
-    f64 = np.empty((_capi.F_FOOD0 + 2 * cfg.num_food_items, dev.n_envs), np.float64)
-    i32 = np.empty((_capi.I_COUNT, dev.n_envs), np.int32)
-    dev.get_state(f64, i32, 0)
-    return f64, i32
-
-
-def same_state(a, b):
-    return np.array_equal(a[0], b[0], equal_nan=True) and np.array_equal(a[1], b[1])
-
-
-def started(cfg, n, f64, i32):
-    dev = SalpLib(cfg, n, device_id=0, seed=pc.ENV_SEED)
-    dev.set_state(f64, i32, 0)
-    return dev
-
-
-def host_outputs(cfg, horizon, n):
-    return dict(obs=np.full((horizon, n, cfg.obs_dim), np.nan, np.float32), reward=np.full((horizon, n), np.nan, np.float32),
-                terminated=np.full((horizon, n), 7, np.uint8), truncated=np.full((horizon, n), 7, np.uint8),
-                actions=np.full((horizon, n, cfg.act_dim), np.nan, np.float32))
-
-
-def run_policy(dev, ph, cfg, horizon, want_actions=True):
-    o = host_outputs(cfg, horizon, dev.n_envs)
-    dev.rollout_policy(ph, horizon, o["obs"], o["reward"], o["terminated"], o["truncated"], o["actions"] if want_actions else None, 0)
-    return o
-
-
-def start_snapshot(name):
-    """cfg, policy and the injected start state of a case (the oracle's own closed-loop run is the CPU guard's business)."""
-    c, cfg = cases.CASES[name], cases.case_cfg(name)
-    orc, f64, i32 = pc.start_oracle(cfg, c["n"], pc.ENV_SEED)
-    orc.close()
-    return c, cfg, cases.case_policy(name), f64, i32
-
-
 @functools.lru_cache(maxsize=None)
 def device_run(name):
     """One closed-loop rollout of a case on the GPU: computed once, shared by the tests below, read-only."""
-    c, cfg, policy, f64, i32 = start_snapshot(name)
+    c, cfg, policy, f64, i32 = cases.start_snapshot(name)
     dev = started(cfg, c["n"], f64, i32)
     obs0 = np.empty((c["n"], cfg.obs_dim), np.float32)
     dev.observe(obs0, 0)
@@ -225,25 +175,13 @@ def test_prologue_observation_is_the_row_before_it(case, no_autoreset):
         assert per_wave.any() and not per_wave.all(), f"column {c}: {int(per_wave.sum())} of {per_wave.size} wavefront-steps with an episode end"
 
 
-def _separated_population(P):
-    """P policies 24 -> 16 -> 1 whose outputs are far apart on every observation: small weights, output biases spread over
-    [-0.9, 0.9] (|W h| stays below 0.15, so two policies' pre-activations differ by at least 0.3)."""
-    ps = []
-    for k in range(P):
-        p = cases.random_policy(24, 1, (16,), "tanh", 200 + k, 0.5, 0.1)
-        (W0, b0), (W1, b1) = p.layers
-        b1 = np.full_like(b1, -0.9 + 1.8 * k / max(P - 1, 1))
-        ps.append(MLPPolicy([(W0, b0), (W1, b1)], p.scale, p.shift, "tanh"))
-    return ps
-
-
 @pytest.mark.parametrize("P,group", [(4, 64), (2, 128)])
 def test_population_each_group_runs_its_own_policy(P, group):
     cfg = pc.case_cfg("single_food")
     n, HP = P * group, 96
     orc, f64, i32 = pc.start_oracle(cfg, n, pc.ENV_SEED)
     orc.close()
-    ps = _separated_population(P)
+    ps = cases.separated_population(P)
     pop = MLPPolicy.stack(ps)
     dev = started(cfg, n, f64, i32)
     obs0 = np.empty((n, cfg.obs_dim), np.float32)
@@ -378,7 +316,7 @@ def test_device_pointers_guard_words_and_null_act_out(name):
 def test_graph_capture_replays_and_takes_new_weights_without_recapture():
     import torch
     name = "one_food_mlp32"
-    c, cfg, policy, f64, i32 = start_snapshot(name)
+    c, cfg, policy, f64, i32 = cases.start_snapshot(name)
     n, K = c["n"], 16
     policy_b = cases.random_policy(cfg.obs_dim, cfg.act_dim, c["hidden"], c["out"], 999, c["gain"], c["out_gain"])
     assert policy_b.words == policy.words

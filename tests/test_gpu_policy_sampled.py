@@ -14,7 +14,10 @@ import pytest
 
 import evaluate_cases as ec
 import parity_cases as pc
+import policy_cases as dc
 import sampled_cases as cases
+from gpu_support import device_state, host_outputs, run_policy, run_sampled, started
+from support import bits, same_state
 from underwater_swimmer_rl_amd import _capi
 from underwater_swimmer_rl_amd._capi import SalpError, SalpLib
 from underwater_swimmer_rl_amd.policy import EVAL_WORDS, GaussianPolicy, evaluation_views, summarize_rollout
@@ -26,57 +29,10 @@ DEV, ACC = _capi.SALP_DEVICE_PTRS, _capi.EVAL_ACCUMULATE
 H = cases.H
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def device_state(dev, cfg):
-    f64 = np.empty((_capi.F_FOOD0 + 2 * cfg.num_food_items, dev.n_envs), np.float64)
-    i32 = np.empty((_capi.I_COUNT, dev.n_envs), np.int32)
-    dev.get_state(f64, i32, 0)
-    return f64, i32
-
-
-def same_state(a, b):
-    return np.array_equal(a[0], b[0], equal_nan=True) and np.array_equal(a[1], b[1])
-
-
-def started(cfg, n, f64, i32, seed=pc.ENV_SEED):
-    dev = SalpLib(cfg, n, device_id=0, seed=seed)
-    dev.set_state(f64, i32, 0)
-    return dev
-
-
-def host_outputs(cfg, horizon, n):
-    return dict(obs=np.full((horizon, n, cfg.obs_dim), np.nan, np.float32), reward=np.full((horizon, n), np.nan, np.float32),
-                terminated=np.full((horizon, n), 7, np.uint8), truncated=np.full((horizon, n), 7, np.uint8),
-                actions=np.full((horizon, n, cfg.act_dim), np.nan, np.float32), logp=np.full((horizon, n), np.nan, np.float32))
-
-
-def run_sampled(dev, ph, cfg, horizon, want_actions=True, want_logp=True):
-    o = host_outputs(cfg, horizon, dev.n_envs)
-    dev.rollout_policy_sampled(ph, horizon, o["obs"], o["reward"], o["terminated"], o["truncated"],
-                               o["actions"] if want_actions else None, o["logp"] if want_logp else None, 0)
-    return o
-
-
-def run_mean(dev, ph, cfg, horizon):
-    o = host_outputs(cfg, horizon, dev.n_envs)
-    dev.rollout_policy(ph, horizon, o["obs"], o["reward"], o["terminated"], o["truncated"], o["actions"], 0)
-    return o
-
-
-def start_snapshot(name):
-    c, cfg = cases.CASES[name], cases.case_cfg(name)
-    orc, f64, i32 = pc.start_oracle(cfg, c["n"], pc.ENV_SEED)
-    orc.close()
-    return c, cfg, cases.case_policy(name), f64, i32
-
-
 @functools.lru_cache(maxsize=None)
 def device_run(name):
     """One sampled closed-loop rollout of a case on the GPU from noise step 0: computed once, shared, read-only."""
-    c, cfg, policy, f64, i32 = start_snapshot(name)
+    c, cfg, policy, f64, i32 = dc.start_snapshot(name, cases)
     dev = started(cfg, c["n"], f64, i32)
     obs0 = np.empty((c["n"], cfg.obs_dim), np.float32)
     dev.observe(obs0, 0)
@@ -124,7 +80,7 @@ def test_the_intended_kernel_ran(name):
     # the deterministic twin: the same case through salp_vec_rollout_policy differs in [5] alone
     dev = started(r["cfg"], c["n"], r["f64"], r["i32"])
     ph = dev.policy_create(r["policy"])
-    run_mean(dev, ph, r["cfg"], 2)
+    run_policy(dev, ph, r["cfg"], 2)
     twin = dev.last_launch()
     assert twin["actions_in_kernel"] == 2 and {k: v for k, v in twin.items() if k != "actions_in_kernel"} == \
         {k: v for k, v in ll.items() if k != "actions_in_kernel"}
@@ -189,7 +145,7 @@ def test_split_equals_whole(name):
     c, cfg, out = r["c"], r["cfg"], r["out"]
     dev = started(cfg, c["n"], r["f64"], r["i32"])
     ph = dev.policy_create(r["policy"])
-    got = host_outputs(cfg, H, c["n"])
+    got = host_outputs(cfg, H, c["n"], logp=True)
     for t in range(H):
         dev.rollout_policy_sampled(ph, 1, got["obs"][t:t + 1], got["reward"][t:t + 1], got["terminated"][t:t + 1],
                                    got["truncated"][t:t + 1], got["actions"][t:t + 1], got["logp"][t:t + 1], 0)
@@ -243,14 +199,14 @@ def test_set_noise_step_continues_a_run_and_reseed_rekeys_the_stream():
 @pytest.mark.parametrize("name", ["one_food_mlp32", "sac_gail_mlp64"])
 def test_the_deterministic_entry_points_run_the_mean(name):
     """A Gaussian policy through salp_vec_rollout_policy / salp_vec_evaluate_policy == its mean_policy(), bit for bit."""
-    c, cfg, policy, f64, i32 = start_snapshot(name)
+    c, cfg, policy, f64, i32 = dc.start_snapshot(name, cases)
     n, HM = c["n"], 128
     runs = []
     for p in (policy, policy.mean_policy()):
         dev = started(cfg, n, f64, i32)
         ph = dev.policy_create(p)
         assert ph.gaussian == isinstance(p, GaussianPolicy)
-        o = run_mean(dev, ph, cfg, HM)
+        o = run_policy(dev, ph, cfg, HM)
         ll = dev.last_launch()
         rec = np.zeros((n, EVAL_WORDS), np.int32)
         dev.evaluate_policy(ph, HM, rec, 0)
@@ -271,7 +227,7 @@ def test_the_deterministic_entry_points_run_the_mean(name):
 def test_log_std_clamps():
     """W_ls = 0: b_ls = -50 gives the bits of b_ls = -20, b_ls = +7 those of b_ls = +2."""
     name, HC = "one_food_mlp32", 48
-    c, cfg, policy, f64, i32 = start_snapshot(name)
+    c, cfg, policy, f64, i32 = dc.start_snapshot(name, cases)
     n = c["n"]
 
     def run(b):
@@ -333,7 +289,7 @@ def test_evaluate_policy_sampled_is_the_summary_of_the_sampled_rollout(name):
 def test_graph_capture_draws_fresh_noise_and_takes_new_weights():
     import torch
     name = "one_food_mlp32"
-    c, cfg, policy, f64, i32 = start_snapshot(name)
+    c, cfg, policy, f64, i32 = dc.start_snapshot(name, cases)
     n, K = c["n"], 16
     policy_b = cases.gaussian_policy(cfg.obs_dim, cfg.act_dim, c["hidden"], 999, c["gain"], c["out_gain"], c["b_ls"])
     assert policy_b.words == policy.words
@@ -468,7 +424,7 @@ def test_refusals_leave_the_handle_and_the_noise_step_unchanged():
     ph_dims = other_dims.policy_create(cases.case_policy("free_breathing_mlp32_clamped"))
     ph.set_noise_step(41)
     before, step0, stats0 = device_state(dev, cfg), dev.global_step, dev.stats()
-    o = host_outputs(cfg, 2, n)
+    o = host_outputs(cfg, 2, n, logp=True)
     base = dict(handle=ph, horizon=2, obs=o["obs"], reward=o["reward"], term=o["terminated"], trunc=o["truncated"],
                 act_out=o["actions"], logp_out=o["logp"], flags=0)
     refused = [("a plain policy", dict(handle=ph_plain)), ("policy of another handle", dict(handle=ph_other)),

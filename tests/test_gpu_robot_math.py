@@ -124,10 +124,9 @@ def _mp_ulps(got, exact_of, x):
 def _kernel_rcp_arguments(count):
     """What the cycle body feeds rcp_nr: dt, mass, width, the inertia diagonal, the aspect span and cos(pitch) down to 1e-6,
     for the default config (column 0) and the random parameter box of the trajectory tests."""
-    from test_gpu_robot_trajectory import _random_params
     from underwater_swimmer_rl_amd.robot_compare import ROBOT_PARAM_NAMES, robot_params
     rng = np.random.default_rng(24)
-    P = _random_params(rng, count)
+    P = cases.random_robot_params(rng, count)
     P[:, 0] = robot_params(1, "cpu").numpy()[:, 0]
     p = {name: P[j] for j, name in enumerate(ROBOT_PARAM_NAMES)}
     u = rng.uniform(0, 1, count)

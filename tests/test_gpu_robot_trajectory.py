@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import robot_oracle_lib as rol
+from robot_math_cases import random_robot_params
 from underwater_swimmer_rl_amd.robot_compare import ROBOT_PARAM_NAMES, compare_actions_with_states, robot_params
 from underwater_swimmer_rl_amd.robot_env import R_EULER, R_OMEGA, R_POS, R_VEL, SalpRobotVectorEnv
 
@@ -26,15 +27,15 @@ def _rel(a, b):
     return float(np.max(np.abs(a - b) / np.maximum(1.0, np.abs(b))))
 
 
-def _p(x):
+def _ptr(x):
     if x is None:
         return None
     return ctypes.c_void_p(x.data_ptr()) if hasattr(x, "data_ptr") else ctypes.c_void_p(x.ctypes.data)
 
 
 def _raw(env, params, actions, cycles, expected, states, metrics, inner, flags, stream=None):
-    return env.L.salp_robot_vec_trajectory(env._h, _p(params), _p(actions), int(cycles), _p(expected), _p(states),
-                                           _p(metrics), _p(inner), flags, stream)
+    return env.L.salp_robot_vec_trajectory(env._h, _ptr(params), _ptr(actions), int(cycles), _ptr(expected), _ptr(states),
+                                           _ptr(metrics), _ptr(inner), flags, stream)
 
 
 def _run_host(n, params, actions, T, expected, per_robot=False):
@@ -91,16 +92,6 @@ def test_mixed_wavefronts_match_their_candidate():
         assert _rel(met[k], np.array([z[f"shared_{m}"][k] for m in KEYS])) <= 1e-6, k
 
 
-def _random_params(rng, n):
-    d = robot_params(1, "cpu").numpy()[:, 0]
-    P = d[:, None] * rng.uniform(0.5, 1.5, (12, n))
-    j = {name: i for i, name in enumerate(ROBOT_PARAM_NAMES)}
-    lo, hi = np.minimum(P[j["drag_coefficient_min"]], P[j["drag_coefficient_max"]]), np.maximum(P[j["drag_coefficient_min"]], P[j["drag_coefficient_max"]])
-    P[j["drag_coefficient_min"]], P[j["drag_coefficient_max"]] = lo, hi + 1e-3
-    P[j["max_contraction"]] = np.minimum(P[j["max_contraction"]], 0.5 * P[j["init_length"]])
-    return P
-
-
 def _oracle_states(col, a):
     c = rol.default_robot_config()
     for j, name in enumerate(ROBOT_PARAM_NAMES):
@@ -129,7 +120,7 @@ def test_random_parameters_at_scale_against_the_oracle():
     spinning robot takes it for its whole wavefront).  The worst differences are printed."""
     rng = np.random.default_rng(11)
     n, T = 65536, 6
-    P = _random_params(rng, n)
+    P = random_robot_params(rng, n)
     a = np.stack([rng.uniform(0, 1, T), rng.uniform(0, 0.2, T), rng.uniform(-1, 1, T)], 1).astype(np.float32)
     out = compare_actions_with_states(_scaled(a), None, P)
     st, inner = out["actual_states"].cpu().numpy(), out["inner_steps"].cpu().numpy()
@@ -197,7 +188,7 @@ def test_the_call_leaves_the_env_alone():
         e.step(a0)
     s0 = envs[0].get_state()
     acts = torch.as_tensor(_scaled(rng.uniform(0, 1, (6, 3)).astype(np.float32)), device="cuda:0")
-    P = torch.as_tensor(_random_params(rng, n), device="cuda:0")
+    P = torch.as_tensor(random_robot_params(rng, n), device="cuda:0")
     st = torch.empty((6, n, 6), dtype=torch.float64, device="cuda:0")
     e0 = envs[0]
     assert _raw(e0, P, acts, 6, None, st, None, None, 1, e0._stream) == 0
@@ -216,7 +207,7 @@ def test_metrics():
     rng = np.random.default_rng(9)
     n, T = 2000, 7
     acts = _scaled(np.stack([rng.uniform(0, 1, T), rng.uniform(0, 0.3, T), rng.uniform(-1, 1, T)], 1).astype(np.float32))
-    P = _random_params(rng, n)
+    P = random_robot_params(rng, n)
     x = rng.normal(0, 0.2, (T, 6))
     full = compare_actions_with_states(acts, x, P)
     only = compare_actions_with_states(acts, x, P, metrics_only=True)
@@ -249,7 +240,7 @@ def test_system_identification_sanity():
 def test_bad_parameters_stay_in_their_lane():
     rng = np.random.default_rng(12)
     n, T = 256, 4
-    P = _random_params(rng, n)
+    P = random_robot_params(rng, n)
     acts = _scaled(np.array([[1.0, 0.1, 0.3], [0.5, 0.0, -1.0], [0.2, 0.2, 1.0], [1.0, 1.0, 0.0]], np.float32))
     clean = compare_actions_with_states(acts, None, P)["actual_states"].cpu().numpy()
     bad = P.copy()
@@ -278,7 +269,7 @@ def test_rejected_arguments_launch_nothing():
     cases = [(None, acts, T, x, 1), (h, None, T, x, 1), (h, acts, 0, x, 1), (h, acts, -2, x, 1), (h, acts, 1025, x, 1),
              (h, acts, T, x, 1 | 4), (h, acts, T, x, 1 << 31), (h, acts, T, None, 1)]
     for hh, a, c, xx, f in cases:
-        rc = L.salp_robot_vec_trajectory(hh, None, _p(a), c, _p(xx), _p(st), _p(met), _p(inner), f, s)
+        rc = L.salp_robot_vec_trajectory(hh, None, _ptr(a), c, _ptr(xx), _ptr(st), _ptr(met), _ptr(inner), f, s)
         assert rc == -1, (c, f)
         assert L.salp_robot_last_error().decode()
     tiny = SalpRobotVectorEnv(64, device="cuda:0", seed=1, dt=1e-9)
@@ -301,7 +292,7 @@ def test_graph_replay_matches_eager():
     env = SalpRobotVectorEnv(n, device="cuda:0", seed=2)
     acts = torch.as_tensor(_scaled(rng.uniform(0, 1, (T, 3)).astype(np.float32)), device="cuda:0")
     x = torch.as_tensor(rng.normal(0, 0.1, (T, 6)), device="cuda:0")
-    P = torch.as_tensor(_random_params(rng, n), device="cuda:0")
+    P = torch.as_tensor(random_robot_params(rng, n), device="cuda:0")
     st = torch.empty((T, n, 6), dtype=torch.float64, device="cuda:0")
     met = torch.empty((n, 5), dtype=torch.float64, device="cuda:0")
     inner = torch.empty((T, n), dtype=torch.int32, device="cuda:0")
@@ -310,10 +301,10 @@ def test_graph_replay_matches_eager():
     g = torch.cuda.CUDAGraph()
     with torch.cuda.stream(s):
         with torch.cuda.graph(g, stream=s):
-            rc = env.L.salp_robot_vec_trajectory(env._h, _p(P), _p(acts), T, _p(x), _p(st), _p(met), _p(inner), 1,
+            rc = env.L.salp_robot_vec_trajectory(env._h, _ptr(P), _ptr(acts), T, _ptr(x), _ptr(st), _ptr(met), _ptr(inner), 1,
                                                  ctypes.c_void_p(s.cuda_stream))
     assert rc == 0
-    P.copy_(torch.as_tensor(_random_params(rng, n), device="cuda:0"))
+    P.copy_(torch.as_tensor(random_robot_params(rng, n), device="cuda:0"))
     g.replay()
     torch.cuda.synchronize()
     eager = compare_actions_with_states(acts, x, P.clone())

@@ -3,7 +3,6 @@ against the header, the sharded step's packed fast path under gloo, and the pack
 import importlib.util
 import os
 import re
-import socket
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import torch.multiprocessing as mp
 
 import oracle_lib as ol
 import parity_cases as pc
+from support import free_port
 import underwater_swimmer_rl_amd as pkg
 from underwater_swimmer_rl_amd import _capi, records
 from underwater_swimmer_rl_amd.records import pack_record, record_width, unpack_record
@@ -126,14 +126,6 @@ class PackedEngine(PlainEngine):
                            out["final_obs"] if want_final_observation else None)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _worker(rank, world, port, tmp):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -176,7 +168,7 @@ def _worker(rank, world, port, tmp):
 @pytest.mark.timeout(300)
 def test_sharded_step_packed_path_equals_the_packing_path(tmp_path):
     world = 2
-    mp.spawn(_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, free_port(), str(tmp_path)), nprocs=world, join=True)
     counts = [int(open(tmp_path / f"ok{r}").read()) for r in range(world)]
     assert counts[0] == counts[1] > 0          # every rank saw the same gathered batch finish episodes
 

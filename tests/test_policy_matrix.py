@@ -10,13 +10,10 @@ import pytest
 import oracle_lib as ol
 import parity_cases as pc
 import policy_matrix as pm
+from support import bits
 
 NOT_BLIND = 0.25            # of the visited rows, per action component, must be out of saturation
 NAMES = list(pm.ENTRIES)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def test_the_table_covers_what_it_must():

@@ -11,14 +11,10 @@ import numpy as np
 import pytest
 
 import robot_oracle_lib as rol
+from support import rel
 
 GOLD = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "robot_*.npz")))
 TOL = 1e-6
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.nanmax(np.abs(a - b) / np.maximum(1.0, np.abs(b)))) if a.size else 0.0
 
 
 def test_fixtures_present():

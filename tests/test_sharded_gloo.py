@@ -4,7 +4,6 @@ The per-rank simulator is injected: here it is the CPU oracle (test infrastructu
 for the HIP engine so that the sharding / global-index keying / gather logic of
 `ShardedSalpVectorEnv` runs without a GPU.  The product default engine is the HIP library."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 import oracle_lib as ol
+from support import free_port
 import underwater_swimmer_rl_amd as pkg
 from underwater_swimmer_rl_amd.sharded import ShardedSalpVectorEnv
 
@@ -41,14 +41,6 @@ class OracleEngine:
 
     def close(self):
         self.o.close()
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, tmp):
@@ -100,7 +92,7 @@ def _worker(rank, world, port, tmp):
 @pytest.mark.timeout(300)
 def test_two_rank_sharding_equals_single_process(tmp_path):
     world = 2
-    mp.spawn(_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, free_port(), str(tmp_path)), nprocs=world, join=True)
     r0 = np.load(tmp_path / "rank0.npz")
     r1 = np.load(tmp_path / "rank1.npz")
     for k in r0.files:   # every rank holds the same gathered batch
@@ -162,7 +154,7 @@ def _sac_worker(rank, world, port, tmp):
 @pytest.mark.timeout(300)
 def test_data_parallel_sac_replicas_stay_identical(tmp_path):
     """SAC(data_parallel=True): broadcast at construction, one gradient all-reduce (mean) per backward."""
-    port = _free_port()
+    port = free_port()
     mp.spawn(_sac_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
     a = torch.load(os.path.join(tmp_path, "sac0.pt"), weights_only=True)
     b = torch.load(os.path.join(tmp_path, "sac1.pt"), weights_only=True)
