@@ -79,7 +79,8 @@ def test_fp32_food_key_error_stays_inside_the_tie_tolerance():
     apart than `tie_tolerance(d2) = 1.4e-7 L^2 + 8e-6 d2`; the claim behind it is that a key (fp32 squared distance from
     fp32-rounded positions, low 4 bits replaced by the slot) is within HALF of that of the exact squared distance.
     Emulated here with numpy float32 arithmetic for random geometry in tanks of several sizes; the GPU-side check of the
-    same property is tests/test_gpu_parity.py::test_near_tie_food_order_matches_oracle_across_scales."""
+    same property is tests/test_gpu_parity.py::test_near_tie_food_order_matches_oracle_across_scales and, per selection
+    network, tie rank and slot pair, tests/test_gpu_food_order.py."""
     import numpy as np
     rng = np.random.default_rng(0)
     for L, H in ((800, 600), (1200, 900), (500, 450), (4000, 3000)):
