@@ -1,6 +1,6 @@
 """Checks behind two claims the kernel source makes without the compiler being able to prove them.
 
-(a) csrc/salp_device.h step_head(): `p = timer / duration` of the breathing cycle (legacy:212-213, :240-246) is computed as
+(a) csrc/salp_step.h step_head(): `p = timer / duration` of the breathing cycle (legacy:212-213, :240-246) is computed as
     y = RN(1/den), q0 = RN(t y), p = RN(q0 + RN_fma(t - den q0) y) instead of the IEEE division sequence, and is claimed
     to equal the correctly rounded quotient for every duration 1..255 and timer 1..257.  Checked here in exact rationals.
 (b) csrc/salp_rollout_traits.h (SWZ, PITCH) and csrc/salp_rollout_kernel.h (the tile writes and the flush plan): the
@@ -59,7 +59,7 @@ def test_swizzled_observation_tile_is_conflict_free():
 
 
 def test_ellipse_a_is_the_larger_axis_for_the_reference_radii():
-    """csrc/salp_device.h step_head(): the literal-constant kernels take r = max(ellipse_a, ellipse_b) = ellipse_a
+    """csrc/salp_step.h step_head(): the literal-constant kernels take r = max(ellipse_a, ellipse_b) = ellipse_a
     (legacy:190-246: a = 1.3R .. 1.1R .. 1.3R, b = 0.8R .. 1.1R .. 0.8R).  Every (phase, timer, duration) the state machine
     can reach, in the kernel's own fp64 expressions (R = 30: a_rest 39, b_rest 24, full 33, slopes -6 / +9 / +6 / -9)."""
     for t in range(0, 121):                       # inhaling, and the unchanged ellipse at release (water = t / 120)

@@ -25,7 +25,8 @@
 //     fp64 offset pair each step (twelve ds_write_b128) for the same purpose.
 // The mirror is written where the food set changes (kernel entry, capture, placement, reset): rare.
 #pragma once
-#include "salp_food_lds.h"
+#include "salp_food_select.h"   // FoodScan, kFoodLanes, bcast_lane, observe_selected
+#include "salp_food_lds.h"      // place_food_coop (named in the comments below); keeps the order of definitions the kernel sees
 
 namespace salp {
 
@@ -472,7 +473,7 @@ __device__ __forceinline__ StepOut step_env_reg(Env<FMAX>& e, FoodF32<FMAX, INRE
 // Wavefront-cooperative placement (place_food_coop of salp_food_lds.h) on register-resident foods: the foods
 // of the env being served (lane L) are broadcast with v_readlane (slot index static, L wave-uniform), an
 // accepted point is written into lane L's slot through a wave-uniform switch.  Draws, order and stream
-// consumption are exactly those of the serial sampler (place_food in salp_device.h).
+// consumption are exactly those of the serial sampler (place_food in salp_env.h).
 // `scratch`: FMAX double2 of LDS private to the wavefront (the kernel lends the tile bytes, idle at this point of the
 // step).  An accepted point is wave-uniform and belongs in ONE lane's slot `slot` (wave-uniform as well): written as
 // `for k: if (slot == k) if (lane == L) fx[k] = ax` the compiler predicates all FMAX bodies — 97 instructions per

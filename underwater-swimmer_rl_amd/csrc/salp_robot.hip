@@ -26,7 +26,7 @@
 #include <vector>
 
 #include "../../include/salp_robot.h"
-#include "salp_device.h"   // philox4x32_10, u53
+#include "salp_philox.h"   // philox4x32_10, u53
 #include "salp_fp64_math.h"   // sincos_small, sincos_euler, advance_euler_sincos, rcp_nr, sqrt_nr
 #include "salp_host.h"        // fail, HIP_TRY, DeviceScope, check_device_id, StageBuffer, staged()
 

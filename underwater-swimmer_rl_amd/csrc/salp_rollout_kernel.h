@@ -77,7 +77,7 @@ __device__ __forceinline__ int wave_sum(int v) {
 }
 
 // ---- experiment builds: what they put into the kernel, as one-line macros (no product build expands one to code) ----
-// -DSALP_EXP_STAMPS: the wavefront's phase stamps (salp_device.h SALP_STAMP) are opened before the step loop, handed to the
+// -DSALP_EXP_STAMPS: the wavefront's phase stamps (salp_exp.h SALP_STAMP) are opened before the step loop, handed to the
 // step with SALP_STAMP_PASS and written out behind the loop.
 #ifdef SALP_EXP_STAMPS
 constexpr int kStampWaves = 8192;
@@ -332,7 +332,7 @@ __global__ __launch_bounds__(kBlock, (RolloutTraits<FMAX, KMAX, FORCED, STD, SIG
         const bool finished = hit || (e.ssf > P.max_steps_wo_food) || (!P.respawn && nlive == 0);
         const bool have_rel0 = !__any(e.ssf == 0 || finished) && (fq.idx[0] >= 0);
         const float rel0 = relative_heading<true>(fq.by[0], fq.bx[0], (float)e.th);
-        observe_lds<KMAX, STD>(e, P, r0, K, fq, nlive, have_rel0, rel0, ob0);
+        observe_selected<KMAX, STD>(e, P, r0, K, fq, nlive, have_rel0, rel0, ob0);
       } else {
         bool have_rel0 = false;
         float rel0 = 0.f;
@@ -545,10 +545,10 @@ __global__ __launch_bounds__(kBlock, (RolloutTraits<FMAX, KMAX, FORCED, STD, SIG
               scan_foods<KMAX, false, true>(food, C.F, e.x, e.y, 0.0, fq, c_, h_, nlive);
               if (__any(fq.tie)) exact_order_lds<KMAX>(food, C.F, K, e.x, e.y, fq);
               resolve<KMAX>(food, K, e.x, e.y, fq);
-              observe_lds<KMAX, STD>(e, C, rmax, K, fq, nlive, false, 0.f, fo);
+              observe_selected<KMAX, STD>(e, C, rmax, K, fq, nlive, false, 0.f, fo);
             } else if constexpr (T::REGF) {
               select_foods_reg<FMAX, KMAX, false, true>(e, ff, mir, K, (STD ? StdConsts::tie_c0 : C.tie_c0), fq, nlive);
-              observe_lds<KMAX, STD>(e, C, rmax, K, fq, nlive, false, 0.f, fo);
+              observe_selected<KMAX, STD>(e, C, rmax, K, fq, nlive, false, 0.f, fo);
             } else {
               observe<FMAX, KMAX, STD>(e, C, rmax, have_rel, o.rel, fo);
             }
@@ -601,9 +601,9 @@ __global__ __launch_bounds__(kBlock, (RolloutTraits<FMAX, KMAX, FORCED, STD, SIG
       float ob[T::OBS];
       if constexpr (T::REGF) {
         // all FMAX slots of every lane alive (the steady state with respawn) => every lane shows K foods
-        if ((KMAX <= FMAX) && K >= 1 && __all(nlive == FMAX)) observe_lds<KMAX, STD, true>(e, P, rmax, K, fq, nlive, have_rel, o.rel, ob);
-        else observe_lds<KMAX, STD>(e, P, rmax, K, fq, nlive, have_rel, o.rel, ob);
-      } else if constexpr (T::LDSF) observe_lds<KMAX, STD>(e, P, rmax, K, fq, nlive, have_rel, o.rel, ob);
+        if ((KMAX <= FMAX) && K >= 1 && __all(nlive == FMAX)) observe_selected<KMAX, STD, true>(e, P, rmax, K, fq, nlive, have_rel, o.rel, ob);
+        else observe_selected<KMAX, STD>(e, P, rmax, K, fq, nlive, have_rel, o.rel, ob);
+      } else if constexpr (T::LDSF) observe_selected<KMAX, STD>(e, P, rmax, K, fq, nlive, have_rel, o.rel, ob);
       else observe<FMAX, KMAX, STD>(e, P, rmax, have_rel, o.rel, ob);
       SALP_STAMP(8);
       // (per-lane 96-B rows stored straight from registers, without the LDS transpose: 2.1x slower, r01 ab_notes)

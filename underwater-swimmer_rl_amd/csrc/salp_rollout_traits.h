@@ -105,7 +105,7 @@ struct ColdBlock {
 // for the prefetch alone instead of draining all stores with s_waitcnt vmcnt(0) every step).
 // RAGGED = true: the same loop with per-lane predicates; the host launches it for the last
 // n % 64 envs only (one wavefront).  `env_begin/env_end`: the env range of this launch.
-// STD = false: where the hot path's constants come from (open_consts, salp_device.h) — the device copy, function by
+// STD = false: where the hot path's constants come from (open_consts, salp_params.h) — the device copy, function by
 // function, for the 4- and 8-slot kernels; the by-value launch parameters for the others (MEMC).
 template <int FMAX_, int KMAX_, bool FORCED_, bool STD_, int SIG_, bool RAGGED_, int ACT_>
 struct RolloutTraits {

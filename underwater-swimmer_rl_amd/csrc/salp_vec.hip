@@ -1,6 +1,8 @@
 // salp_vec.hip — the service kernels (reset / observe, state snapshots, generated actions, reseed, policy relayout and
 // noise step) and the C ABI of include/salp_vec.h.  The fused step/rollout kernel is salp_rollout_kernel.h; its
 // instantiations are compiled by the salp_rollout_*.hip units and reached through their rollout_unit_fn functions.
+// The config's defaults and ranges and the launch parameters derived from it (default_config, validate, make_params,
+// is_std) are the host functions of salp_params.h.
 #include <new>
 #include <string>
 #include <type_traits>
@@ -180,60 +182,11 @@ struct salp_policy {
 
 namespace {
 
-DevParams make_params(const salp_config_t& c, int64_t n, int64_t pitch, uint64_t seed, int64_t base) {
-  DevParams P;
-  memset(&P, 0, sizeof(P));
-  P.W = (double)c.width; P.H = (double)c.height;
-  P.half_W = (double)c.width / 2; P.half_H = (double)c.height / 2;
-  P.margin = c.tank_margin;
-  P.wall_hi_x = (double)c.width - c.tank_margin; P.wall_hi_y = (double)c.height - c.tank_margin;
-  P.R = c.base_radius;
-  P.a_rest = c.base_radius * 1.3; P.b_rest = c.base_radius * 0.8; P.ab_full = c.base_radius * 1.1;
-  P.da_inh = P.ab_full - P.a_rest; P.db_inh = P.ab_full - P.b_rest;
-  P.da_exh = P.a_rest - P.ab_full; P.db_exh = P.b_rest - P.ab_full;
-  P.max_nozzle = c.max_nozzle_angle; P.nozzle_rate = c.nozzle_response_rate;
-  P.thrust_force = c.max_thrust_force; P.drag = c.drag_coefficient; P.ang_drag = c.angular_drag;
-  P.exhale_dur_d = (double)c.exhale_duration;
-  P.food_radius = c.food_radius; P.min_food_dist2 = c.min_food_distance * c.min_food_distance;
-  P.food_xlo = c.tank_margin + c.food_radius;
-  P.food_xspan = ((double)c.width - c.tank_margin - c.food_radius) - P.food_xlo;
-  P.food_ylo = P.food_xlo;
-  P.food_yspan = ((double)c.height - c.tank_margin - c.food_radius) - P.food_ylo;
-  P.food_reward = c.food_reward; P.collision_penalty = c.collision_penalty;
-  P.time_penalty = c.time_penalty; P.efficiency_bonus = c.efficiency_bonus;
-  P.prox_w = c.proximity_reward_weight;
-  P.inv_W = 1.0 / P.W; P.inv_H = 1.0 / P.H; P.inv_pi = 1.0 / 3.141592653589793;
-  P.inv_R = 1.0 / c.base_radius; P.inv_max_nozzle = 1.0 / c.max_nozzle_angle;
-  P.inv_diag = (float)(1.0 / sqrt(P.W * P.W + P.H * P.H));
-  { const double L = P.W > P.H ? P.W : P.H; P.tie_c0 = (float)(1.4e-7 * L * L); }
-  P.inhale_dur = c.inhale_duration; P.exhale_dur = c.exhale_duration;
-  P.cycle_len = c.inhale_duration + c.exhale_duration + c.rest_duration;
-  P.max_steps_wo_food = c.max_steps_without_food;
-  P.F = c.num_food_items; P.K = c.max_observed_food;
-  P.F_base = c.num_food_items;
-  P.forced = c.forced_breathing != 0; P.random_food_count = c.random_food_count != 0;
-  P.respawn = c.respawn_food != 0;
-  P.autoreset = c.no_autoreset == 0;
-  P.seed = nullptr;   // set by salp_vec_create once the ColdBlock exists
-  P.env_base = (uint64_t)base; P.n = n; P.pitch = pitch;
-  return P;
-}
-
+// make_params(), is_std() and the config's ranges: salp_params.h (host functions, under test without a GPU).
 int validate(const salp_config_t* c) {
-  if (!c) return fail(SALP_ERR_INVALID, "config is NULL");
-  if (c->struct_size != sizeof(salp_config_t))
-    return fail(SALP_ERR_INVALID, "salp_config_t.struct_size mismatch (ABI version skew)");
-  if (c->width <= 0 || c->height <= 0) return fail(SALP_ERR_INVALID, "width/height must be positive");
-  if (c->num_food_items < 0 || c->num_food_items > SALP_MAX_FOOD)
-    return fail(SALP_ERR_INVALID, "num_food_items must be in [0, SALP_MAX_FOOD]");
-  if (c->max_observed_food < 0 || c->max_observed_food > SALP_MAX_OBSERVED_FOOD)
-    return fail(SALP_ERR_INVALID, "max_observed_food must be in [0, SALP_MAX_OBSERVED_FOOD]");
-  if (c->inhale_duration < 1 || c->inhale_duration > 255 || c->exhale_duration < 4 || c->exhale_duration > 254)
-    return fail(SALP_ERR_INVALID, "inhale_duration in [1,255], exhale_duration in [4,254] required");
-  if (c->rest_duration < 0) return fail(SALP_ERR_INVALID, "rest_duration must be >= 0");
-  if (!(c->base_radius > 0) || !(c->max_nozzle_angle > 0))
-    return fail(SALP_ERR_INVALID, "base_radius and max_nozzle_angle must be positive");
-  return SALP_OK;
+  const char* why = "";
+  const int rc = salp::validate(c, &why);
+  return rc == SALP_OK ? rc : fail(rc, why);
 }
 
 typedef void (*reset_fn)(DevParams, DevState, const uint8_t*, float*, int);
@@ -266,22 +219,6 @@ reset_fn reset_kernel_k3(const salp_vec* h) {
 reset_fn reset_kernel_for(const salp_vec* h) {
   if (h->kmax == 3) return h->std_consts ? reset_kernel_k3<true>(h) : reset_kernel_k3<false>(h);
   return (reset_fn)salp_reset_kernel<16, 8, false>;
-}
-
-// True when every constant of DevParams equals its StdConsts literal (the reference's defaults).
-bool is_std(const DevParams& P) {
-  typedef StdConsts C;
-  return P.W == C::W && P.H == C::H && P.half_W == C::half_W && P.half_H == C::half_H && P.margin == C::margin &&
-         P.wall_hi_x == C::wall_hi_x && P.wall_hi_y == C::wall_hi_y && P.R == C::R && P.a_rest == C::a_rest &&
-         P.b_rest == C::b_rest && P.ab_full == C::ab_full && P.da_inh == C::da_inh && P.db_inh == C::db_inh &&
-         P.da_exh == C::da_exh && P.db_exh == C::db_exh && P.max_nozzle == C::max_nozzle &&
-         P.nozzle_rate == C::nozzle_rate && P.thrust_force == C::thrust_force && P.drag == C::drag &&
-         P.ang_drag == C::ang_drag && P.exhale_dur_d == C::exhale_dur_d && P.food_radius == C::food_radius &&
-         P.min_food_dist2 == C::min_food_dist2 && P.food_xlo == C::food_xlo && P.food_xspan == C::food_xspan &&
-         P.food_ylo == C::food_ylo && P.food_yspan == C::food_yspan && P.inv_W == C::inv_W && P.inv_H == C::inv_H &&
-         P.inv_pi == C::inv_pi && P.inv_R == C::inv_R && P.inv_max_nozzle == C::inv_max_nozzle &&
-         P.inv_diag == C::inv_diag && P.tie_c0 == C::tie_c0 && P.inhale_dur == C::inhale_dur && P.exhale_dur == C::exhale_dur &&
-         P.cycle_len == C::cycle_len;
 }
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }   // workgroups of kBlock threads
@@ -444,16 +381,7 @@ int salp_device_count(void) {
 
 int salp_config_default(salp_config_t* c) {
   if (!c) return fail(SALP_ERR_INVALID, "cfg is NULL");
-  memset(c, 0, sizeof(*c));
-  c->struct_size = (uint32_t)sizeof(*c);
-  c->width = 800; c->height = 600; c->num_food_items = 5; c->max_observed_food = 3;
-  c->max_steps_without_food = 1500; c->forced_breathing = 1; c->random_food_count = 0; c->respawn_food = 1;
-  c->food_reward = 10.0; c->collision_penalty = -50.0; c->time_penalty = -0.1; c->efficiency_bonus = 1.0;
-  c->proximity_reward_weight = 0.0;
-  c->tank_margin = 50.0; c->base_radius = 30.0; c->max_thrust_force = 100.0; c->drag_coefficient = 0.98;
-  c->angular_drag = 0.95; c->max_nozzle_angle = 3.141592653589793 / 3; c->nozzle_response_rate = 0.05;
-  c->food_radius = 15.0; c->min_food_distance = 80.0;
-  c->inhale_duration = 120; c->exhale_duration = 150; c->rest_duration = 60;
+  default_config(c);     // salp_params.h
   return SALP_OK;
 }
 
