@@ -1,7 +1,7 @@
 #!/bin/bash
 # gfx950 assembly of one csrc/*.hip with the product flags: bash profiles/isa_dump.sh out.s [UNIT.hip] [-DNAME ...]
 # UNIT defaults to salp_rollout_f1_std.hip, the one-food literal-constant kernels (the bench kernel among them);
-# salp_vec.hip holds the service kernels.  Feed to profiles/isa_regs.py / isa_stats.py / isa_ophist.py / isa_cndruns.py;
+# salp_vec.hip compiles the service kernels (salp_service_kernels.h).  Feed to profiles/isa_regs.py / isa_stats.py / isa_ophist.py / isa_cndruns.py;
 # profiles/isa_kernel_diff.py compares the kernels of two sets of dumps.
 set -e
 OUT=$1; shift

@@ -1,0 +1,101 @@
+"""ctypes bindings of the in-kernel policy's layout functions on the host — TEST INFRASTRUCTURE.
+
+oracle/libsalp_policy_host.so is tests/policy_host.cpp: the host sections of csrc/salp_policy.h and csrc/salp_params.h
+compiled as plain C++.  What salp_policy_create and salp_vec_set_state decide before they touch a GPU is callable here
+without one: check_policy_desc(), policy_block_map(), policy_header() and check_snapshot().
+"""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+
+from underwater_swimmer_rl_amd.policy import CPolicyDesc
+
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_SO = os.path.join(_ROOT, "oracle", "libsalp_policy_host.so")
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        csrc = os.path.join(_ROOT, "underwater-swimmer_rl_amd", "csrc")
+        deps = [os.path.join(_ROOT, "tests", "policy_host.cpp"), os.path.join(_ROOT, "include", "salp_vec.h"),
+                os.path.join(csrc, "salp_policy.h"), os.path.join(csrc, "salp_params.h")]
+        if not os.path.isfile(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(d) for d in deps):
+            subprocess.run(["make", "-C", os.path.join(_ROOT, "oracle"), "-s", "-B", "libsalp_policy_host.so"], check=True)
+        L = ctypes.CDLL(_SO)
+        desc, i32p = ctypes.POINTER(CPolicyDesc), ctypes.POINTER(ctypes.c_int32)
+        L.salp_policy_host_header_slots.argtypes = [i32p]
+        L.salp_policy_host_header_slots.restype = None
+        L.salp_policy_host_check.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, desc, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_char_p)]
+        L.salp_policy_host_map.argtypes = [ctypes.c_int, ctypes.c_int, desc, ctypes.c_int, i32p, ctypes.c_int]
+        L.salp_policy_host_header.argtypes = [desc, ctypes.c_int, ctypes.c_int64, ctypes.c_int, i32p]
+        L.salp_policy_host_header.restype = None
+        L.salp_policy_host_check_snapshot.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
+        L.salp_policy_host_max_angle.restype = ctypes.c_double
+        _lib = L
+    return _lib
+
+
+def desc(n_hidden=0, hidden=(0, 0), out=0, P=1, size=None) -> CPolicyDesc:
+    """A salp_policy_desc_t, field by field (size None: the struct's own size)."""
+    d = CPolicyDesc()
+    d.struct_size = ctypes.sizeof(CPolicyDesc) if size is None else size
+    d.n_hidden, d.out_activation, d.n_policies = n_hidden, out, P
+    d.hidden[0], d.hidden[1] = hidden
+    return d
+
+
+def desc_of(hidden=(), out=0, P=1) -> CPolicyDesc:
+    """The descriptor of a policy with these hidden widths."""
+    return desc(len(hidden), tuple(hidden) + (0,) * (2 - len(hidden)), out, P)
+
+
+def header_slots() -> dict:
+    """The header's word indices by name, and WORDS."""
+    v = (ctypes.c_int32 * 9)()
+    lib().salp_policy_host_header_slots(v)
+    names = ("NHIDDEN", "H0", "H1", "OUT", "STRIDE", "GROUP", "COUNT", "GAUSS", "NOISE")
+    return dict(zip(names, v), WORDS=lib().salp_policy_host_header_words())
+
+
+def check(d, obs_dim=24, act_dim=1, kmax=3, n_envs=256, gaussian=False):
+    """(status, public words or None, message) of check_policy_desc(); d None is the NULL descriptor."""
+    words, why = ctypes.c_int(-1), ctypes.c_char_p()
+    rc = lib().salp_policy_host_check(obs_dim, act_dim, kmax, n_envs, None if d is None else ctypes.byref(d), int(gaussian),
+                                      ctypes.byref(words), ctypes.byref(why))
+    return rc, (words.value if rc == 0 else None), why.value.decode()
+
+
+def block_map(d, obs_dim=24, act_dim=1, gaussian=False) -> np.ndarray:
+    """policy_block_map(): int32 [stride]."""
+    stride = lib().salp_policy_host_map(obs_dim, act_dim, ctypes.byref(d), int(gaussian), None, 0)
+    m = np.full(stride, -2, np.int32)
+    assert lib().salp_policy_host_map(obs_dim, act_dim, ctypes.byref(d), int(gaussian),
+                                      m.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), stride) == stride
+    return m
+
+
+def header(d, stride, n_envs, gaussian=False) -> np.ndarray:
+    """policy_header(): int32 [PH_WORDS]."""
+    hd = np.full(lib().salp_policy_host_header_words(), -2, np.int32)
+    lib().salp_policy_host_header(ctypes.byref(d), stride, n_envs, int(gaussian), hd.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    return hd
+
+
+def check_snapshot(n, f64, i32):
+    """(status, message) of check_snapshot() on float64 [rows, n] / int32 [rows, n] (either may be None)."""
+    msg = ctypes.create_string_buffer(200)
+    for a, t in ((f64, np.float64), (i32, np.int32)):
+        assert a is None or (a.dtype == t and a.flags.c_contiguous and a.shape[1] == n)
+    rc = lib().salp_policy_host_check_snapshot(n, None if f64 is None else f64.ctypes.data, None if i32 is None else i32.ctypes.data,
+                                               msg, len(msg))
+    return rc, msg.value.decode()
+
+
+def max_angle() -> float:
+    return lib().salp_policy_host_max_angle()

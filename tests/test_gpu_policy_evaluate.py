@@ -217,7 +217,7 @@ def test_split_equals_whole_and_zeros_equal_overwriting(name):
                                     ("class_default_F5", 100)])
 def test_other_constant_sets_and_launch_forms(case, n):
     """The summary kernels that the case table does not reach — run-time constants with 1, 8, 12 and 16 slots (they take their
-    constants from another place than their rollout twins, csrc/salp_vec.hip MEMC) and the predicated forms (n = 100: one
+    constants from another place than their rollout twins, csrc/salp_rollout_traits.h MEMC) and the predicated forms (n = 100: one
     ragged launch) — against `summarize_rollout` of salp_vec_rollout_policy from the same start state."""
     HP = 160
     cfg = pc.case_cfg(case)

@@ -147,7 +147,7 @@ def test_prologue_observation_is_the_row_before_it(case, no_autoreset):
     prologue forms from the stored state: in calls of horizon 1 it must be the row the call before wrote, column by column —
     whatever the case's MLP happens to be sensitive to.  Column 13 is the one that depends on more than the state's values:
     the step hands the reward's own bearing of the nearest food to the row unless the food set or the episode changed in
-    that step (csrc/salp_vec.hip, the policy prologue); both kinds of wavefront-step must occur."""
+    that step (csrc/salp_rollout_kernel.h, the policy prologue); both kinds of wavefront-step must occur."""
     n, HP = 256, 64
     spec = dict(pc.CASES[case])
     spec.setdefault("max_steps_without_food", pc.DEFAULT_BUDGET)

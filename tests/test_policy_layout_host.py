@@ -1,0 +1,270 @@
+"""Where every weight of an in-kernel policy sits in its device block is decided on the host, by the map that
+salp_policy_create hands to the relayout kernel; a wrong entry evaluates another network with no error.  The host section
+of csrc/salp_policy.h (check_policy_desc, policy_block_map, policy_header) and check_snapshot of csrc/salp_params.h compile
+as plain C++ (tests/policy_host.cpp), so the map is checked here against the layout that the header's comment states, the
+descriptor's and the snapshot's ranges at their edges, and the header words, all without a GPU."""
+import ctypes
+import itertools
+import math
+
+import numpy as np
+import pytest
+
+import policy_host_lib as ph
+from underwater_swimmer_rl_amd import _capi
+from underwater_swimmer_rl_amd.policy import CPolicyDesc, GaussianPolicy, MLPPolicy
+
+SALP_OK, SALP_ERR_INVALID = 0, -1
+OBS_DIM = 24
+HIDDEN = [(), (16,), (64,), (16, 16), (16, 64), (32, 48), (64, 64)]
+SHAPES = list(itertools.product([1, 2], HIDDEN, [False, True]))      # act_dim, hidden, gaussian: 28 shapes
+IDS = [f"A{a}-{'x'.join(map(str, h)) or 'linear'}-{'gauss' if g else 'plain'}" for a, h, g in SHAPES]
+
+
+def counting_policy(act_dim, hidden, gaussian):
+    """A policy whose public layout is float32(k + 1) at word k: every word distinct, exact and non-zero.  The arrays are
+    cut from that sequence in the order of include/salp_vec.h (per layer W[out][in] row-major, then b[out]; a Gaussian
+    policy's W_ls, b_ls; scale; shift)."""
+    pos = [0]
+
+    def take(*shape):
+        k = int(np.prod(shape))
+        a = np.arange(pos[0] + 1, pos[0] + k + 1, dtype=np.float32).reshape(shape)
+        pos[0] += k
+        return a
+    layers, d = [], OBS_DIM
+    for o in hidden + (act_dim,):
+        layers.append((take(o, d), take(o)))
+        d = o
+    d = hidden[-1] if hidden else OBS_DIM       # what both heads read
+    if gaussian:
+        log_std = (take(act_dim, d), take(act_dim))
+        p = GaussianPolicy.from_layers(layers, log_std, take(act_dim), take(act_dim))
+    else:
+        p = MLPPolicy.from_layers(layers, take(act_dim), take(act_dim))
+    assert pos[0] < 2 ** 24 and np.array_equal(p.pack()[0], np.arange(1, pos[0] + 1, dtype=np.float32))
+    return p
+
+
+def apply_map(m, pub):
+    """What the relayout kernel does with one policy: block[k] = pub[map[k]], 0 where map[k] < 0."""
+    return np.where(m >= 0, pub[np.maximum(m, 0)], np.float32(0.0)).astype(np.float32)
+
+
+def decode(block, act_dim, hidden, gaussian):
+    """One policy's words of the device block, read as the comment at the top of csrc/salp_policy.h lays them out.
+    Returns the layers [(W, b), ...] (the last one the output layer), scale, shift, the log-std head or None, and every
+    padding word."""
+    pos, pads, layers, d = 0, [], [], OBS_DIM
+
+    def take(k):
+        nonlocal pos
+        pos += k
+        return block[pos - k:pos]
+    for o in hidden:      # per chunk c of 16 units: b[16 c .. 16 c + 15], then for i = 0 .. IN-1 the 16 weights W[16 c + j][i]
+        W, b = np.empty((o, d), np.float32), np.empty(o, np.float32)
+        for c in range(o // 16):
+            b[16 * c:16 * c + 16] = take(16)
+            W[16 * c:16 * c + 16, :] = take(16 * d).reshape(d, 16).T
+        layers.append((W, b))
+        d = o
+    A, rs = act_dim, (d + 15) // 16 * 16
+    tail = take(16)       # b_last[A], scale[A], shift[A], zero padding
+    b_last, scale, shift = tail[:A], tail[A:2 * A], tail[2 * A:3 * A]
+    pads.append(tail[3 * A:])
+    rows = take(A * rs).reshape(A, rs)        # W_last[a][0 .. IN-1], zero-padded to a multiple of 16 words
+    layers.append((rows[:, :d], b_last))
+    pads.append(rows[:, d:].ravel())
+    log_std = None
+    if gaussian:
+        tail = take(16)   # b_ls[A], zero padding
+        pads.append(tail[A:])
+        rows = take(A * rs).reshape(A, rs)
+        log_std = (rows[:, :d], tail[:A])
+        pads.append(rows[:, d:].ravel())
+    assert pos == len(block), (pos, len(block))
+    return layers, scale, shift, log_std, np.concatenate(pads)
+
+
+@pytest.mark.parametrize("act_dim,hidden,gaussian", SHAPES, ids=IDS)
+def test_the_map_puts_every_weight_where_the_layout_says(act_dim, hidden, gaussian):
+    p = counting_policy(act_dim, hidden, gaussian)
+    d = p.desc()
+    rc, words, why = ph.check(d, OBS_DIM, act_dim, gaussian=gaussian)
+    assert (rc, why) == (SALP_OK, "") and words == p.words
+    m = ph.block_map(d, OBS_DIM, act_dim, gaussian)
+    stride = len(m)
+    # structure: whole 16-word groups; every public word exactly once; the rest zero
+    assert stride % 16 == 0
+    assert np.array_equal(np.sort(m[m >= 0]), np.arange(words))
+    assert m.min() >= -1 and int((m == -1).sum()) == stride - words
+    # meaning: the block decodes to the arrays the public layout was built from, and to exactly 0.0 in every pad
+    layers, scale, shift, log_std, pads = decode(apply_map(m, p.pack()[0]), act_dim, hidden, gaussian)
+    assert len(layers) == len(p.layers)
+    for (W, b), (Wp, bp) in zip(layers, p.layers):
+        assert np.array_equal(W, Wp[0]) and np.array_equal(b, bp[0])
+    assert np.array_equal(scale, p.scale[0]) and np.array_equal(shift, p.shift[0])
+    if gaussian:
+        assert np.array_equal(log_std[0], p.log_std[0][0]) and np.array_equal(log_std[1], p.log_std[1][0])
+    assert len(pads) == stride - words and not pads.any() and not np.signbit(pads).any()
+
+
+@pytest.mark.parametrize("act_dim,hidden", [(a, h) for a, h, g in SHAPES if g], ids=[i for i, s in zip(IDS, SHAPES) if s[2]])
+def test_a_gaussian_block_starts_with_the_block_of_its_mean_policy(act_dim, hidden):
+    """What deterministic runs of a Gaussian policy rely on: they read a Gaussian block as if it were the mean policy's."""
+    g = counting_policy(act_dim, hidden, True)
+    mean = g.mean_policy()
+    mg, mm = ph.block_map(g.desc(), OBS_DIM, act_dim, True), ph.block_map(mean.desc(), OBS_DIM, act_dim, False)
+    assert len(mm) < len(mg)
+    assert np.array_equal(apply_map(mg, g.pack()[0])[:len(mm)], apply_map(mm, mean.pack()[0]))
+
+
+def test_header_words():
+    s = ph.header_slots()
+    assert s["WORDS"] == 16 and sorted(v for k, v in s.items() if k != "WORDS") == list(range(9))
+    d = ph.desc_of((32, 48), out=1, P=2)
+    hd = ph.header(d, 4000, 256, gaussian=False)
+    want = {"NHIDDEN": 2, "H0": 32, "H1": 48, "OUT": 1, "STRIDE": 4000, "GROUP": 128, "COUNT": 2, "GAUSS": 0}
+    assert {k: int(hd[s[k]]) for k in want} == want
+    named = {s[k] for k in want}
+    assert not hd[[i for i in range(16) if i not in named]].any()          # the noise step (two words) and the unused words
+    d = ph.desc_of((16,), P=1)
+    hd = ph.header(d, 464, 256, gaussian=True)
+    want = {"NHIDDEN": 1, "H0": 16, "H1": 0, "OUT": 0, "STRIDE": 464, "GROUP": 0x7FFFFFFF, "COUNT": 1, "GAUSS": 1}
+    assert {k: int(hd[s[k]]) for k in want} == want
+    assert hd[s["NOISE"]] == 0 and hd[s["NOISE"] + 1] == 0
+
+
+WIDTHS = "hidden widths must be multiples of 16 in [16, 64] (unused entries 0)"
+WAVES = "n_policies > 1 needs n_envs % P == 0 and (n_envs / P) % 64 == 0"
+REFUSED = [   # descriptor, keyword arguments of the check, message
+    (ph.desc(n_hidden=3, hidden=(32, 32)), {}, "n_hidden must be 0, 1 or 2"),
+    (ph.desc(n_hidden=-1, hidden=(32, 32)), {}, "n_hidden must be 0, 1 or 2"),
+    (ph.desc(n_hidden=2, hidden=(32, 24)), {}, WIDTHS),
+    (ph.desc(n_hidden=2, hidden=(80, 32)), {}, WIDTHS),
+    (ph.desc(n_hidden=2, hidden=(0, 32)), {}, WIDTHS),
+    (ph.desc(n_hidden=1, hidden=(32, 32)), {}, WIDTHS),                     # an unused entry non-zero
+    (ph.desc(n_hidden=2, hidden=(32, 32), out=2), {}, "out_activation must be SALP_POLICY_OUT_TANH or SALP_POLICY_OUT_CLIP"),
+    (ph.desc(n_hidden=2, hidden=(32, 32), out=-1), {}, "out_activation must be SALP_POLICY_OUT_TANH or SALP_POLICY_OUT_CLIP"),
+    (ph.desc(n_hidden=2, hidden=(32, 32), P=0), {}, "n_policies must be >= 1"),
+    (ph.desc(n_hidden=2, hidden=(32, 32), P=3), {}, WAVES),
+    (ph.desc(n_hidden=2, hidden=(32, 32), P=8), {}, WAVES),
+    (ph.desc(n_hidden=2, hidden=(32, 32), size=20), {}, "salp_policy_desc_t.struct_size mismatch"),
+    (ph.desc(n_hidden=2, hidden=(32, 32), out=1), dict(gaussian=True), "a Gaussian policy's out_activation must be SALP_POLICY_OUT_TANH"),
+    (ph.desc(n_hidden=2, hidden=(32, 32)), dict(kmax=8), "policies need a handle with max_observed_food == 3"),
+    (ph.desc(n_hidden=2, hidden=(32, 32)), dict(kmax=2), "policies need a handle with max_observed_food == 3"),
+    (None, {}, "handle/desc is NULL"),
+]
+
+
+@pytest.mark.parametrize("d,kw,message", REFUSED, ids=[f"{i}-{r[2][:24]}" for i, r in enumerate(REFUSED)])
+def test_descriptors_outside_the_ranges_are_refused(d, kw, message):
+    assert ph.check(d, n_envs=256, **kw) == (SALP_ERR_INVALID, None, message)
+
+
+def test_the_last_value_inside_each_range_is_accepted():
+    ok = lambda d, **kw: ph.check(d, n_envs=256, **kw)[::2] == (SALP_OK, "")
+    assert ok(ph.desc(n_hidden=0)) and ok(ph.desc(n_hidden=2, hidden=(16, 64))) and ok(ph.desc(n_hidden=2, hidden=(64, 16)))
+    assert ok(ph.desc(n_hidden=1, hidden=(16, 0))) and ok(ph.desc(n_hidden=1, hidden=(64, 0)))
+    assert ok(ph.desc(out=0)) and ok(ph.desc(out=1)) and ok(ph.desc(out=0), gaussian=True)
+    assert ok(ph.desc(P=1)) and ok(ph.desc(P=2)) and ok(ph.desc(P=4))
+    assert ok(ph.desc(), kmax=3)
+    assert ctypes.sizeof(CPolicyDesc) == 24
+
+
+def test_policies_share_the_envs_in_whole_wavefronts():
+    two = ph.desc(P=2)
+    assert ph.check(two, n_envs=128)[::2] == (SALP_OK, "")
+    assert ph.check(two, n_envs=64) == (SALP_ERR_INVALID, None, WAVES)       # 32 envs each
+    assert ph.check(two, n_envs=192) == (SALP_ERR_INVALID, None, WAVES)      # 96 envs each
+    assert ph.check(ph.desc(P=3), n_envs=192)[::2] == (SALP_OK, "")
+    assert ph.check(ph.desc(P=3), n_envs=193) == (SALP_ERR_INVALID, None, WAVES)
+    assert ph.check(ph.desc(P=1), n_envs=100)[::2] == (SALP_OK, "")          # one policy serves any n_envs
+
+
+def test_words_are_those_of_the_python_policies():
+    for act_dim, hidden, gaussian in SHAPES:
+        p = counting_policy(act_dim, hidden, gaussian)
+        assert ph.check(p.desc(), OBS_DIM, act_dim, gaussian=gaussian)[1] == p.words == p.pack().shape[1]
+
+
+# ---------------------------------------------------------------------- check_snapshot (the ranges of salp_vec_set_state)
+N, FOODS = 5, 3
+
+
+def snapshot():
+    """A snapshot inside every range, values that differ per env."""
+    f64 = np.zeros((_capi.F_FOOD0 + 2 * FOODS, N), np.float64)
+    i32 = np.zeros((_capi.I_COUNT, N), np.int32)
+    f64[_capi.F_WATER] = np.linspace(0.0, 1.0, N)
+    i32[_capi.I_PHASE] = np.arange(N) % 3
+    return f64, i32
+
+
+def test_snapshot_boundary_values_are_accepted():
+    A = ph.max_angle()
+    assert A == 100.0
+    f64, i32 = snapshot()
+    f64[_capi.F_THETA] = [A, -A, 0.0, math.nextafter(A, 0.0), -0.0]
+    f64[_capi.F_OMEGA] = [-A, A, A, -A, 0.0]
+    f64[_capi.F_WATER] = [0.0, 1.0, -0.0, math.nextafter(1.0, 0.0), 5e-324]
+    i32[_capi.I_PHASE] = [0, 2, 1, 2, 0]
+    i32[_capi.I_TIMER] = [0, 255, 1, 254, 255]
+    i32[_capi.I_EXHALE_DUR] = [255, 0, 255, 0, 1]
+    i32[_capi.I_SHAPE_HOLD] = [7, 0, 7, 6, 1]
+    assert ph.check_snapshot(N, f64, i32) == (SALP_OK, "")
+    assert ph.check_snapshot(N, f64, None) == (SALP_OK, "") and ph.check_snapshot(N, None, i32) == (SALP_OK, "")
+    assert ph.check_snapshot(N, None, None) == (SALP_OK, "")
+    # rows that have no range: any value, NaN included
+    f64[_capi.F_X] = np.nan
+    f64[_capi.F_FOOD0:] = np.nan
+    i32[_capi.I_FOOD_COLLECTED] = -7
+    assert ph.check_snapshot(N, f64, i32) == (SALP_OK, "")
+
+
+A_OUT = math.nextafter(100.0, math.inf)
+F64_OUTSIDE = [   # row, value, the message for env 3 with the other rows 0
+    ("F_THETA", A_OUT, f"set_state: env 3: theta {A_OUT:g} / omega 0 outside [-100, 100] (or NaN)"),
+    ("F_THETA", -A_OUT, f"set_state: env 3: theta {-A_OUT:g} / omega 0 outside [-100, 100] (or NaN)"),
+    ("F_THETA", math.nan, "set_state: env 3: theta nan / omega 0 outside [-100, 100] (or NaN)"),
+    ("F_THETA", math.inf, "set_state: env 3: theta inf / omega 0 outside [-100, 100] (or NaN)"),
+    ("F_OMEGA", A_OUT, f"set_state: env 3: theta 0 / omega {A_OUT:g} outside [-100, 100] (or NaN)"),
+    ("F_OMEGA", -A_OUT, f"set_state: env 3: theta 0 / omega {-A_OUT:g} outside [-100, 100] (or NaN)"),
+    ("F_OMEGA", math.nan, "set_state: env 3: theta 0 / omega nan outside [-100, 100] (or NaN)"),
+    ("F_WATER", -5e-324, "set_state: env 3: water -4.9406564584124654e-324 outside [0, 1] (or NaN)"),
+    ("F_WATER", math.nextafter(1.0, 2.0), "set_state: env 3: water 1.0000000000000002 outside [0, 1] (or NaN)"),
+    ("F_WATER", math.nan, "set_state: env 3: water nan outside [0, 1] (or NaN)"),
+]
+
+
+@pytest.mark.parametrize("row,value,message", F64_OUTSIDE, ids=[f"{r[0]}={r[1]!r}" for r in F64_OUTSIDE])
+def test_snapshot_first_value_outside_and_nan_are_refused(row, value, message):
+    f64, i32 = snapshot()
+    f64[_capi.F_WATER] = 0.0
+    f64[getattr(_capi, row), 3:] = value          # envs 3 and 4 are outside: the message names the first
+    assert ph.check_snapshot(N, f64, i32) == (SALP_ERR_INVALID, message)
+    assert ph.check_snapshot(N, f64, None) == (SALP_ERR_INVALID, message)
+    assert ph.check_snapshot(N, None, i32) == (SALP_OK, "")
+
+
+I32_OUTSIDE = [("I_PHASE", -1), ("I_PHASE", 3), ("I_TIMER", -1), ("I_TIMER", 256), ("I_EXHALE_DUR", -1), ("I_EXHALE_DUR", 256),
+               ("I_SHAPE_HOLD", -1), ("I_SHAPE_HOLD", 8)]
+
+
+@pytest.mark.parametrize("row,value", I32_OUTSIDE, ids=[f"{r}={v}" for r, v in I32_OUTSIDE])
+def test_snapshot_packed_fields_outside_are_refused(row, value):
+    f64, i32 = snapshot()
+    i32[_capi.I_PHASE] = 1
+    i32[getattr(_capi, row), 2:] = value          # envs 2, 3 and 4 are outside: the message names the first
+    v = {k: int(i32[getattr(_capi, k), 2]) for k in ("I_PHASE", "I_TIMER", "I_EXHALE_DUR", "I_SHAPE_HOLD")}
+    message = (f"set_state: env 2: phase {v['I_PHASE']} / timer {v['I_TIMER']} / exhale duration {v['I_EXHALE_DUR']} / "
+               f"shape hold {v['I_SHAPE_HOLD']} outside 0..2 / 0..255 / 0..255 / 0..7")
+    assert ph.check_snapshot(N, f64, i32) == (SALP_ERR_INVALID, message)
+    assert ph.check_snapshot(N, f64, None) == (SALP_OK, "")
+
+
+def test_snapshot_the_doubles_are_checked_before_the_integers():
+    f64, i32 = snapshot()
+    f64[_capi.F_WATER, 4] = 2.0
+    i32[_capi.I_TIMER, 0] = 300
+    assert ph.check_snapshot(N, f64, i32) == (SALP_ERR_INVALID, "set_state: env 4: water 2 outside [0, 1] (or NaN)")

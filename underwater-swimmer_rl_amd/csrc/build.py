@@ -7,7 +7,7 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "salp_vec.hip")             # service kernels and the C ABI of SalpSnakeEnv.step's hot path
+SRC = os.path.join(HERE, "salp_vec.hip")             # the C ABI of SalpSnakeEnv.step's hot path: host code; the service kernels it compiles are salp_service_kernels.h
 SRC_ROBOT = os.path.join(HERE, "salp_robot.hip")     # HEAD Robot simulator
 INCLUDE = os.path.normpath(os.path.join(HERE, "..", "..", "include"))
 

@@ -1,6 +1,7 @@
 // salp_host.h — host-only support shared by the two C ABI files, salp_vec.hip and salp_robot.hip: the error string and
-// HIP_TRY, DeviceScope, the device-id check of the create calls and the staging path of the host-pointer calls
-// (StageBuffer, HostStream, staged()).  Everything here has internal linkage, so each of the two translation units has an
+// HIP_TRY, DeviceScope, the device-id check of the create calls, the frame every call on a handle opens with (CallFrame),
+// launch_1d() and the one body that serves the host-pointer and the device-pointer form of a call (StageBuffer,
+// HostStream, staged()).  Everything here has internal linkage, so each of the two translation units has an
 // error string of its own (salp_last_error and salp_robot_last_error stay independent).  No device code; the rollout
 // kernel units do not include it.
 #ifndef SALP_HOST_H
@@ -50,7 +51,31 @@ int check_device_id(int device_id) {
   return SALP_OK;
 }
 
+// The opening of an ABI call on a handle: the handle's device is current for the frame's scope, `st` is the caller's
+// stream, and a handle that keeps a `last_stream` (the snake handle; the robot handle has none) records it.
+template <class Handle> auto record_stream(Handle* h, hipStream_t st, int) -> decltype((void)(h->last_stream = st)) { h->last_stream = st; }
+template <class Handle> void record_stream(Handle*, hipStream_t, long) {}
+struct CallFrame {
+  DeviceScope dev_scope;
+  hipStream_t st = nullptr;
+  template <class Handle> int enter(Handle* h, void* stream) {
+    HIP_TRY(dev_scope.enter(h->device));
+    st = (hipStream_t)stream;
+    record_stream(h, st, 0);
+    return SALP_OK;
+  }
+};
+
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// One thread per element: `kernel` over n elements in workgroups of `block` threads on `st`, and the launch's status.
+inline unsigned blocks_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
+template <class... Params, class... Args>
+int launch_1d(void (*kernel)(Params...), int64_t n, int block, hipStream_t st, const Args&... args) {
+  hipLaunchKernelGGL(kernel, dim3(blocks_for(n, block)), dim3(block), 0, st, args...);
+  HIP_TRY(hipGetLastError());
+  return SALP_OK;
+}
 
 // Device memory for the host-pointer calls, grown on demand.  `shrink` (the robot handle): a block over 64 MiB is also
 // given up when a call needs less than a quarter of it — a history step with host pointers can stage gigabytes, the
@@ -94,8 +119,14 @@ inline HostStream stream_scratch(size_t bytes) { return {nullptr, bytes, 0, null
 // block `b`, the kIn ones are copied in, `launch` enqueues the call's kernels on the device pointers — a failure there
 // ends the call — then the kOut ones are copied out and the stream is waited for.  The pieces stay where they are until
 // the next call on `b`.
+// `device_ptrs`: the caller's pointers are device pointers.  Each stream's `dev` is then the caller's pointer and `launch`
+// is all there is: nothing is allocated, copied or waited for (such a call can be captured into a graph), `b` is not touched.
 template <int N, class Launch>
-int staged(StageBuffer& b, hipStream_t st, HostStream (&s)[N], Launch&& launch) {
+int staged(StageBuffer& b, hipStream_t st, bool device_ptrs, HostStream (&s)[N], Launch&& launch) {
+  if (device_ptrs) {
+    for (HostStream& x : s) x.dev = x.host;
+    return launch();
+  }
   size_t need = 0;
   for (const HostStream& x : s)
     if (x.present()) need = align_up(need, 256) + x.bytes;

@@ -1,6 +1,7 @@
 // salp_params.h — the parameters of a snake-simulator launch: the packed breathing word, the launch-parameter block
 // DevParams with its literal twin StdConsts and CV(), the SoA state layout and the statistics slots; and the host functions
-// that derive a DevParams from a salp_config_t (default_config, validate, make_params, is_std).
+// that derive a DevParams from a salp_config_t (default_config, validate, make_params, is_std) and check a host snapshot
+// (check_snapshot).
 //
 // The header compiles in two ways, like salp_fp64_math.h:
 //   * with hipcc: what the kernels and salp_vec.hip include, through salp_device.h;
@@ -15,9 +16,10 @@
 #endif
 #include <math.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <string.h>
 
-#include "../../include/salp_vec.h"   // salp_config_t, SALP_OK, SALP_ERR_INVALID, SALP_MAX_*
+#include "../../include/salp_vec.h"   // salp_config_t, SALP_OK, SALP_ERR_INVALID, SALP_MAX_*, SALP_F_* / SALP_I_*
 
 namespace salp {
 
@@ -186,6 +188,37 @@ inline int validate(const salp_config_t* c, const char** why) {
   if (c->rest_duration < 0) return refuse("rest_duration must be >= 0");
   if (!(c->base_radius > 0) || !(c->max_nozzle_angle > 0))
     return refuse("base_radius and max_nozzle_angle must be positive");
+  return (int)SALP_OK;
+}
+
+// The ranges of include/salp_vec.h ("Ranges accepted by salp_vec_set_state"), on a host snapshot of n envs (either array
+// may be NULL).  SALP_OK, or SALP_ERR_INVALID with the reason, which names the first env outside, in msg.
+inline int check_snapshot(int64_t n, const double* f64, const int32_t* i32, char* msg, size_t msg_size) {
+  if (f64) {
+    for (int64_t i = 0; i < n; ++i) {
+      const double th = f64[SALP_F_THETA * n + i], om = f64[SALP_F_OMEGA * n + i], w = f64[SALP_F_WATER * n + i];
+      if (!(fabs(th) <= SALP_SET_STATE_MAX_ANGLE) || !(fabs(om) <= SALP_SET_STATE_MAX_ANGLE)) {
+        snprintf(msg, msg_size, "set_state: env %lld: theta %g / omega %g outside [-%g, %g] (or NaN)", (long long)i, th, om,
+                 SALP_SET_STATE_MAX_ANGLE, SALP_SET_STATE_MAX_ANGLE);
+        return (int)SALP_ERR_INVALID;
+      }
+      if (!(w >= 0.0 && w <= 1.0)) {
+        snprintf(msg, msg_size, "set_state: env %lld: water %.17g outside [0, 1] (or NaN)", (long long)i, w);
+        return (int)SALP_ERR_INVALID;
+      }
+    }
+  }
+  if (i32) {
+    for (int64_t i = 0; i < n; ++i) {
+      const int32_t ph = i32[SALP_I_PHASE * n + i], tm = i32[SALP_I_TIMER * n + i], du = i32[SALP_I_EXHALE_DUR * n + i],
+                    ho = i32[SALP_I_SHAPE_HOLD * n + i];
+      if (ph < 0 || ph > 2 || tm < 0 || tm > 255 || du < 0 || du > 255 || ho < 0 || ho > 7) {
+        snprintf(msg, msg_size, "set_state: env %lld: phase %d / timer %d / exhale duration %d / shape hold %d outside 0..2 / 0..255 / 0..255 / 0..7",
+                 (long long)i, ph, tm, du, ho);
+        return (int)SALP_ERR_INVALID;
+      }
+    }
+  }
   return (int)SALP_OK;
 }
 

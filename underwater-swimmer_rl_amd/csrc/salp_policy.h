@@ -27,14 +27,101 @@
 // same way) — and the only activations that are stored are those of
 // the FIRST of two hidden layers: at most 64 VGPRs (indexed at compile time; the widths are run-time values tested per
 // group of 16, wave-uniform).
+//
+// The header has a host section and a device section.  The host section — the descriptor's ranges, the map from the public
+// layout (include/salp_vec.h) to the block above, and the header words — is plain C++17 with no HIP call and no fail(), like
+// the host functions of salp_params.h: tests/policy_host.cpp compiles it with g++, so the layout is under test without a GPU.
 #pragma once
 #include <stdint.h>
+
+#include <vector>
+
+#include "../../include/salp_vec.h"   // salp_policy_desc_t, SALP_POLICY_OUT_*, SALP_OK, SALP_ERR_INVALID
 
 namespace salp {
 
 enum { PH_NHIDDEN = 0, PH_H0, PH_H1, PH_OUT, PH_STRIDE, PH_GROUP, PH_COUNT, PH_GAUSS, PH_NOISE = 8 /* two words, lo then hi */, PH_WORDS = 16 };
 enum { POLICY_CHUNK = 16, POLICY_MAX_HIDDEN = 64, POLICY_TAIL_WORDS = 16 };
+enum { POLICY_WAVE = 64 };   // envs of one wavefront (kWave of the kernels)
 
+// ------------------------------------------------------------------ host side: descriptor -> ranges, block map, header
+// A wavefront never mixes policies: P policies share the envs in equal runs of whole wavefronts.
+inline int check_n_policies(int64_t n_envs, int P, const char** why) {
+  if (P > 1 && (n_envs % P != 0 || (n_envs / P) % POLICY_WAVE != 0)) {
+    *why = "n_policies > 1 needs n_envs % P == 0 and (n_envs / P) % 64 == 0";
+    return (int)SALP_ERR_INVALID;
+  }
+  return (int)SALP_OK;
+}
+
+// The descriptor's ranges (include/salp_vec.h) for a handle of these dimensions.  SALP_OK with *words (nullable) = public
+// words of one policy, or SALP_ERR_INVALID with the reason in *why.
+inline int check_policy_desc(int obs_dim, int act_dim, int kmax, int64_t n_envs, const salp_policy_desc_t* d, bool gaussian,
+                             int* words, const char** why) {
+  const auto refuse = [why](const char* msg) { *why = msg; return (int)SALP_ERR_INVALID; };
+  if (!d) return refuse("handle/desc is NULL");
+  if (d->struct_size != sizeof(salp_policy_desc_t)) return refuse("salp_policy_desc_t.struct_size mismatch");
+  if (kmax != 3) return refuse("policies need a handle with max_observed_food == 3");
+  if (d->n_hidden < 0 || d->n_hidden > 2) return refuse("n_hidden must be 0, 1 or 2");
+  for (int l = 0; l < 2; ++l) {
+    const int w = d->hidden[l];
+    if (l < d->n_hidden ? (w < POLICY_CHUNK || w > POLICY_MAX_HIDDEN || w % POLICY_CHUNK) : (w != 0))
+      return refuse("hidden widths must be multiples of 16 in [16, 64] (unused entries 0)");
+  }
+  if (d->out_activation != SALP_POLICY_OUT_TANH && d->out_activation != SALP_POLICY_OUT_CLIP)
+    return refuse("out_activation must be SALP_POLICY_OUT_TANH or SALP_POLICY_OUT_CLIP");
+  if (gaussian && d->out_activation != SALP_POLICY_OUT_TANH)
+    return refuse("a Gaussian policy's out_activation must be SALP_POLICY_OUT_TANH");
+  if (d->n_policies < 1) return refuse("n_policies must be >= 1");
+  if (const int rc = check_n_policies(n_envs, d->n_policies, why)) return rc;
+  int in = obs_dim, w = 0;
+  for (int l = 0; l < d->n_hidden; ++l) { w += d->hidden[l] * in + d->hidden[l]; in = d->hidden[l]; }
+  w += act_dim * in + 3 * act_dim;
+  if (gaussian) w += act_dim * in + act_dim;     // the log-std head
+  if (words) *words = w;
+  return (int)SALP_OK;
+}
+
+// map[k] = the public word that word k of a policy in the device block holds, -1 = zero (the layout above for the block,
+// include/salp_vec.h for the public layout); `d` has passed check_policy_desc.  Returns the stride: every piece is a
+// multiple of 16 words.
+inline int policy_block_map(int obs_dim, int act_dim, const salp_policy_desc_t& d, bool gaussian, std::vector<int32_t>& map) {
+  map.clear();
+  const auto push = [&map](int32_t v) { map.push_back(v); };
+  const int AD = act_dim;
+  int in = obs_dim, pubo = 0;
+  for (int l = 0; l < d.n_hidden; ++l) {
+    const int O = d.hidden[l], Wp = pubo, bp = pubo + O * in;
+    for (int c = 0; c < O / POLICY_CHUNK; ++c) {
+      for (int j = 0; j < POLICY_CHUNK; ++j) push(bp + c * POLICY_CHUNK + j);
+      for (int i = 0; i < in; ++i)
+        for (int j = 0; j < POLICY_CHUNK; ++j) push(Wp + (c * POLICY_CHUNK + j) * in + i);
+    }
+    pubo = bp + O; in = O;
+  }
+  // Gaussian: W_mu, b_mu, W_ls, b_ls, scale, shift in the public layout; the log-std head behind the mean head in the block
+  const int Wl = pubo, bl = pubo + AD * in, W2 = bl + AD, b2 = W2 + AD * in, sc = gaussian ? b2 + AD : bl + AD, sh = sc + AD;
+  for (int k = 0; k < POLICY_TAIL_WORDS; ++k) push(k < AD ? bl + k : (k < 2 * AD ? sc + k - AD : (k < 3 * AD ? sh + k - 2 * AD : -1)));
+  const int rs = (in + POLICY_CHUNK - 1) / POLICY_CHUNK * POLICY_CHUNK;    // 24 -> 32 for the linear policy
+  for (int a = 0; a < AD; ++a)
+    for (int i = 0; i < rs; ++i) push(i < in ? Wl + a * in + i : -1);
+  if (gaussian) {
+    for (int k = 0; k < POLICY_TAIL_WORDS; ++k) push(k < AD ? b2 + k : -1);
+    for (int a = 0; a < AD; ++a)
+      for (int i = 0; i < rs; ++i) push(i < in ? W2 + a * in + i : -1);
+  }
+  return (int)map.size();
+}
+
+// The PH_WORDS header words of a block of d.n_policies policies of `stride` words each, bound to a handle of n_envs envs.
+inline void policy_header(const salp_policy_desc_t& d, int stride, int64_t n_envs, bool gaussian, int32_t (&hd)[PH_WORDS]) {
+  for (int32_t& w : hd) w = 0;     // (noise step: 0)
+  hd[PH_NHIDDEN] = d.n_hidden; hd[PH_H0] = d.hidden[0]; hd[PH_H1] = d.hidden[1]; hd[PH_OUT] = d.out_activation;
+  hd[PH_STRIDE] = stride; hd[PH_COUNT] = d.n_policies; hd[PH_GAUSS] = gaussian ? 1 : 0;
+  hd[PH_GROUP] = d.n_policies > 1 ? (int32_t)(n_envs / d.n_policies) : 0x7FFFFFFF;
+}
+
+// ------------------------------------------------------------------ device side
 #ifdef __HIPCC__
 typedef const float __attribute__((address_space(4))) pol_float;
 typedef const int32_t __attribute__((address_space(4))) pol_int;

@@ -28,7 +28,7 @@
 #include "../../include/salp_robot.h"
 #include "salp_philox.h"   // philox4x32_10, u53
 #include "salp_fp64_math.h"   // sincos_small, sincos_euler, advance_euler_sincos, rcp_nr, sqrt_nr
-#include "salp_host.h"        // fail, HIP_TRY, DeviceScope, check_device_id, StageBuffer, staged()
+#include "salp_host.h"        // fail, HIP_TRY, DeviceScope, check_device_id, CallFrame, launch_1d, StageBuffer, staged()
 
 using namespace salp;
 
@@ -392,7 +392,7 @@ __global__ __launch_bounds__(kRBlock) void salp_robot_math_probe_kernel(int func
 
 }  // namespace
 
-// ---- host side (fail, HIP_TRY, DeviceScope, staged(): salp_host.h) -------------------------------------------------
+// ---- host side (fail, HIP_TRY, CallFrame, launch_1d, staged(): salp_host.h) -------------------------------------------------
 struct salp_robot_vec {
   salp_robot_config_t cfg;
   RobotParams P;
@@ -425,24 +425,20 @@ static const int64_t kScheduleMinEnvs = 32768;
 static int launch_robot_step(salp_robot_vec* h, const float* act, float* obs, float* reward, uint8_t* terminated,
                              uint8_t* truncated, float* final_obs, int32_t* inner_steps, hipStream_t st,
                              const RobotHistory* hist = nullptr) {
-  const unsigned grid = (unsigned)((h->n + kRBlock - 1) / kRBlock);
   const int32_t* order = nullptr;
   if (h->schedule) {
     HIP_TRY(hipMemsetAsync(h->bins, 0, kSchedBins * sizeof(uint32_t), st));
-    const unsigned sgrid = (unsigned)((h->n + kSchedBlock - 1) / kSchedBlock);
-    hipLaunchKernelGGL(robot_schedule_count, dim3(sgrid), dim3(kSchedBlock), 0, st, h->P, act, h->bins);
-    hipLaunchKernelGGL(robot_schedule_scan, dim3(1), dim3(kSchedBins), 0, st, h->bins);
-    hipLaunchKernelGGL(robot_schedule_scatter, dim3(sgrid), dim3(kSchedBlock), 0, st, h->P, act, h->bins, h->order);
+    int rc = launch_1d(robot_schedule_count, h->n, kSchedBlock, st, h->P, act, h->bins);
+    if (rc == SALP_OK) rc = launch_1d(robot_schedule_scan, kSchedBins, kSchedBins, st, h->bins);     // one workgroup
+    if (rc == SALP_OK) rc = launch_1d(robot_schedule_scatter, h->n, kSchedBlock, st, h->P, act, h->bins, h->order);
+    if (rc != SALP_OK) return rc;
     order = h->order;
   }
   if (hist && hist->count > 0)
-    hipLaunchKernelGGL(salp_robot_step_record_kernel, dim3(grid), dim3(kRBlock), 0, st, h->P, h->S, act, obs, reward,
-                       terminated, truncated, final_obs, inner_steps, order, *hist);
-  else
-    hipLaunchKernelGGL(salp_robot_step_kernel, dim3(grid), dim3(kRBlock), 0, st, h->P, h->S, act, obs, reward, terminated,
-                       truncated, final_obs, inner_steps, order);
-  HIP_TRY(hipGetLastError());
-  return 0;
+    return launch_1d(salp_robot_step_record_kernel, h->n, kRBlock, st, h->P, h->S, act, obs, reward, terminated, truncated,
+                     final_obs, inner_steps, order, *hist);
+  return launch_1d(salp_robot_step_kernel, h->n, kRBlock, st, h->P, h->S, act, obs, reward, terminated, truncated, final_obs,
+                   inner_steps, order);
 }
 
 extern "C" {
@@ -523,18 +519,12 @@ int64_t salp_robot_vec_num_envs(const salp_robot_vec_t* h) { return h ? h->n : 0
 
 int salp_robot_vec_reset(salp_robot_vec_t* h, const uint8_t* mask, float* obs, uint32_t flags, void* stream) {
   if (!h) return fail(SALP_ERR_INVALID, "handle is NULL");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  auto launch = [&](const uint8_t* d_mask, float* d_obs) {
-    hipLaunchKernelGGL(salp_robot_reset_kernel, dim3((unsigned)((h->n + kRBlock - 1) / kRBlock)), dim3(kRBlock), 0, st, h->P, h->S,
-                       d_mask, d_obs, 1);
-    HIP_TRY(hipGetLastError());
-    return 0;
-  };
-  if (flags & 1u) return launch(mask, obs);
+  CallFrame f;
+  if (const int rc = f.enter(h, stream)) return rc;
   HostStream s[] = {stream_in(mask, (size_t)h->n), stream_out(obs, (size_t)h->n * 6)};
-  return staged(h->stage, st, s, [&] { return launch(s[0].as<const uint8_t>(), s[1].as<float>()); });
+  return staged(h->stage, f.st, flags & 1u, s, [&] {
+    return launch_1d(salp_robot_reset_kernel, h->n, kRBlock, f.st, h->P, h->S, s[0].as<const uint8_t>(), s[1].as<float>(), 1);
+  });
 }
 
 // salp_robot_vec_step (H == NULL) and salp_robot_vec_step_history (H: the caller's range and pointers, count > 0);
@@ -542,9 +532,11 @@ int salp_robot_vec_reset(salp_robot_vec_t* h, const uint8_t* mask, float* obs, u
 static int robot_step_impl(salp_robot_vec_t* h, const float* act, float* obs, float* reward, uint8_t* terminated,
                            uint8_t* truncated, float* final_obs, int32_t* inner_steps, const RobotHistory* H, uint32_t flags,
                            void* stream) {
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(h->device));
-  hipStream_t st = (hipStream_t)stream;
+  CallFrame f;
+  if (const int rc = f.enter(h, stream)) return rc;
+  hipStream_t st = f.st;
+  // The two forms are kept apart here: with a history the host-pointer form is more than copies around the launch (a
+  // scratch piece for the samples, a second copy once the lengths are known), which staged() does not take on.
   if (flags & 1u) return launch_robot_step(h, act, obs, reward, terminated, truncated, final_obs, inner_steps, st, H);
   // host pointers.  final_obs goes in as well as out: only the rows of ended episodes are written.  The history stays on
   // the device until the lengths are known (they are fetched even when the caller does not want them): it goes back as
@@ -556,7 +548,7 @@ static int robot_step_impl(salp_robot_vec_t* h, const float* act, float* obs, fl
   HostStream s[] = {stream_in(act, n * 3), stream_out(obs, n * 6), stream_out(final_obs, n * 6, true), stream_out(reward, n),
                     stream_out(terminated, n), stream_out(truncated, n), stream_out(inner_steps, n),
                     stream_out(H ? len.data() : nullptr, rows), stream_scratch(rows * row)};
-  const int rc = staged(h->stage, st, s, [&] {
+  const int rc = staged(h->stage, st, false, s, [&] {
     RobotHistory D;
     if (H) { D = *H; D.len = s[7].as<int32_t>(); D.hist = s[8].as<float>(); }
     return launch_robot_step(h, s[0].as<const float>(), s[1].as<float>(), s[3].as<float>(), s[4].as<uint8_t>(), s[5].as<uint8_t>(),
@@ -619,34 +611,27 @@ int salp_robot_vec_trajectory(salp_robot_vec_t* h, const double* params, const d
   if (metrics && !expected) return fail(SALP_ERR_INVALID, "metrics need expected states");
   // the same refusal as the history calls: with such a dt one cycle of the 14.6 s cut exceeds 2^24 Euler steps
   if (h->max_steps < 0) return fail(SALP_ERR_INVALID, "dt is too small (more than 2^24 Euler steps per cycle)");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(h->device));
-  hipStream_t st = (hipStream_t)stream;
+  CallFrame f;
+  if (const int rc = f.enter(h, stream)) return rc;
   const bool per_robot = (flags & SALP_ROBOT_PER_ROBOT_ACTIONS) != 0;
   RobotTrajectory J;
   J.cycles = cycles; J.per_robot = per_robot ? 1 : 0;
-  auto launch = [&](const double* d_par, const double* d_act, const double* d_exp, double* d_st, double* d_met, int32_t* d_in) {
-    J.params = d_par; J.actions = d_act; J.expected = d_exp; J.states = d_st; J.metrics = d_met; J.inner_steps = d_in;
-    hipLaunchKernelGGL(salp_robot_trajectory_kernel, dim3((unsigned)((h->n + kRBlock - 1) / kRBlock)), dim3(kRBlock), 0, st, h->P, J);
-    HIP_TRY(hipGetLastError());
-    return 0;
-  };
-  if (flags & 1u) return launch(params, actions, expected, states, metrics, inner_steps);
   const size_t n = (size_t)h->n, T = (size_t)cycles;
   HostStream s[] = {stream_in(params, (size_t)SALP_RP_COUNT * n), stream_in(actions, T * (per_robot ? n : 1) * 3),
                     stream_in(expected, T * 6), stream_out(states, T * n * 6), stream_out(metrics, n * SALP_RM_COUNT),
                     stream_out(inner_steps, T * n)};
-  return staged(h->stage, st, s, [&] {
-    return launch(s[0].as<const double>(), s[1].as<const double>(), s[2].as<const double>(), s[3].as<double>(), s[4].as<double>(),
-                  s[5].as<int32_t>());
+  return staged(h->stage, f.st, flags & 1u, s, [&] {
+    J.params = s[0].as<const double>(); J.actions = s[1].as<const double>(); J.expected = s[2].as<const double>();
+    J.states = s[3].as<double>(); J.metrics = s[4].as<double>(); J.inner_steps = s[5].as<int32_t>();
+    return launch_1d(salp_robot_trajectory_kernel, h->n, kRBlock, f.st, h->P, J);
   });
 }
 
 int salp_robot_vec_get_state(salp_robot_vec_t* h, double* state, uint32_t flags, void* stream) {
   if (!h || !state) return fail(SALP_ERR_INVALID, "handle / state is NULL");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(h->device));
-  hipStream_t st = (hipStream_t)stream;
+  CallFrame f;
+  if (const int rc = f.enter(h, stream)) return rc;
+  hipStream_t st = f.st;
   // rows are [pitch] on the device and [n] in the snapshot
   HIP_TRY(hipMemcpy2DAsync(state, (size_t)h->n * sizeof(double), h->S.f, (size_t)h->P.pitch * sizeof(double),
                             (size_t)h->n * sizeof(double), SALP_R_COUNT,
@@ -677,11 +662,8 @@ int salp_robot_math_probe(int device_id, int function, const double* in, double*
   HIP_TRY(dev_scope.enter(device_id));
   StageBuffer stage;     // the call's own, released on return
   HostStream s[] = {stream_in(in, rows_in * (size_t)n), stream_out(out, rows_out * (size_t)n)};
-  return staged(stage, nullptr, s, [&] {
-    hipLaunchKernelGGL(salp_robot_math_probe_kernel, dim3((unsigned)((n + kRBlock - 1) / kRBlock)), dim3(kRBlock), 0, nullptr, function,
-                       s[0].as<const double>(), s[1].as<double>(), n, steps);
-    HIP_TRY(hipGetLastError());
-    return 0;
+  return staged(stage, nullptr, false, s, [&] {
+    return launch_1d(salp_robot_math_probe_kernel, n, kRBlock, nullptr, function, s[0].as<const double>(), s[1].as<double>(), n, steps);
   });
 }
 

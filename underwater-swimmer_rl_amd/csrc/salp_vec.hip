@@ -1,147 +1,22 @@
-// salp_vec.hip — the service kernels (reset / observe, state snapshots, generated actions, reseed, policy relayout and
-// noise step) and the C ABI of include/salp_vec.h.  The fused step/rollout kernel is salp_rollout_kernel.h; its
-// instantiations are compiled by the salp_rollout_*.hip units and reached through their rollout_unit_fn functions.
-// The config's defaults and ranges and the launch parameters derived from it (default_config, validate, make_params,
-// is_std) are the host functions of salp_params.h.
+// salp_vec.hip — the C ABI of include/salp_vec.h: host code only.  The service kernels it launches (reset / observe,
+// state snapshots, generated actions, reseed, policy relayout and noise step) are salp_service_kernels.h.  The fused
+// step/rollout kernel is salp_rollout_kernel.h; its instantiations are compiled by the salp_rollout_*.hip units and
+// reached through their rollout_unit_fn functions.  What is decided before a GPU is touched lives in host functions that
+// are under test without one: the config's defaults and ranges, the launch parameters derived from it and the ranges of
+// a snapshot (default_config, validate, make_params, is_std, check_snapshot: salp_params.h); a policy descriptor's ranges,
+// the map from the public weight layout to the device block and the block's header (salp_policy.h).
 #include <new>
 #include <string>
 #include <type_traits>
+#include <vector>
 
 #include "salp_host.h"
 #include "salp_rollout_kernel.h"
+#include "salp_service_kernels.h"
 
-namespace {
+static_assert(POLICY_WAVE == kWave, "salp_policy.h states the wavefront rule with its own constant");
 
-// Device-generated actions (salp_vec_rollout with act == NULL): a[t][env][j] from the env's
-// action stream, Philox counter (env_lo, env_hi, global_step + t, 1 + j).
-__global__ __launch_bounds__(kBlock) void salp_gen_actions_kernel(DevParams P, float* act, int H, int AD, int64_t global_step) {
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= P.n) return;
-  const uint64_t genv = P.env_base + (uint64_t)i;
-  U4 w = {0u, 0u, 0u, 0u}, w2 = {0u, 0u, 0u, 0u};
-  for (int t = 0; t < H; ++t) {
-    const uint32_t ts = (uint32_t)(global_step + t);
-    if (t == 0 || (ts & 3u) == 0u) {
-      w = philox4x32_10((uint32_t)genv, (uint32_t)(genv >> 32), ts >> 2, 1u, P.seed[0], P.seed[1]);
-      if (AD == 2) w2 = philox4x32_10((uint32_t)genv, (uint32_t)(genv >> 32), ts >> 2, 2u, P.seed[0], P.seed[1]);
-    }
-    const uint32_t k = ts & 3u;
-    const uint32_t x0 = (k == 0) ? w.x : (k == 1) ? w.y : (k == 2) ? w.z : w.w;
-    const uint32_t x1 = (k == 0) ? w2.x : (k == 1) ? w2.y : (k == 2) ? w2.z : w2.w;
-    const int64_t o = ((int64_t)t * P.n + i) * AD;
-    if (AD == 1) {
-      act[o] = (float)(x0 >> 8) * 1.1920928955078125e-7f - 1.0f;
-    } else {
-      act[o] = (float)(x0 >> 8) * 5.9604644775390625e-8f;
-      act[o + 1] = (float)(x1 >> 8) * 1.1920928955078125e-7f - 1.0f;
-    }
-  }
-}
-
-// reset(mask) + observation
-template <int FMAX, int KMAX, bool STD>
-__global__ __launch_bounds__(kBlock) void salp_reset_kernel(DevParams P, DevState S, const uint8_t* mask, float* obs, int do_reset) {
-  const int64_t env = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (env >= P.n) return;
-  const uint64_t genv = P.env_base + (uint64_t)env;
-  Env<FMAX> e;
-  load_env(e, S, P, env);
-  const bool resetting = do_reset && (!mask || mask[env]);
-  int todo = 0;
-  if (resetting) {
-    const int nf = reset_pose<FMAX, STD>(e, P, genv, P.F_base);
-    // place_food loops until no lane of the wavefront has food left to place; lanes that are not
-    // being reset pass todo = 0
-    todo = nf;
-  }
-  place_food<FMAX, STD>(e, P, genv, todo, 100);
-  if (resetting) {
-    store_env(e, S, P, env);
-  }
-  if (obs) {
-    const int K = (KMAX == 3) ? 3 : P.K;
-    double a, b;
-    shape_of<STD>(P, e.packed, e.water, a, b);
-    float ob[12 + 4 * KMAX];
-    observe<FMAX, KMAX, STD>(e, P, pymax(a, b), false, 0.f, ob);
-    float4* dst = reinterpret_cast<float4*>(obs + env * (12 + 4 * K));
-#pragma unroll
-    for (int q = 0; q < 3 + KMAX; ++q)
-      if (q < 3 + K) dst[q] = make_float4(ob[4 * q], ob[4 * q + 1], ob[4 * q + 2], ob[4 * q + 3]);
-  }
-}
-
-// public snapshot <-> device layout
-__global__ void salp_get_state_kernel(DevParams P, DevState S, double* f64, int32_t* i32) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= P.n) return;
-  const int64_t p = P.pitch, n = P.n;
-  const uint32_t packed = (uint32_t)S.i[SI_PACKED * p + i];
-  if (f64) {
-    f64[SALP_F_X * n + i] = S.f[SF_X * p + i]; f64[SALP_F_Y * n + i] = S.f[SF_Y * p + i];
-    f64[SALP_F_VX * n + i] = S.f[SF_VX * p + i]; f64[SALP_F_VY * n + i] = S.f[SF_VY * p + i];
-    f64[SALP_F_THETA * n + i] = S.f[SF_TH * p + i]; f64[SALP_F_OMEGA * n + i] = S.f[SF_OM * p + i];
-    f64[SALP_F_NOZZLE * n + i] = S.f[SF_NOZ * p + i];
-    const double water = S.f[SF_WATER * p + i];
-    f64[SALP_F_WATER * n + i] = water;
-    double a, b;
-    shape_of<false>(P, packed, water, a, b);
-    f64[SALP_F_ELLIPSE_A * n + i] = a; f64[SALP_F_ELLIPSE_B * n + i] = b;
-    for (int k = 0; k < 2 * P.F; ++k) f64[(SALP_F_FOOD0 + k) * n + i] = S.f[(SF_FOOD0 + k) * p + i];
-  }
-  if (i32) {
-    i32[SALP_I_PHASE * n + i] = bw_phase(packed); i32[SALP_I_TIMER * n + i] = bw_timer(packed);
-    i32[SALP_I_EXHALE_DUR * n + i] = bw_dur(packed); i32[SALP_I_SHAPE_HOLD * n + i] = bw_hold(packed);
-    i32[SALP_I_STEPS_SINCE_FOOD * n + i] = S.i[SI_SSF * p + i];
-    i32[SALP_I_FOOD_COLLECTED * n + i] = S.i[SI_FC * p + i];
-    i32[SALP_I_RNG_COUNTER * n + i] = S.i[SI_RNG * p + i];
-    i32[SALP_I_EPISODE_LENGTH * n + i] = S.i[SI_EPLEN * p + i];
-  }
-}
-
-__global__ void salp_set_state_kernel(DevParams P, DevState S, const double* f64, const int32_t* i32) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= P.n) return;
-  const int64_t p = P.pitch, n = P.n;
-  if (f64) {
-    S.f[SF_X * p + i] = f64[SALP_F_X * n + i]; S.f[SF_Y * p + i] = f64[SALP_F_Y * n + i];
-    S.f[SF_VX * p + i] = f64[SALP_F_VX * n + i]; S.f[SF_VY * p + i] = f64[SALP_F_VY * n + i];
-    S.f[SF_TH * p + i] = f64[SALP_F_THETA * n + i]; S.f[SF_OM * p + i] = f64[SALP_F_OMEGA * n + i];
-    S.f[SF_NOZ * p + i] = f64[SALP_F_NOZZLE * n + i]; S.f[SF_WATER * p + i] = f64[SALP_F_WATER * n + i];
-    for (int k = 0; k < P.F; ++k) {
-      double fx = f64[(SALP_F_FOOD0 + k) * n + i], fy = f64[(SALP_F_FOOD0 + P.F + k) * n + i];
-      if (fx != fx || fy != fy) { fx = __builtin_nan(""); fy = __builtin_nan(""); }
-      S.f[(SF_FOOD0 + k) * p + i] = fx; S.f[(SF_FOOD0 + P.F + k) * p + i] = fy;
-    }
-  }
-  if (i32) {
-    S.i[SI_PACKED * p + i] = (int32_t)pack_breath(i32[SALP_I_PHASE * n + i], i32[SALP_I_TIMER * n + i],
-                                                  i32[SALP_I_EXHALE_DUR * n + i], i32[SALP_I_SHAPE_HOLD * n + i]);
-    S.i[SI_SSF * p + i] = i32[SALP_I_STEPS_SINCE_FOOD * n + i];
-    S.i[SI_FC * p + i] = i32[SALP_I_FOOD_COLLECTED * n + i];
-    S.i[SI_RNG * p + i] = i32[SALP_I_RNG_COUNTER * n + i];
-    S.i[SI_EPLEN * p + i] = i32[SALP_I_EPISODE_LENGTH * n + i];
-  }
-}
-
-// salp_vec_reseed: the state a freshly created handle has before its initial reset (every row zero, draw counters
-// included), the new key words, cleared statistics.  The reset kernel that follows on the same stream reads the new key.
-__global__ __launch_bounds__(kBlock) void salp_reseed_kernel(ColdBlock* cold, DevStats* stats, int64_t pitch, int nf_rows,
-                                                            uint32_t seed_lo, uint32_t seed_hi) {
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i < pitch) {
-    double* f = cold->S.f;
-    int32_t* w = cold->S.i;
-    for (int r = 0; r < nf_rows; ++r) f[(int64_t)r * pitch + i] = 0.0;
-    for (int r = 0; r < SI_COUNT; ++r) w[(int64_t)r * pitch + i] = 0;
-  }
-  if (i == 0) { cold->seed[0] = seed_lo; cold->seed[1] = seed_hi; }
-  if (i < (int64_t)SALP_STATS_REPLICAS * 16) stats[i / 16].v[i % 16] = 0ull;
-}
-
-}  // namespace
-
-// ------------------------------------------------------------------ host side (fail, HIP_TRY, DeviceScope, staged(): salp_host.h)
+// ------------------------------------------------------------------ host side (fail, HIP_TRY, CallFrame, launch_1d, staged(): salp_host.h)
 struct salp_vec {
   salp_config_t cfg;
   DevParams P;
@@ -189,6 +64,14 @@ int validate(const salp_config_t* c) {
   return rc == SALP_OK ? rc : fail(rc, why);
 }
 
+// The descriptor's ranges for this handle: salp_policy.h (likewise).  On success *words = public words of one policy.
+int check_policy_desc(const salp_vec* h, const salp_policy_desc_t* d, int* words, bool gaussian) {
+  const char* why = "";
+  const int rc = h ? salp::check_policy_desc(h->obs_dim, h->act_dim, h->kmax, h->n, d, gaussian, words, &why)
+                   : salp::check_policy_desc(0, 0, 0, 0, nullptr, gaussian, words, &why);     // one refusal, one text, for either NULL
+  return rc == SALP_OK ? rc : fail(rc, why);
+}
+
 typedef void (*reset_fn)(DevParams, DevState, const uint8_t*, float*, int);
 
 // True when in-kernel action generation is available for this handle and output signature.
@@ -220,8 +103,6 @@ reset_fn reset_kernel_for(const salp_vec* h) {
   if (h->kmax == 3) return h->std_consts ? reset_kernel_k3<true>(h) : reset_kernel_k3<false>(h);
   return (reset_fn)salp_reset_kernel<16, 8, false>;
 }
-
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }   // workgroups of kBlock threads
 
 // The part of IOPtrs that every rollout call fills in the same way; the rest starts out NULL.
 IOPtrs io_for(const salp_vec* h) {
@@ -288,65 +169,11 @@ int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, Rollout
   g_read_counters = first.read_counters;
 #endif
   if (n_full > 0) {
-    hipLaunchKernelGGL((rollout_fn)full.fn, dim3(blocks_for(n_full)), dim3(kBlock), 0, st, h->P, h->S, io, H,
-                       (int64_t)0, n_full, (const ColdBlock*)h->cold);
-    HIP_TRY(hipGetLastError());
+    const int rc = launch_1d((rollout_fn)full.fn, n_full, kBlock, st, h->P, h->S, io, H, (int64_t)0, n_full, (const ColdBlock*)h->cold);
+    if (rc != SALP_OK) return rc;
   }
-  if (n_full < h->n) {                              // the last n % 64 envs (or the whole small batch): predicated stores
-    hipLaunchKernelGGL((rollout_fn)ragged.fn, dim3(blocks_for(h->n - n_full)), dim3(kBlock), 0, st, h->P, h->S, io, H,
-                       n_full, h->n, (const ColdBlock*)h->cold);
-    HIP_TRY(hipGetLastError());
-  }
-  return SALP_OK;
-}
-
-// public layout -> device block of P policies (salp_policy.h): one thread per word of the block
-__global__ __launch_bounds__(kBlock) void salp_policy_relayout_kernel(float* __restrict__ block, const float* __restrict__ pub,
-                                                                      const int32_t* __restrict__ map, int stride, int words, int64_t total) {
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= total) return;
-  const int64_t p = i / stride;
-  const int m = map[i - p * stride];
-  block[PH_WORDS + i] = m >= 0 ? pub[p * words + m] : 0.f;
-}
-
-// The policy's noise step (header words PH_NOISE, PH_NOISE + 1 of its device block): one thread, behind the launches that read it
-__global__ void salp_policy_noise_kernel(float* block, uint64_t add, uint64_t set, int do_set) {
-  uint32_t* const w = reinterpret_cast<uint32_t*>(block) + PH_NOISE;
-  const uint64_t v = do_set ? set : ((((uint64_t)w[1] << 32) | w[0]) + add);
-  w[0] = (uint32_t)v;
-  w[1] = (uint32_t)(v >> 32);
-}
-
-// A wavefront never mixes policies: P policies share the envs in equal runs of whole wavefronts.
-int check_n_policies(const salp_vec* h, int P) {
-  if (P > 1 && (h->n % P != 0 || (h->n / P) % kWave != 0))
-    return fail(SALP_ERR_INVALID, "n_policies > 1 needs n_envs % P == 0 and (n_envs / P) % 64 == 0");
-  return SALP_OK;
-}
-
-// The descriptor's ranges (include/salp_vec.h).  On success *words = public words of one policy.
-int check_policy_desc(const salp_vec* h, const salp_policy_desc_t* d, int* words, bool gaussian = false) {
-  if (!h || !d) return fail(SALP_ERR_INVALID, "handle/desc is NULL");
-  if (d->struct_size != sizeof(salp_policy_desc_t)) return fail(SALP_ERR_INVALID, "salp_policy_desc_t.struct_size mismatch");
-  if (h->kmax != 3) return fail(SALP_ERR_INVALID, "policies need a handle with max_observed_food == 3");
-  if (d->n_hidden < 0 || d->n_hidden > 2) return fail(SALP_ERR_INVALID, "n_hidden must be 0, 1 or 2");
-  for (int l = 0; l < 2; ++l) {
-    const int w = d->hidden[l];
-    if (l < d->n_hidden ? (w < POLICY_CHUNK || w > POLICY_MAX_HIDDEN || w % POLICY_CHUNK) : (w != 0))
-      return fail(SALP_ERR_INVALID, "hidden widths must be multiples of 16 in [16, 64] (unused entries 0)");
-  }
-  if (d->out_activation != SALP_POLICY_OUT_TANH && d->out_activation != SALP_POLICY_OUT_CLIP)
-    return fail(SALP_ERR_INVALID, "out_activation must be SALP_POLICY_OUT_TANH or SALP_POLICY_OUT_CLIP");
-  if (gaussian && d->out_activation != SALP_POLICY_OUT_TANH)
-    return fail(SALP_ERR_INVALID, "a Gaussian policy's out_activation must be SALP_POLICY_OUT_TANH");
-  if (d->n_policies < 1) return fail(SALP_ERR_INVALID, "n_policies must be >= 1");
-  if (const int rc = check_n_policies(h, d->n_policies)) return rc;
-  int in = h->obs_dim, w = 0;
-  for (int l = 0; l < d->n_hidden; ++l) { w += d->hidden[l] * in + d->hidden[l]; in = d->hidden[l]; }
-  w += h->act_dim * in + 3 * h->act_dim;
-  if (gaussian) w += h->act_dim * in + h->act_dim;     // the log-std head
-  if (words) *words = w;
+  if (n_full < h->n)                                // the last n % 64 envs (or the whole small batch): predicated stores
+    return launch_1d((rollout_fn)ragged.fn, h->n - n_full, kBlock, st, h->P, h->S, io, H, n_full, h->n, (const ColdBlock*)h->cold);
   return SALP_OK;
 }
 
@@ -359,12 +186,21 @@ int policy_upload(salp_policy* pol, const float* weights, uint32_t flags, hipStr
     src = pol->pub;
   }
   const int64_t total = (int64_t)pol->d.n_policies * pol->stride;
-  hipLaunchKernelGGL(salp_policy_relayout_kernel, dim3(blocks_for(total)), dim3(kBlock), 0, st,
-                     pol->block, src, (const int32_t*)pol->map, pol->stride, pol->words, total);
-  HIP_TRY(hipGetLastError());
+  const int rc = launch_1d(salp_policy_relayout_kernel, total, kBlock, st, pol->block, src, (const int32_t*)pol->map, pol->stride,
+                           pol->words, total);
+  if (rc != SALP_OK) return rc;
   if (!(flags & SALP_DEVICE_PTRS)) HIP_TRY(hipStreamSynchronize(st));
   return SALP_OK;
 }
+
+// What the record calls (packed, summary, navigation) check of `flags` and of a device `rec`: no bit outside `allowed`,
+// and 16-byte alignment, as the kernels write a record in 16-byte stores.
+int check_record_args(uint32_t flags, uint32_t allowed, const char* bits_msg, const void* rec, const char* align_msg) {
+  if (flags & ~allowed) return fail(SALP_ERR_INVALID, bits_msg);
+  if ((flags & SALP_DEVICE_PTRS) && ((uintptr_t)rec & 15u)) return fail(SALP_ERR_INVALID, align_msg);
+  return SALP_OK;
+}
+const char* const kEvalFlagBits = "unknown flag bits (SALP_DEVICE_PTRS and SALP_EVAL_ACCUMULATE are defined)";
 
 }  // namespace
 
@@ -413,35 +249,34 @@ int salp_vec_create(const salp_config_t* cfg, int64_t n_envs, int device_id, uin
   h->nf_rows = (size_t)(SF_FOOD0 + 2 * h->F);
   h->stats_enabled = 1;
 
-  hipError_t e1 = hipMalloc((void**)&h->S.f, h->nf_rows * (size_t)pitch * sizeof(double));
-  hipError_t e2 = (e1 == hipSuccess) ? hipMalloc((void**)&h->S.i, (size_t)SI_COUNT * (size_t)pitch * sizeof(int32_t)) : e1;
-  hipError_t e3 = (e2 == hipSuccess) ? hipMalloc((void**)&h->stats, SALP_STATS_REPLICAS * sizeof(DevStats)) : e2;
-  if (e3 != hipSuccess) {
-    std::string m = std::string("hipMalloc(state): ") + hipGetErrorString(e3);
-    salp_vec_destroy(h);
-    return fail(e3 == hipErrorOutOfMemory ? SALP_ERR_OOM : SALP_ERR_HIP, m);
+  // allocations, the cold block's copy and the memsets as one chain: `stage` names the step that failed
+  const size_t f_bytes = h->nf_rows * (size_t)pitch * sizeof(double), i_bytes = (size_t)SI_COUNT * (size_t)pitch * sizeof(int32_t);
+  const char* stage = "hipMalloc(state): ";
+  hipError_t e = hipMalloc((void**)&h->S.f, f_bytes);
+  if (e == hipSuccess) e = hipMalloc((void**)&h->S.i, i_bytes);
+  if (e == hipSuccess) e = hipMalloc((void**)&h->stats, SALP_STATS_REPLICAS * sizeof(DevStats));
+  if (e == hipSuccess) {
+    stage = "hipMalloc/hipMemcpy(cold block): ";
+    e = hipMalloc((void**)&h->cold, sizeof(ColdBlock));
   }
-  hipError_t e4 = hipMalloc((void**)&h->cold, sizeof(ColdBlock));
-  if (e4 == hipSuccess) {
+  if (e == hipSuccess) {
     h->P.seed = (seed_word_t*)(uintptr_t)h->cold->seed;   // device address; the kernels read the key words through it
     h->P.self = (dev_params_c*)(uintptr_t)&h->cold->P;    // likewise the constants of the STD = false kernels
     ColdBlock cb;
     cb.P = h->P; cb.S = h->S;
     cb.seed[0] = (uint32_t)seed; cb.seed[1] = (uint32_t)(seed >> 32);
-    e4 = hipMemcpy(h->cold, &cb, sizeof(cb), hipMemcpyHostToDevice);
+    e = hipMemcpy(h->cold, &cb, sizeof(cb), hipMemcpyHostToDevice);
   }
-  if (e4 != hipSuccess) {
-    std::string m = std::string("hipMalloc/hipMemcpy(cold block): ") + hipGetErrorString(e4);
-    salp_vec_destroy(h);
-    return fail(e4 == hipErrorOutOfMemory ? SALP_ERR_OOM : SALP_ERR_HIP, m);
+  if (e == hipSuccess) {
+    stage = "hipMemset(state): ";
+    e = hipMemset(h->S.f, 0, f_bytes);
   }
-  hipError_t e = hipMemset(h->S.f, 0, h->nf_rows * (size_t)pitch * sizeof(double));
-  if (e == hipSuccess) e = hipMemset(h->S.i, 0, (size_t)SI_COUNT * (size_t)pitch * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMemset(h->S.i, 0, i_bytes);
   if (e == hipSuccess) e = hipMemset(h->stats, 0, SALP_STATS_REPLICAS * sizeof(DevStats));
   if (e != hipSuccess) {
-    std::string m = std::string("hipMemset(state): ") + hipGetErrorString(e);
+    const std::string m = std::string(stage) + hipGetErrorString(e);
     salp_vec_destroy(h);
-    return fail(SALP_ERR_HIP, m);
+    return fail(e == hipErrorOutOfMemory ? SALP_ERR_OOM : SALP_ERR_HIP, m);
   }
   // initial reset of every env (consumes the first draws of each env's stream)
   rc = salp_vec_reset(h, nullptr, nullptr, SALP_DEVICE_PTRS, nullptr);
@@ -513,38 +348,24 @@ int salp_vec_set_base_num_food(salp_vec_t* h, int32_t k) {
 }
 int32_t salp_vec_base_num_food(const salp_vec_t* h) { return h ? h->P.F_base : 0; }
 
+// reset (do_reset = 1, every env or those of `mask`) and observe (do_reset = 0): one kernel
+static int reset_impl(salp_vec_t* h, const uint8_t* mask, float* obs, int do_reset, uint32_t flags, void* stream) {
+  CallFrame f;
+  if (const int rc = f.enter(h, stream)) return rc;
+  HostStream s[] = {stream_out(obs, (size_t)h->n * h->obs_dim), stream_in(mask, (size_t)h->n)};
+  return staged(h->stage, f.st, flags & SALP_DEVICE_PTRS, s, [&] {
+    return launch_1d(reset_kernel_for(h), h->n, kBlock, f.st, h->P, h->S, s[1].as<const uint8_t>(), s[0].as<float>(), do_reset);
+  });
+}
+
 int salp_vec_reset(salp_vec_t* h, const uint8_t* mask, float* obs, uint32_t flags, void* stream) {
   if (!h) return fail(SALP_ERR_INVALID, "handle is NULL");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  h->last_stream = st;
-  const reset_fn fn = reset_kernel_for(h);
-  auto launch = [&](const uint8_t* d_mask, float* d_obs) {
-    hipLaunchKernelGGL(fn, dim3(blocks_for(h->n)), dim3(kBlock), 0, st, h->P, h->S, d_mask, d_obs, 1);
-    HIP_TRY(hipGetLastError());
-    return (int)SALP_OK;
-  };
-  if (flags & SALP_DEVICE_PTRS) return launch(mask, obs);
-  HostStream s[] = {stream_out(obs, (size_t)h->n * h->obs_dim), stream_in(mask, (size_t)h->n)};
-  return staged(h->stage, st, s, [&] { return launch(s[1].as<const uint8_t>(), s[0].as<float>()); });
+  return reset_impl(h, mask, obs, 1, flags, stream);
 }
 
 int salp_vec_observe(salp_vec_t* h, float* obs, uint32_t flags, void* stream) {
   if (!h || !obs) return fail(SALP_ERR_INVALID, "handle/obs is NULL");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  h->last_stream = st;
-  const reset_fn fn = reset_kernel_for(h);
-  auto launch = [&](float* d_obs) {
-    hipLaunchKernelGGL(fn, dim3(blocks_for(h->n)), dim3(kBlock), 0, st, h->P, h->S, (const uint8_t*)nullptr, d_obs, 0);
-    HIP_TRY(hipGetLastError());
-    return (int)SALP_OK;
-  };
-  if (flags & SALP_DEVICE_PTRS) return launch(obs);
-  HostStream s[] = {stream_out(obs, (size_t)h->n * h->obs_dim)};
-  return staged(h->stage, st, s, [&] { return launch(s[0].as<float>()); });
+  return reset_impl(h, nullptr, obs, 0, flags, stream);
 }
 
 // Behind the launches of a sampled call: the policy's noise step goes on by the call's horizon, on the device (a replayed
@@ -554,9 +375,7 @@ int salp_vec_observe(salp_vec_t* h, float* obs, uint32_t flags, void* stream) {
 // but the noise step where it was — the caller must set it (salp_policy_set_noise_step) before sampling on.
 static int advance_noise(const salp_policy_t* pol, int H, hipStream_t st) {
   pol->last_stream = st;
-  hipLaunchKernelGGL(salp_policy_noise_kernel, dim3(1), dim3(1), 0, st, pol->block, (uint64_t)H, (uint64_t)0, 0);
-  HIP_TRY(hipGetLastError());
-  return SALP_OK;
+  return launch_1d(salp_policy_noise_kernel, 1, 1, st, pol->block, (uint64_t)H, (uint64_t)0, 0);
 }
 
 // Device-generated actions of the next H steps into act_out when given, else into the handle's own buffer (grown on demand).
@@ -571,10 +390,8 @@ static int generate_actions(salp_vec_t* h, int32_t H, float* act_out, hipStream_
     }
     dst = h->act_buf;
   }
-  hipLaunchKernelGGL(salp_gen_actions_kernel, dim3(blocks_for(h->n)), dim3(kBlock), 0, st, h->P, dst, (int)H, h->act_dim, (int64_t)h->global_step);
-  HIP_TRY(hipGetLastError());
   *act = dst;
-  return SALP_OK;
+  return launch_1d(salp_gen_actions_kernel, h->n, kBlock, st, h->P, dst, (int)H, h->act_dim, (int64_t)h->global_step);
 }
 
 // The launches of a rollout call and what follows them when they succeed: the global step goes on by the horizon and, for
@@ -591,36 +408,37 @@ static int rollout_impl(salp_vec_t* h, const float* act, int32_t H, float* obs, 
                         float* act_out, uint32_t flags, void* stream) {
   if (!h) return fail(SALP_ERR_INVALID, "handle is NULL");
   if (H <= 0) return fail(SALP_ERR_INVALID, "horizon must be >= 1");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  h->last_stream = st;
+  CallFrame f;
+  if (const int rc = f.enter(h, stream)) return rc;
+  const bool device_ptrs = (flags & SALP_DEVICE_PTRS) != 0;
   IOPtrs io = io_for(h);
-  if (flags & SALP_DEVICE_PTRS) {
-    io.act = act; io.obs = obs; io.reward = reward; io.terminated = terminated; io.truncated = truncated;
-    io.final_obs = final_obs; io.info = info; io.act_out = act_out;
-    const bool full_sig = obs && reward && terminated && truncated && !final_obs && !info;
-    if (!act && !can_generate_in_kernel(h, full_sig)) {
-      int rc = generate_actions(h, H, act_out, st, &io.act);
-      if (rc != SALP_OK) return rc;
-    }
-    return run_rollout(h, io, H, st, {kOutStreams, ACT_READ});
-  }
-  // host pointers: the actions are always generated ahead of the launch when none are given (never in the kernel), into
-  // act_out's staging when that is wanted; final_obs goes in as well as out (the rows of unfinished envs stay as they are)
+  // final_obs goes in as well as out (the rows of unfinished envs stay as they are)
   const size_t HN = (size_t)H * (size_t)h->n;
   HostStream s[] = {act ? stream_in(act, HN * h->act_dim) : stream_out(act_out, HN * h->act_dim),
                     stream_out(obs, HN * h->obs_dim), stream_out(final_obs, HN * h->obs_dim, true), stream_out(reward, HN),
                     stream_out(terminated, HN), stream_out(truncated, HN), stream_out(info, HN * SALP_INFO_COLS)};
-  return staged(h->stage, st, s, [&] {
-    io.act = s[0].as<float>();
-    if (!act) {
-      int rc = generate_actions(h, H, s[0].as<float>(), st, &io.act);
-      if (rc != SALP_OK) return rc;
-    }
+  return staged(h->stage, f.st, device_ptrs, s, [&] {
     io.obs = s[1].as<float>(); io.final_obs = s[2].as<float>(); io.reward = s[3].as<float>();
     io.terminated = s[4].as<uint8_t>(); io.truncated = s[5].as<uint8_t>(); io.info = s[6].as<int32_t>();
-    return run_rollout(h, io, H, st, {kOutStreams, ACT_READ});
+    // The actions are where the two forms differ.  Device pointers: act and act_out are two arrays (the kernel writes the
+    // actions it took to act_out), and with no act the actions are generated in the kernel where such a kernel exists.
+    // Host pointers: with no act they are always generated ahead of the launch (never in the kernel), into act_out's
+    // staging when that is wanted, and the kernel has no act_out.
+    if (device_ptrs) {
+      io.act = act; io.act_out = act_out;
+      const bool full_sig = io.obs && io.reward && io.terminated && io.truncated && !io.final_obs && !io.info;
+      if (!act && !can_generate_in_kernel(h, full_sig)) {
+        const int rc = generate_actions(h, H, act_out, f.st, &io.act);
+        if (rc != SALP_OK) return rc;
+      }
+    } else {
+      io.act = s[0].as<float>();
+      if (!act) {
+        const int rc = generate_actions(h, H, s[0].as<float>(), f.st, &io.act);
+        if (rc != SALP_OK) return rc;
+      }
+    }
+    return run_rollout(h, io, H, f.st, {kOutStreams, ACT_READ});
   });
 }
 
@@ -646,29 +464,26 @@ static int packed_impl(salp_vec_t* h, const float* act, int32_t H, float* rec, f
   if (!h) return fail(SALP_ERR_INVALID, "handle is NULL");
   if (!rec) return fail(SALP_ERR_INVALID, "rec is NULL");
   if (H <= 0) return fail(SALP_ERR_INVALID, "horizon must be >= 1");
-  if (flags & ~(uint32_t)(SALP_DEVICE_PTRS | SALP_REC_FINAL_OBS))
-    return fail(SALP_ERR_INVALID, "unknown flag bits (SALP_DEVICE_PTRS and SALP_REC_FINAL_OBS are defined)");
-  if ((flags & SALP_DEVICE_PTRS) && ((uintptr_t)rec & 15u))
-    return fail(SALP_ERR_INVALID, "rec must be 16-byte aligned (the records are written as float4)");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  h->last_stream = st;
+  if (const int rc = check_record_args(flags, SALP_DEVICE_PTRS | SALP_REC_FINAL_OBS,
+                                       "unknown flag bits (SALP_DEVICE_PTRS and SALP_REC_FINAL_OBS are defined)", rec,
+                                       "rec must be 16-byte aligned (the records are written as float4)"))
+    return rc;
+  CallFrame f;
+  if (const int rc = f.enter(h, stream)) return rc;
   const bool with_final = (flags & SALP_REC_FINAL_OBS) != 0;
   IOPtrs io = io_for(h);
-  auto launch = [&](const float* d_act, float* d_gen, float* d_rec) {   // d_gen: where generated actions go (NULL: the handle's buffer)
-    io.act = d_act; set_record_block(io, d_rec, with_final);
-    if (!act) {
-      int rc = generate_actions(h, H, d_gen, st, &io.act);
-      if (rc != SALP_OK) return rc;
-    }
-    return run_rollout(h, io, H, st, {kOutPacked, ACT_READ});
-  };
-  if (flags & SALP_DEVICE_PTRS) return launch(act, act_out, rec);
+  // s[0]: the actions, or — none given — where generated ones go (act_out; NULL: the handle's buffer)
   const size_t HN = (size_t)H * (size_t)h->n;
   HostStream s[] = {act ? stream_in(act, HN * h->act_dim) : stream_out(act_out, HN * h->act_dim),
                     stream_out(rec, HN * (size_t)salp_vec_record_width(h, flags), with_final)};   // in: the tails of unfinished rows stay as they are
-  return staged(h->stage, st, s, [&] { return launch(s[0].as<float>(), s[0].as<float>(), s[1].as<float>()); });
+  return staged(h->stage, f.st, flags & SALP_DEVICE_PTRS, s, [&] {
+    io.act = s[0].as<float>(); set_record_block(io, s[1].as<float>(), with_final);
+    if (!act) {
+      const int rc = generate_actions(h, H, s[0].as<float>(), f.st, &io.act);
+      if (rc != SALP_OK) return rc;
+    }
+    return run_rollout(h, io, H, f.st, {kOutPacked, ACT_READ});
+  });
 }
 
 int salp_vec_step_packed(salp_vec_t* h, const float* act, float* rec, uint32_t flags, void* stream) {
@@ -683,7 +498,7 @@ int salp_vec_rollout_packed(salp_vec_t* h, const float* act, int32_t horizon, fl
 
 int salp_policy_words(const salp_vec_t* h, const salp_policy_desc_t* desc) {
   int words = 0;
-  const int rc = check_policy_desc(h, desc, &words);
+  const int rc = check_policy_desc(h, desc, &words, false);
   return rc != SALP_OK ? rc : words;
 }
 
@@ -714,46 +529,17 @@ static int policy_create_impl(salp_vec_t* h, const salp_policy_desc_t* desc, con
   memset(pol, 0, sizeof(*pol));
   pol->h = h; pol->d = *desc; pol->device = h->device; pol->obs_dim = h->obs_dim; pol->act_dim = h->act_dim; pol->n = h->n;
   pol->words = words; pol->gaussian = gaussian ? 1 : 0;
-  // word k of a policy in the device block <- public word map[k] (salp_policy.h for the block, salp_vec.h for the public layout)
-  const int AD = h->act_dim, nh = desc->n_hidden;
-  std::string mapbuf;      // int32 entries
-  auto push = [&](int32_t v) { mapbuf.append(reinterpret_cast<const char*>(&v), sizeof(v)); };
-  int in = h->obs_dim, pubo = 0;
-  for (int l = 0; l < nh; ++l) {
-    const int O = desc->hidden[l], Wp = pubo, bp = pubo + O * in;
-    for (int c = 0; c < O / POLICY_CHUNK; ++c) {
-      for (int j = 0; j < POLICY_CHUNK; ++j) push(bp + c * POLICY_CHUNK + j);
-      for (int i = 0; i < in; ++i)
-        for (int j = 0; j < POLICY_CHUNK; ++j) push(Wp + (c * POLICY_CHUNK + j) * in + i);
-    }
-    pubo = bp + O; in = O;
-  }
-  {
-    // Gaussian: W_mu, b_mu, W_ls, b_ls, scale, shift in the public layout; the log-std head behind the mean head in the block
-    const int Wl = pubo, bl = pubo + AD * in, W2 = bl + AD, b2 = W2 + AD * in, sc = gaussian ? b2 + AD : bl + AD, sh = sc + AD;
-    for (int k = 0; k < POLICY_TAIL_WORDS; ++k) push(k < AD ? bl + k : (k < 2 * AD ? sc + k - AD : (k < 3 * AD ? sh + k - 2 * AD : -1)));
-    const int rs = (in + POLICY_CHUNK - 1) / POLICY_CHUNK * POLICY_CHUNK;    // 24 -> 32 for the linear policy
-    for (int a = 0; a < AD; ++a)
-      for (int i = 0; i < rs; ++i) push(i < in ? Wl + a * in + i : -1);
-    if (gaussian) {
-      for (int k = 0; k < POLICY_TAIL_WORDS; ++k) push(k < AD ? b2 + k : -1);
-      for (int a = 0; a < AD; ++a)
-        for (int i = 0; i < rs; ++i) push(i < in ? W2 + a * in + i : -1);
-    }
-  }
-  pol->stride = (int)(mapbuf.size() / sizeof(int32_t));     // every piece above is a multiple of 16 words
+  std::vector<int32_t> map;     // word k of a policy in the device block <- public word map[k]: salp_policy.h
+  pol->stride = policy_block_map(h->obs_dim, h->act_dim, *desc, gaussian, map);
   const size_t block_b = ((size_t)PH_WORDS + (size_t)desc->n_policies * pol->stride) * sizeof(float);
-  const size_t pub_b = (size_t)desc->n_policies * words * sizeof(float);
+  const size_t pub_b = (size_t)desc->n_policies * words * sizeof(float), map_b = map.size() * sizeof(int32_t);
   hipError_t e = hipMalloc((void**)&pol->block, block_b);
   if (e == hipSuccess) e = hipMalloc((void**)&pol->pub, pub_b);
-  if (e == hipSuccess) e = hipMalloc((void**)&pol->map, mapbuf.size());
-  if (e == hipSuccess) e = hipMemcpy(pol->map, mapbuf.data(), mapbuf.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMalloc((void**)&pol->map, map_b);
+  if (e == hipSuccess) e = hipMemcpy(pol->map, map.data(), map_b, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     int32_t hd[PH_WORDS];
-    memset(hd, 0, sizeof(hd));
-    hd[PH_NHIDDEN] = nh; hd[PH_H0] = desc->hidden[0]; hd[PH_H1] = desc->hidden[1]; hd[PH_OUT] = desc->out_activation;
-    hd[PH_STRIDE] = pol->stride; hd[PH_COUNT] = desc->n_policies; hd[PH_GAUSS] = pol->gaussian;   // (noise step: 0)
-    hd[PH_GROUP] = desc->n_policies > 1 ? (int32_t)(h->n / desc->n_policies) : 0x7FFFFFFF;
+    policy_header(*desc, pol->stride, h->n, gaussian, hd);
     e = hipMemcpy(pol->block, hd, sizeof(hd), hipMemcpyHostToDevice);
   }
   if (e != hipSuccess) {
@@ -789,9 +575,7 @@ int salp_policy_set_noise_step(salp_policy_t* pol, uint64_t n, void* stream) {
   DeviceScope dev_scope;
   HIP_TRY(dev_scope.enter(pol->device));
   pol->last_stream = (hipStream_t)stream;
-  hipLaunchKernelGGL(salp_policy_noise_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pol->block, (uint64_t)0, n, 1);
-  HIP_TRY(hipGetLastError());
-  return SALP_OK;
+  return launch_1d(salp_policy_noise_kernel, 1, 1, (hipStream_t)stream, pol->block, (uint64_t)0, n, 1);
 }
 
 int salp_policy_noise_step(salp_policy_t* pol, uint64_t* n) {
@@ -813,15 +597,15 @@ int salp_policy_update(salp_policy_t* pol, const float* weights, uint32_t flags,
   return policy_upload(pol, weights, flags, (hipStream_t)stream);
 }
 
-// What every call that runs a policy checks first.  (The n_policies test cannot fail once the policy is known to be the
-// handle's: it passed at create with the same n_envs.  It is kept as the guard of the kernels' one-policy-per-wavefront rule.)
+// What every call that runs a policy checks first.  (The descriptor cannot fail once the policy is known to be the handle's:
+// it passed at create with the same handle.  Its check is kept as the guard of the kernels' K = 3 and one-policy-per-wavefront
+// rules.)
 static int check_policy_call(const salp_vec_t* h, const salp_policy_t* pol, bool sampled) {
   if (!h || !pol) return fail(SALP_ERR_INVALID, "handle/policy is NULL");
   if (sampled && !pol->gaussian) return fail(SALP_ERR_INVALID, "sampling needs a Gaussian policy (salp_policy_create_gaussian)");
   if (pol->h != h || pol->device != h->device || pol->obs_dim != h->obs_dim || pol->act_dim != h->act_dim || pol->n != h->n)
     return fail(SALP_ERR_INVALID, "the policy belongs to another handle (or other dimensions)");
-  if (h->kmax != 3) return fail(SALP_ERR_INVALID, "policies need a handle with max_observed_food == 3");
-  return check_n_policies(h, pol->d.n_policies);
+  return check_policy_desc(h, &pol->d, nullptr, pol->gaussian != 0);
 }
 
 // salp_vec_rollout_policy (sampled = false, logp_out = NULL) and salp_vec_rollout_policy_sampled
@@ -832,23 +616,18 @@ static int rollout_policy_impl(salp_vec_t* h, const salp_policy_t* pol, int32_t 
   if (H <= 0) return fail(SALP_ERR_INVALID, "horizon must be >= 1");
   if (!obs || !reward || !terminated || !truncated)
     return fail(SALP_ERR_INVALID, "obs, reward, terminated and truncated are all required");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  h->last_stream = st;
+  CallFrame f;
+  if ((rc = f.enter(h, stream)) != SALP_OK) return rc;
   IOPtrs io = io_for(h);
   set_policy_block(io, pol->block);
-  auto launch = [&](float* d_obs, float* d_rew, uint8_t* d_term, uint8_t* d_trunc, float* d_aout, float* d_logp) {
-    io.obs = d_obs; io.reward = d_rew; io.terminated = d_term; io.truncated = d_trunc; io.act_out = d_aout;
-    if (sampled) io.logp_out = d_logp;
-    return run_rollout(h, io, H, st, {kOutStreams, sampled ? ACT_POLICY_SAMPLED : ACT_POLICY}, pol);
-  };
-  if (flags & SALP_DEVICE_PTRS) return launch(obs, reward, terminated, truncated, act_out, logp_out);
   const size_t HN = (size_t)H * (size_t)h->n;
   HostStream s[] = {stream_out(obs, HN * h->obs_dim), stream_out(reward, HN), stream_out(terminated, HN), stream_out(truncated, HN),
                     stream_out(act_out, HN * h->act_dim), stream_out(sampled ? logp_out : nullptr, HN)};
-  return staged(h->stage, st, s, [&] {
-    return launch(s[0].as<float>(), s[1].as<float>(), s[2].as<uint8_t>(), s[3].as<uint8_t>(), s[4].as<float>(), s[5].as<float>());
+  return staged(h->stage, f.st, flags & SALP_DEVICE_PTRS, s, [&] {
+    io.obs = s[0].as<float>(); io.reward = s[1].as<float>(); io.terminated = s[2].as<uint8_t>(); io.truncated = s[3].as<uint8_t>();
+    io.act_out = s[4].as<float>();
+    if (sampled) io.logp_out = s[5].as<float>();
+    return run_rollout(h, io, H, f.st, {kOutStreams, sampled ? ACT_POLICY_SAMPLED : ACT_POLICY}, pol);
   });
 }
 
@@ -869,24 +648,19 @@ static int evaluate_policy_impl(salp_vec_t* h, const salp_policy_t* pol, int32_t
   if (rc != SALP_OK) return rc;
   if (!rec) return fail(SALP_ERR_INVALID, "rec is NULL");
   if (H <= 0) return fail(SALP_ERR_INVALID, "horizon must be >= 1");
-  if (flags & ~(uint32_t)(SALP_DEVICE_PTRS | SALP_EVAL_ACCUMULATE))
-    return fail(SALP_ERR_INVALID, "unknown flag bits (SALP_DEVICE_PTRS and SALP_EVAL_ACCUMULATE are defined)");
-  if ((flags & SALP_DEVICE_PTRS) && ((uintptr_t)rec & 15u))
-    return fail(SALP_ERR_INVALID, "rec must be 16-byte aligned (a record is written as two 16-byte stores)");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  h->last_stream = st;
+  rc = check_record_args(flags, SALP_DEVICE_PTRS | SALP_EVAL_ACCUMULATE, kEvalFlagBits, rec,
+                         "rec must be 16-byte aligned (a record is written as two 16-byte stores)");
+  if (rc != SALP_OK) return rc;
+  CallFrame f;
+  if ((rc = f.enter(h, stream)) != SALP_OK) return rc;
   const bool accumulate = (flags & SALP_EVAL_ACCUMULATE) != 0;
   IOPtrs io = io_for(h);
   set_policy_block(io, pol->block);
-  auto launch = [&](float* d_rec) {
-    set_record_block(io, d_rec, accumulate);
-    return run_rollout(h, io, H, st, {kOutSummary, sampled ? ACT_POLICY_SAMPLED : ACT_POLICY}, pol);
-  };
-  if (flags & SALP_DEVICE_PTRS) return launch((float*)rec);
   HostStream s[] = {stream_out((int32_t*)rec, (size_t)h->n * SALP_EVAL_WORDS, accumulate)};
-  return staged(h->stage, st, s, [&] { return launch(s[0].as<float>()); });
+  return staged(h->stage, f.st, flags & SALP_DEVICE_PTRS, s, [&] {
+    set_record_block(io, s[0].as<float>(), accumulate);
+    return run_rollout(h, io, H, f.st, {kOutSummary, sampled ? ACT_POLICY_SAMPLED : ACT_POLICY}, pol);
+  });
 }
 
 int salp_vec_evaluate_policy(salp_vec_t* h, const salp_policy_t* pol, int32_t H, void* rec, uint32_t flags, void* stream) {
@@ -908,96 +682,48 @@ int salp_vec_evaluate_navigation(salp_vec_t* h, const salp_policy_t* pol, int32_
   if (!rec || !line) return fail(SALP_ERR_INVALID, "rec/line is NULL");
   if (H <= 0) return fail(SALP_ERR_INVALID, "horizon must be >= 1");
   if (!(goal_radius > 0.0) || !(goal_radius <= 1.7976931348623157e308)) return fail(SALP_ERR_INVALID, "goal_radius must be finite and positive");
-  if (flags & ~(uint32_t)(SALP_DEVICE_PTRS | SALP_EVAL_ACCUMULATE))
-    return fail(SALP_ERR_INVALID, "unknown flag bits (SALP_DEVICE_PTRS and SALP_EVAL_ACCUMULATE are defined)");
-  if ((flags & SALP_DEVICE_PTRS) && ((uintptr_t)rec & 15u))
-    return fail(SALP_ERR_INVALID, "rec must be 16-byte aligned (a record is written as five 16-byte stores)");
+  rc = check_record_args(flags, SALP_DEVICE_PTRS | SALP_EVAL_ACCUMULATE, kEvalFlagBits, rec,
+                         "rec must be 16-byte aligned (a record is written as five 16-byte stores)");
+  if (rc != SALP_OK) return rc;
   if ((flags & SALP_DEVICE_PTRS) && ((((uintptr_t)line) | ((uintptr_t)track)) & 15u))
     return fail(SALP_ERR_INVALID, "line and track must be 16-byte aligned (read / written 16 bytes at a time)");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  h->last_stream = st;
+  CallFrame f;
+  if ((rc = f.enter(h, stream)) != SALP_OK) return rc;
   const bool accumulate = (flags & SALP_EVAL_ACCUMULATE) != 0;
   IOPtrs io = io_for(h);
   set_policy_block(io, pol->block);
   io.nav_radius = goal_radius;       // (shares its bytes with global_step, which only generated actions read)
-  auto launch = [&](const double* d_line, float* d_rec, double* d_track) {
-    io.nav_line = d_line; set_record_block(io, d_rec, accumulate); io.nav_track = d_track;
-    return run_rollout(h, io, H, st, {kOutNav, ACT_POLICY}, pol);
-  };
-  if (flags & SALP_DEVICE_PTRS) return launch(line, (float*)rec, track);
   HostStream s[] = {stream_in(line, (size_t)h->n * 4), stream_out((int32_t*)rec, (size_t)h->n * SALP_NAV_WORDS, accumulate),
                     stream_out(track, (size_t)H * (size_t)h->n * 2)};
-  return staged(h->stage, st, s, [&] { return launch(s[0].as<const double>(), s[1].as<float>(), s[2].as<double>()); });
+  return staged(h->stage, f.st, flags & SALP_DEVICE_PTRS, s, [&] {
+    io.nav_line = s[0].as<const double>(); set_record_block(io, s[1].as<float>(), accumulate); io.nav_track = s[2].as<double>();
+    return run_rollout(h, io, H, f.st, {kOutNav, ACT_POLICY}, pol);
+  });
 }
 
 int salp_vec_get_state(salp_vec_t* h, double* f64, int32_t* i32, uint32_t flags, void* stream) {
   if (!h) return fail(SALP_ERR_INVALID, "handle is NULL");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  h->last_stream = st;
-  auto launch = [&](double* d_f, int32_t* d_i) {
-    hipLaunchKernelGGL(salp_get_state_kernel, dim3(blocks_for(h->n)), dim3(kBlock), 0, st, h->P, h->S, d_f, d_i);
-    HIP_TRY(hipGetLastError());
-    return (int)SALP_OK;
-  };
-  if (flags & SALP_DEVICE_PTRS) return launch(f64, i32);
+  CallFrame f;
+  if (const int rc = f.enter(h, stream)) return rc;
   HostStream s[] = {stream_out(f64, (size_t)SALP_F_COUNT(h->F) * h->n), stream_out(i32, (size_t)SALP_I_COUNT * h->n)};
-  return staged(h->stage, st, s, [&] { return launch(s[0].as<double>(), s[1].as<int32_t>()); });
-}
-
-// The ranges of include/salp_vec.h ("Ranges accepted by salp_vec_set_state"), on a host snapshot.
-static int check_snapshot(const salp_vec_t* h, const double* f64, const int32_t* i32) {
-  const int64_t n = h->n;
-  char msg[200];
-  if (f64) {
-    for (int64_t i = 0; i < n; ++i) {
-      const double th = f64[SALP_F_THETA * n + i], om = f64[SALP_F_OMEGA * n + i], w = f64[SALP_F_WATER * n + i];
-      if (!(fabs(th) <= SALP_SET_STATE_MAX_ANGLE) || !(fabs(om) <= SALP_SET_STATE_MAX_ANGLE)) {
-        snprintf(msg, sizeof msg, "set_state: env %lld: theta %g / omega %g outside [-%g, %g] (or NaN)", (long long)i, th, om,
-                 SALP_SET_STATE_MAX_ANGLE, SALP_SET_STATE_MAX_ANGLE);
-        return fail(SALP_ERR_INVALID, msg);
-      }
-      if (!(w >= 0.0 && w <= 1.0)) {
-        snprintf(msg, sizeof msg, "set_state: env %lld: water %.17g outside [0, 1] (or NaN)", (long long)i, w);
-        return fail(SALP_ERR_INVALID, msg);
-      }
-    }
-  }
-  if (i32) {
-    for (int64_t i = 0; i < n; ++i) {
-      const int32_t ph = i32[SALP_I_PHASE * n + i], tm = i32[SALP_I_TIMER * n + i], du = i32[SALP_I_EXHALE_DUR * n + i],
-                    ho = i32[SALP_I_SHAPE_HOLD * n + i];
-      if (ph < 0 || ph > 2 || tm < 0 || tm > 255 || du < 0 || du > 255 || ho < 0 || ho > 7) {
-        snprintf(msg, sizeof msg, "set_state: env %lld: phase %d / timer %d / exhale duration %d / shape hold %d outside 0..2 / 0..255 / 0..255 / 0..7",
-                 (long long)i, ph, tm, du, ho);
-        return fail(SALP_ERR_INVALID, msg);
-      }
-    }
-  }
-  return SALP_OK;
+  return staged(h->stage, f.st, flags & SALP_DEVICE_PTRS, s, [&] {
+    return launch_1d(salp_get_state_kernel, h->n, kBlock, f.st, h->P, h->S, s[0].as<double>(), s[1].as<int32_t>());
+  });
 }
 
 int salp_vec_set_state(salp_vec_t* h, const double* f64, const int32_t* i32, uint32_t flags, void* stream) {
   if (!h) return fail(SALP_ERR_INVALID, "handle is NULL");
-  if (!(flags & SALP_DEVICE_PTRS)) {     // nothing is written when any env is out of range
-    const int bad = check_snapshot(h, f64, i32);
-    if (bad != SALP_OK) return bad;
+  if (!(flags & SALP_DEVICE_PTRS)) {     // a host snapshot's ranges (salp_params.h): nothing is written when any env is out of range
+    char msg[200];
+    const int bad = check_snapshot(h->n, f64, i32, msg, sizeof msg);
+    if (bad != SALP_OK) return fail(bad, msg);
   }
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  h->last_stream = st;
-  auto launch = [&](const double* d_f, const int32_t* d_i) {
-    hipLaunchKernelGGL(salp_set_state_kernel, dim3(blocks_for(h->n)), dim3(kBlock), 0, st, h->P, h->S, d_f, d_i);
-    HIP_TRY(hipGetLastError());
-    return (int)SALP_OK;
-  };
-  if (flags & SALP_DEVICE_PTRS) return launch(f64, i32);
+  CallFrame f;
+  if (const int rc = f.enter(h, stream)) return rc;
   HostStream s[] = {stream_in(f64, (size_t)SALP_F_COUNT(h->F) * h->n), stream_in(i32, (size_t)SALP_I_COUNT * h->n)};
-  return staged(h->stage, st, s, [&] { return launch(s[0].as<const double>(), s[1].as<const int32_t>()); });
+  return staged(h->stage, f.st, flags & SALP_DEVICE_PTRS, s, [&] {
+    return launch_1d(salp_set_state_kernel, h->n, kBlock, f.st, h->P, h->S, s[0].as<const double>(), s[1].as<const int32_t>());
+  });
 }
 
 int salp_vec_get_stats(salp_vec_t* h, salp_stats_t* out) {
@@ -1031,14 +757,12 @@ int salp_vec_clear_stats(salp_vec_t* h) {
 
 int salp_vec_reseed(salp_vec_t* h, uint64_t seed, float* obs, uint32_t flags, void* stream) {
   if (!h) return fail(SALP_ERR_INVALID, "handle is NULL");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  h->last_stream = st;
+  CallFrame f;
+  if (int rc = f.enter(h, stream)) return rc;
   const int64_t pitch = h->P.pitch;
-  hipLaunchKernelGGL(salp_reseed_kernel, dim3(blocks_for(pitch)), dim3(kBlock), 0, st, h->cold, h->stats, pitch, (int)h->nf_rows,
-                     (uint32_t)seed, (uint32_t)(seed >> 32));
-  HIP_TRY(hipGetLastError());
+  const int rc = launch_1d(salp_reseed_kernel, pitch, kBlock, f.st, h->cold, h->stats, pitch, (int)h->nf_rows, (uint32_t)seed,
+                           (uint32_t)(seed >> 32));
+  if (rc != SALP_OK) return rc;
   h->seed = seed;
   h->global_step = 0;
   return salp_vec_reset(h, nullptr, obs, flags, stream);   // every env, from draw counter 0 of the new streams
