@@ -83,7 +83,7 @@ def test_out_of_box_and_non_finite_actions_return_promptly():
 
 
 def test_cycle_length_schedule_does_not_change_results(monkeypatch):
-    """The longest-cycle-first walk order (salp_robot.hip, robot_schedule_*) only moves envs between lanes:
+    """The longest-cycle-first walk order (salp_robot_kernels.h, robot_schedule_*) only moves envs between lanes:
     with it forced on and forced off every output and the final state are bit-identical."""
     n, seed, T = 5000, 9, 6
     rng = np.random.default_rng(4)

@@ -199,6 +199,19 @@ def test_tiny_dt_is_refused_by_the_history_calls():
     env.close()
 
 
+def test_capacity_of_the_built_library_is_the_host_twin():
+    """The library that runs on the GPU counts what tests/test_robot_params_host.py checks on the host: handles and
+    capacities only, no step (a step at dt = 8e-7 is millions of Euler steps)."""
+    import robot_params_host_lib as rp
+    for dt in (0.01, 0.005, 0.02, 8e-7):
+        env = SalpRobotVectorEnv(64, device="cuda:0", seed=1, output="numpy", dt=dt)
+        steps = rp.max_steps(dt)
+        assert (steps == -1) == (dt == 8e-7)
+        for s in (1, 4, 10):
+            assert env.L.salp_robot_vec_history_capacity(env._h, s) == rp.history_capacity(steps, s), (dt, s)
+        env.close()
+
+
 def test_rejected_arguments_launch_nothing():
     import torch
     n = 512

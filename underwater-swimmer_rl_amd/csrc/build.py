@@ -8,7 +8,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "salp_vec.hip")             # the C ABI of SalpSnakeEnv.step's hot path: host code; the service kernels it compiles are salp_service_kernels.h
-SRC_ROBOT = os.path.join(HERE, "salp_robot.hip")     # HEAD Robot simulator
+SRC_ROBOT = os.path.join(HERE, "salp_robot.hip")     # the C ABI of the HEAD Robot simulator: host code; its kernels are salp_robot_kernels.h
 INCLUDE = os.path.normpath(os.path.join(HERE, "..", "..", "include"))
 
 

@@ -1,4 +1,4 @@
-// salp_fp64_math.h — the hand-written fp64 math of the robot kernels (salp_robot.hip, salp_robot_cycle_body.h):
+// salp_fp64_math.h — the hand-written fp64 math of the robot kernels (salp_robot_kernels.h, salp_robot_cycle_body.h):
 // sin / cos with its own argument reduction, the carried sin / cos of the Euler angles, and Newton-refined
 // reciprocal / square root.  They replace the device library's routines on a path bound by the fp64 VALU rate, and
 // each has a stated error bound that tests/test_robot_math.py (against mpmath) and tests/test_gpu_robot_math.py
@@ -154,7 +154,7 @@ SALP_MATH_FN double sqrt_nr(double x) {
 }  // namespace salp
 
 // ---- test support ---------------------------------------------------------------------------------------------------
-// salp_robot_math_probe (salp_robot.hip) runs one of the functions above on the device, element i on thread i of
+// salp_robot_math_probe (salp_robot.hip; its kernel is in salp_robot_kernels.h) runs one of the functions above on the device, element i on thread i of
 // 256-thread blocks, so wavefront w holds the elements [64 w, 64 w + 64) and a test can put a lane that triggers a
 // wave-uniform fallback into a wavefront of its choice.  tests/robot_math_host.cpp is the same call on the host, a
 // group of 64 indices voting like a wavefront.  Not part of the public ABI (include/salp_robot.h).

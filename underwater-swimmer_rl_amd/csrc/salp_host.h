@@ -3,7 +3,8 @@
 // launch_1d() and the one body that serves the host-pointer and the device-pointer form of a call (StageBuffer,
 // HostStream, staged()).  Everything here has internal linkage, so each of the two translation units has an
 // error string of its own (salp_last_error and salp_robot_last_error stay independent).  No device code; the rollout
-// kernel units do not include it.
+// kernel units do not include it.  What the two files refuse is decided in headers that do not know fail() and compile
+// without HIP (salp_params.h, salp_policy.h, salp_robot_params.h); the ABI file hands the reason to fail().
 #ifndef SALP_HOST_H
 #define SALP_HOST_H
 

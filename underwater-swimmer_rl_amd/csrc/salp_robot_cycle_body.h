@@ -1,4 +1,4 @@
-// salp_robot_cycle_body.h — one breathing cycle of one robot, included inside the three kernels of salp_robot.hip
+// salp_robot_cycle_body.h — one breathing cycle of one robot, included inside the three kernels of salp_robot_kernels.h
 // that run one: nozzle.solve_angles + Robot.set_control + Robot.step_through_cycle (robot.py:55-85, 335-358, 422-445).
 //   salp_robot_step_kernel, salp_robot_step_record_kernel   through salp_robot_step_body.h (env step)
 //   salp_robot_trajectory_kernel                            once per cycle of the trajectory (compare_trajectories.py)
@@ -45,7 +45,7 @@
   }
   // Robot.set_control (robot.py:335-358)
   r.cycle += 1;
-  const double contract_rate = 0.06 / 3, release_rate = 0.06 / 1.5;
+  const double contract_rate = kContractRate, release_rate = kReleaseRate;   // salp_robot_params.h
   const double refill_time = contraction / contract_rate;
   const double jet_time = contraction / release_rate;
   // The cycle length comes straight from the caller's action.  Inside the action Box [0, 1]^3 it is at most

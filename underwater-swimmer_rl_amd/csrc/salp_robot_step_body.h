@@ -1,4 +1,4 @@
-// salp_robot_step_body.h — the body of the two step kernels of salp_robot.hip (SalpRobotEnv.step,
+// salp_robot_step_body.h — the body of the two step kernels of salp_robot_kernels.h (SalpRobotEnv.step,
 // salp_robot_env.py:139-201: one breathing cycle per env), included inside each kernel:
 //   salp_robot_step_kernel          constexpr bool kRecord = false;  RobotHistory H = {} (unused)
 //   salp_robot_step_record_kernel   constexpr bool kRecord = true;   H = the kernel argument
@@ -12,17 +12,17 @@
 // No include guard: included once per kernel.
   const int64_t i0 = (int64_t)blockIdx.x * kRBlock + threadIdx.x;
   const bool active = i0 < P.n;
-  // `order` (robot_schedule_* in salp_robot.hip) lists the envs longest cycle first, so that the lanes of a wavefront
+  // `order` (robot_schedule_* in salp_robot_kernels.h) lists the envs longest cycle first, so that the lanes of a wavefront
   // run about the same number of Euler steps; results do not depend on which lane an env runs in.
   const int64_t i = active ? (order ? (int64_t)order[i0] : i0) : (P.n - 1);
   const uint64_t genv = P.env_base + (uint64_t)i;
   Rb r;
   load_robot(r, S, P, i);
 
-  // _rescale_action (:129-137) in fp64
-  const double contraction = (double)act[i * 3 + 0] * 0.06;
-  const double coast_time = (double)act[i * 3 + 1] * 10.0;
-  const double yaw = (double)act[i * 3 + 2] * (kPi / 2);
+  // _rescale_action (:129-137) in fp64 (the scales: salp_robot_params.h)
+  const double contraction = (double)act[i * 3 + 0] * kActContraction;
+  const double coast_time = (double)act[i * 3 + 1] * kActCoast;
+  const double yaw = (double)act[i * 3 + 2] * kActYaw;
 #include "salp_robot_cycle_body.h"
   if constexpr (kRecord) {
     if (rec && H.len) H.len[hj] = n_samples;
