@@ -1,8 +1,10 @@
 // salp_service_kernels.h — the service kernels of the snake library, everything on the device that is not the fused
 // step/rollout kernel (salp_rollout_kernel.h): generated actions, reset / observe, the state snapshots, reseed, and the
-// policy relayout and noise step.  Included by salp_vec.hip alone, which launches them; device code only.
+// policy relayout and noise step; and the math probe of the tests.  Included by salp_vec.hip alone, which launches them;
+// device code only.
 #pragma once
 #include "salp_rollout_kernel.h"   // through it: DevParams / DevState / ColdBlock, Env, the draw streams, PH_*, kBlock
+#include "salp_snake_math_probe.h" // SALP_SNAKE_MATH_*
 
 namespace {
 
@@ -149,6 +151,43 @@ __global__ void salp_policy_noise_kernel(float* block, uint64_t add, uint64_t se
   const uint64_t v = do_set ? set : ((((uint64_t)w[1] << 32) | w[0]) + add);
   w[0] = (uint32_t)v;
   w[1] = (uint32_t)(v >> 32);
+}
+
+// ---- test support: the snake step's math primitives on their own (salp_snake_math_probe, salp_snake_math_probe.h) ----
+// Element i on thread i; `function` is uniform, so the table pointer and the key words stay scalar as in the step.
+template <bool STD>
+__device__ __forceinline__ void probe_thrust_terms(const DevParams& P, const double* in, double* out, int64_t n, int64_t i) {
+  const uint64_t genv = (uint64_t)(uint32_t)in[5 * n + i] | ((uint64_t)(uint32_t)in[6 * n + i] << 32);
+  const ThrustTerms t = jet_thrust_terms<STD>(in[i], in[n + i], in[2 * n + i], in[3 * n + i], (uint32_t)in[4 * n + i], genv, P);
+  out[i] = t.ax; out[n + i] = t.ay; out[2 * n + i] = t.bx; out[3 * n + i] = t.by;
+  out[4 * n + i] = t.cx; out[5 * n + i] = t.cy; out[6 * n + i] = t.om;
+}
+__global__ __launch_bounds__(kBlock) void salp_snake_math_probe_kernel(DevParams P, int function, const double* in, double* out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  switch (function) {
+    case SALP_SNAKE_MATH_SINCOS_T: { double s, c; sincos_small_t(thrust_table(), in[i], s, c); out[i] = s; out[n + i] = c; break; }
+    case SALP_SNAKE_MATH_SIN_NOZZLE_T: out[i] = sin_nozzle_t(thrust_table(), in[i]); break;
+    case SALP_SNAKE_MATH_ATAN2: out[i] = (double)atan2_fast<false>((float)in[i], (float)in[n + i]); break;
+    case SALP_SNAKE_MATH_ATAN2_PRECISE: out[i] = (double)atan2_fast<true>((float)in[i], (float)in[n + i]); break;
+    case SALP_SNAKE_MATH_COS_WRAPPED: out[i] = (double)cos_wrapped((float)in[i]); break;
+    case SALP_SNAKE_MATH_REL_HEADING:
+      out[i] = (double)relative_heading<false>((float)in[i], (float)in[n + i], (float)in[2 * n + i]);
+      break;
+    case SALP_SNAKE_MATH_REL_HEADING_PRECISE:
+      out[i] = (double)relative_heading<true>((float)in[i], (float)in[n + i], (float)in[2 * n + i]);
+      break;
+    case SALP_SNAKE_MATH_PHILOX: {
+      const U4 w = philox4x32_10((uint32_t)in[i], (uint32_t)in[n + i], (uint32_t)in[2 * n + i], (uint32_t)in[3 * n + i],
+                                 (uint32_t)in[4 * n + i], (uint32_t)in[5 * n + i]);
+      out[i] = (double)w.x; out[n + i] = (double)w.y; out[2 * n + i] = (double)w.z; out[3 * n + i] = (double)w.w;
+      break;
+    }
+    case SALP_SNAKE_MATH_U53: out[i] = u53((uint32_t)in[i], (uint32_t)in[n + i]); break;
+    case SALP_SNAKE_MATH_THRUST_STD: probe_thrust_terms<true>(P, in, out, n, i); break;
+    case SALP_SNAKE_MATH_THRUST_RT: probe_thrust_terms<false>(P, in, out, n, i); break;
+    default: break;
+  }
 }
 
 }  // namespace

@@ -28,7 +28,8 @@ __device__ __forceinline__ bool is_none(double fx) { return fx != fx; }
 // which v_fma_f64 / v_mul_f64 take directly as an operand.  The table pointer is made opaque at the point of
 // use so that the loads stay inside the (conditional) thrust block instead of being hoisted across the step
 // loop, where they would only be spilled.  Values and evaluation order are those of sincos_small
-// (salp_fp64_math.h) and of sin_nozzle_t's polynomial below: results are bit-identical.
+// (salp_fp64_math.h) and of sin_nozzle_t's polynomial below: results are bit-identical (tests/test_gpu_snake_math.py holds
+// sincos_small_t to sincos_small's host twin bit for bit; tests/test_snake_math.py holds every row to its definition).
 typedef const double __attribute__((address_space(4))) tbl_double;
 enum {
   TT_2OPI = 0, TT_PIO2_1, TT_PIO2_1T, TT_S5, TT_S4, TT_S3, TT_S2, TT_S1,          // sincos reduction, sin kernel
@@ -94,8 +95,11 @@ __device__ __forceinline__ void sincos_small_t(tbl_double* T, double x, double& 
   s = (q & 2) ? -s0 : s0;
   c = ((q + 1) & 2) ? -c0 : c0;
 }
-// sin(x) for |x| <= pi/3 (the nozzle angle): odd Taylor polynomial to x^21, error < 2e-22 for |x| <= pi/3.  The
-// coefficients (1/21!, -1/19!, ... -1/3!) are rows TT_N10 .. TT_N1 of the table.
+// sin(x) for |x| <= pi/3 (the nozzle angle): odd Taylor polynomial to x^21.  The polynomial's truncation error is < 2e-22
+// for |x| <= pi/3; the function's error is its roundings, <= 1 ulp of sin x (the last fma rounds x + x z p once, the
+// correction is <= 0.19 |x| with a few ulps of relative error; measured 0.95 ulp, tests/test_snake_math.py).  The
+// coefficients (1/21!, -1/19!, ... -1/3!) are rows TT_N10 .. TT_N1 of the table.  The sum of -0 and the correction's +0
+// is +0, so the sign of a zero argument is copied over: sin(-0) = -0, as the reference's.
 __device__ __forceinline__ double sin_nozzle_t(tbl_double* T, double x) {
   const double z = x * x;
   double p = fma_s(z, (double)T[TT_N10], T[TT_N9]);
@@ -107,16 +111,23 @@ __device__ __forceinline__ double sin_nozzle_t(tbl_double* T, double x) {
   p = fma_s(z, p, T[TT_N3]);
   p = fma_s(z, p, T[TT_N2]);
   p = fma_s(z, p, T[TT_N1]);
-  return fma(x * z, p, x);
+  return __builtin_copysign(fma(x * z, p, x), x);
 }
 
 // fp32 helpers for quantities that only leave the simulator (observation angle, reward shaping).  Three food bearings per
 // step were 110 of the 12-food kernel's ~590 VALU instructions per wavefront-step (round 2: degree-17 polynomial, Newton
 // step on the reciprocal, compare / select unfolding and wrapping); the contract is 1e-5 on angle / pi.
 // atan2 for the food bearing: t = min / max through v_rcp_f32 (1 ulp), odd minimax polynomial on [0, 1] (Remez fits),
-// octant / quadrant unfolding, sign by bit copy.  PRECISE = false (bearings that only go to the observation): degree 11,
-// max error 1.7e-6 rad = 5.3e-7 of the observation's unit.  PRECISE = true (the nearest food's bearing, which the reward
-// multiplies by proximity_reward_weight, 5 in single_food.yaml): degree 13, 2.5e-7 rad.
+// octant / quadrant unfolding, sign by bit copy.  PRECISE = false (bearings that only go to the observation): degree 11.
+// PRECISE = true (the nearest food's bearing, which the reward multiplies by proximity_reward_weight, 5 in
+// single_food.yaml): degree 13.  Two errors, not one:
+//   polynomial (the fit's own, in exact arithmetic)       1.7e-6 rad (degree 11)    2.5e-7 rad (degree 13)
+//   function (with the fp32 roundings of t, the Horner steps, t p and the unfolding subtractions from pi/2 and pi, whose
+//   results carry up to 1.2e-7 of rounding each, and pi_f32 - pi = 8.7e-8; correctly rounded reciprocal)
+//                                                         1.9e-6 rad = 6.1e-7 of pi  5.0e-7 .. 5.4e-7 rad
+// v_rcp_f32 adds one ulp of t (<= 1.2e-7 rad).  The device's measured figures are in DESIGN.md §4; tests/test_gpu_snake_math.py
+// asserts the function's error, never the polynomial's.  Both arguments under the 1e-30 floor: t = min * 1e30, not atan2
+// (an fp64 tank position yields offsets that are 0 or above 1e-14).
 template <bool PRECISE>
 __device__ __forceinline__ float atan2_fast(float y, float x) {
   const float ax = fabsf(x), ay = fabsf(y);
@@ -145,7 +156,9 @@ __device__ __forceinline__ float atan2_fast(float y, float x) {
   return __builtin_copysignf(a, y);
 }
 
-// cos(x) for |x| <= pi (a wrapped heading): fold to [0, pi/2], even Taylor polynomial to x^12 (error 6.5e-9).
+// cos(x) for |x| <= pi (a wrapped heading): fold to [0, pi/2], even Taylor polynomial to x^12.  The polynomial's truncation
+// error is 6.5e-9; the function's error is 1.6e-7: the fold pi_f32 - |x| is off by pi_f32 - pi = 8.7e-8 where the slope is 1,
+// and the result is rounded to fp32 (3e-8 .. 6e-8).  No reciprocal: the device equals the fp32 emulation bit for bit.
 __device__ __forceinline__ float cos_wrapped(float x) {
   float ax = fabsf(x);
   const bool flip = ax > 1.57079632679489662f;
@@ -162,6 +175,10 @@ __device__ __forceinline__ float cos_wrapped(float x) {
 
 // Heading of a food relative to the body axis, wrapped to [-pi, pi] (fp32): both angles are in [-pi, pi], so one multiple
 // of 2 pi at most is off — round-to-nearest-even of rel / 2 pi is 0 on the closed interval, as snake:403-407's strict loops.
+// Error on the circle for |th| <= pi: atan2_fast's plus the rounding of the difference and of the wrap, 2.2e-6 rad
+// (PRECISE: 8.1e-7 rad, and 7.9e-7 on cos_wrapped of it, 4e-6 on a reward term of weight 5).  An injected heading up to
+// SALP_SET_STATE_MAX_ANGLE = 100 rad that has not been wrapped by a step yet takes up to 16 turns out with an fp32 2 pi
+// (1.7e-7 off per turn) from a difference rounded at ulp(64 .. 128) = 7.6e-6: 8e-6 rad = 2.5e-6 of pi, inside the contract.
 template <bool PRECISE = false>
 __device__ __forceinline__ float relative_heading(float dy, float dx, float th) {
   const float rel = atan2_fast<PRECISE>(dy, dx) - th;

@@ -40,9 +40,11 @@ __device__ __forceinline__ ThrustTerms jet_thrust_terms(double th, double noz, d
   const double moment = mul_s(perp * arm, TT[TT_K00005]);
   const double shape = mul_s((nn * T) * water, TT[TT_K00003]);
   t.om = (primary + moment) + shape;
-  {  // side thrust at fl(phi + fl(pi/2)) = phi + pi/2 + dl,  dl = fl(pi/2) - pi/2 (6.1e-17) up to the rounding of the sum
-     // (<= 4.4e-16: 4e-17 px per step through the 0.1-px side term, below the device sincos' own last-bit departure from
-     // glibc — round 2 recovered it with a TwoSum, six fp64 instructions per thrust step)
+  {  // side thrust at fl(phi + fl(pi/2)) = phi + pi/2 + dl,  dl = fl(pi/2) - pi/2 (6.1e-17) up to the rounding of the sum,
+     // ulp(|phi + pi/2|) / 2: 2.2e-16 rad below 2, 4.4e-16 below 4 (a wrapped heading: 4e-17 px per step through the 0.1-px
+     // side term, below the device sincos' own last-bit departure from glibc — round 2 recovered it with a TwoSum, six fp64
+     // instructions per thrust step), and 7.1e-15 rad up to the |theta| <= 100 that salp_vec_set_state admits before the
+     // first step wraps it (7e-16 px).  Measured per term against the reference's formulas: tests/test_gpu_snake_math.py.
     const double dl = TT[TT_DL];
     const double sc = -fma(dl, c, s);     // cos(side) = -sin(phi + dl)
     const double ss = fma(-dl, s, c);     // sin(side) =  cos(phi + dl)
@@ -58,7 +60,9 @@ __device__ __forceinline__ ThrustTerms jet_thrust_terms(double th, double noz, d
     const U4 w = philox4x32_10(g0, (uint32_t)(genv >> 32), rng, 0u, k0, k1);
     const double u = u53(w.x, w.y);
     const double d = mul_s(u - 0.5, TT[TT_K005]);
-    const double D = d;                   // fl(phi + d) = phi + D up to the sum's rounding (<= 4.4e-16 rad on a 3e-3-px term)
+    const double D = d;                   // fl(phi + d) = phi + D up to the sum's rounding, ulp(|phi + d|) / 2 as above (<= 4.4e-16
+                                          // rad for a wrapped heading, 7.1e-15 at |theta| = 100, on a 3e-3-px term); the series drop
+                                          // D^11 / 11! and D^10 / 10! (< 3e-23 at |D| <= 0.025)
     const double z = D * D;
     double sp = fma_s(z, (double)TT[TT_J_S3], TT[TT_J_S2]);
     sp = fma_s(z, sp, TT[TT_J_S1]);

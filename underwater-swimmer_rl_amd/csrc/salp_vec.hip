@@ -768,4 +768,46 @@ int salp_vec_reseed(salp_vec_t* h, uint64_t seed, float* obs, uint32_t flags, vo
   return salp_vec_reset(h, nullptr, obs, flags, stream);   // every env, from draw counter 0 of the new streams
 }
 
+// Test support (salp_snake_math_probe.h): one of the snake step's math primitives over host arrays, staged like the other
+// host-pointer calls.  The thrust forms get the launch parameters a handle of this config would have; the key words and the
+// memory copy of the parameters sit in a ColdBlock of the call's own, behind the arrays in the staging block.
+int salp_snake_math_probe(int device_id, int function, const salp_config_t* cfg, uint64_t seed, const double* in, double* out,
+                          int64_t n) {
+  if (!in || !out) return fail(SALP_ERR_INVALID, "in / out is NULL");
+  if (n < 1 || n > ((int64_t)1 << 24)) return fail(SALP_ERR_INVALID, "n must be in [1, 2^24]");
+  size_t rows_in = 1, rows_out = 1;
+  switch (function) {
+    case SALP_SNAKE_MATH_SINCOS_T: rows_out = 2; break;
+    case SALP_SNAKE_MATH_SIN_NOZZLE_T: case SALP_SNAKE_MATH_COS_WRAPPED: break;
+    case SALP_SNAKE_MATH_ATAN2: case SALP_SNAKE_MATH_ATAN2_PRECISE: case SALP_SNAKE_MATH_U53: rows_in = 2; break;
+    case SALP_SNAKE_MATH_REL_HEADING: case SALP_SNAKE_MATH_REL_HEADING_PRECISE: rows_in = 3; break;
+    case SALP_SNAKE_MATH_PHILOX: rows_in = 6; rows_out = 4; break;
+    case SALP_SNAKE_MATH_THRUST_STD: case SALP_SNAKE_MATH_THRUST_RT: rows_in = 7; rows_out = 7; break;
+    default: return fail(SALP_ERR_INVALID, "unknown function code");
+  }
+  salp_config_t c;
+  if (cfg) c = *cfg; else default_config(&c);
+  int rc = validate(&c);
+  if (rc != SALP_OK) return rc;
+  ColdBlock cb;
+  memset(&cb, 0, sizeof(cb));
+  cb.P = make_params(c, n, n, seed, 0);
+  cb.seed[0] = (uint32_t)seed; cb.seed[1] = (uint32_t)(seed >> 32);
+  if (function == SALP_SNAKE_MATH_THRUST_STD && !is_std(cb.P))
+    return fail(SALP_ERR_INVALID, "THRUST_STD needs a config whose constants are the literals (the product runs it through the runtime-constant kernels)");
+  rc = check_device_id(device_id);
+  if (rc != SALP_OK) return rc;
+  DeviceScope dev_scope;
+  HIP_TRY(dev_scope.enter(device_id));
+  StageBuffer stage;     // the call's own, released on return
+  HostStream s[] = {stream_in(in, rows_in * (size_t)n), stream_out(out, rows_out * (size_t)n), stream_in(&cb, 1)};
+  return staged(stage, nullptr, false, s, [&] {
+    DevParams P = cb.P;
+    ColdBlock* const dev = s[2].as<ColdBlock>();
+    P.seed = (seed_word_t*)(uintptr_t)dev->seed;      // device addresses, as salp_vec_create sets them
+    P.self = (dev_params_c*)(uintptr_t)&dev->P;
+    return launch_1d(salp_snake_math_probe_kernel, n, kBlock, nullptr, P, function, s[0].as<const double>(), s[1].as<double>(), n);
+  });
+}
+
 }  // extern "C"
