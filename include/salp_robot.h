@@ -15,6 +15,7 @@
  *   salp_robot_vec_history_capacity  samples per env that salp_robot_vec_step_history may write
  *   salp_robot_vec_trajectory   compare_actions_with_states (compare_trajectories.py:19-117) for every robot of the
  *                               handle at once, each with its own physical parameters (system identification)
+ * (H cycles per robot in one launch, open loop or under an in-kernel policy: salp_robot_rollout.h.)
  *
  * Actions are float32 [n][3] in the env's Box ([0,1], [0,1], [-1,1]): contraction / 0.06 m, coast time
  * / 10 s, nozzle yaw / (pi/2).  They are widened to fp64 before the rescale of salp_robot_env.py:129-137.

@@ -1,0 +1,159 @@
+#!/usr/bin/env python3
+"""Multi-cycle robot rollouts (salp_robot_vec_rollout / salp_robot_vec_rollout_policy) against the host loop they replace,
+and the rollout kernel's service period M (csrc/salp_robot_kernels.h).  On the GPU box.
+    python profiles/robot_rollout_perf.py [--envs 4096,262144] [--horizon 16] [--rounds 5] [--window 0.5] [--out FILE]
+
+Rows: env count x action mix (Box-wide: coast 0-10 s; short: coast <= 1 s) x loop (open: recorded actions; closed: a linear
+and a 64 x 64 tanh policy).  Forms of a row, each on an env of its own (same seed):
+    step loop     the path without this feature: H `step` calls on the recorded actions; closed loop: `sac.Actor` forward
+                  (deterministic) + `step`, H times.  The cycle-length schedule stays at its default (on from 32768 envs).
+    M = 0         the rollout kernel, synchronised form (a wavefront's lanes go cycle by cycle)
+    M = 32, 128, 512   a lane whose cycle has ended waits at most M Euler iterations for its next one
+Method: device events around `calls` back-to-back calls, `calls` chosen so that a window lasts `--window` seconds; every
+form is warmed up first; the forms of a row are ALTERNATED inside each of `--rounds` rounds, and a row reports the median
+over the rounds and the spread (max - min) / median of each form's identical repeats.  Closed-loop envs are reset before every
+window so that every form starts its episodes from rest; the policies' output layers are scaled up so that their actions
+spread over the Box (the mean and the largest cycle length of a row are printed).  M is read by the library at create
+(SALP_ROBOT_ROLLOUT_M), which is how one process holds all four."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+
+PERIODS = (0, 32, 128, 512)
+MIXES = {"box": 1.0, "short": 0.1}          # upper end of the coast component
+
+
+def make_env(n, period=None):
+    from underwater_swimmer_rl_amd.robot_env import SalpRobotVectorEnv
+    if period is None:
+        os.environ.pop("SALP_ROBOT_ROLLOUT_M", None)
+    else:
+        os.environ["SALP_ROBOT_ROLLOUT_M"] = str(period)
+    env = SalpRobotVectorEnv(n, device="cuda:0", seed=3)
+    os.environ.pop("SALP_ROBOT_ROLLOUT_M", None)
+    return env
+
+
+def actor_for(hidden, coast_hi, seed, obs):
+    """A `sac.Actor` on the Box [0, 1] x [0, coast_hi] x [-1, 1] whose deterministic actions spread over it: the output
+    layer is scaled so that its pre-activations have a standard deviation of 1.2 on the observations `obs`."""
+    import torch
+    from underwater_swimmer_rl_amd.sac import Actor
+    torch.manual_seed(seed)
+    actor = Actor(6, 3, hidden, act_low=np.array([0.0, 0.0, -1.0]), act_high=np.array([1.0, coast_hi, 1.0])).to("cuda:0")
+    with torch.no_grad():
+        actor.mu.bias.zero_()
+        actor.mu.weight.mul_(1.2 / actor.mu(actor.body(obs)).std())
+    return actor.eval()
+
+
+def timed(run, calls):
+    import torch
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ev[0].record()
+    for _ in range(calls):
+        run()
+    ev[1].record()
+    ev[1].synchronize()
+    return ev[0].elapsed_time(ev[1]) / calls
+
+
+def measure(forms, rounds, window, before=None):
+    """forms: name -> callable.  Returns name -> (median ms, spread, calls per window)."""
+    import torch
+    calls = {}
+    for name, run in forms.items():           # warm-up of every form, and the calls that fill a window
+        run()
+        torch.cuda.synchronize()
+        if before:
+            before(name)
+        ms = timed(run, 2)
+        calls[name] = max(2, min(200, int(round(window * 1e3 / ms))))
+    samples = {name: [] for name in forms}
+    for _ in range(rounds):
+        for name, run in forms.items():       # alternated
+            if before:
+                before(name)
+            samples[name].append(timed(run, calls[name]))
+    return {name: (float(np.median(v)), float((max(v) - min(v)) / np.median(v)), calls[name]) for name, v in samples.items()}
+
+
+def main():
+    import torch
+    from underwater_swimmer_rl_amd.policy import MLPPolicy
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", default="4096,262144")
+    ap.add_argument("--horizon", type=int, default=16)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--window", type=float, default=0.5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    H = args.horizon
+    rows = []
+    for n in (int(x) for x in args.envs.split(",")):
+        base = make_env(n)
+        rolls = {m: make_env(n, m) for m in PERIODS}
+        for mix, coast_hi in MIXES.items():
+            rng = np.random.default_rng(7)
+            acts = torch.as_tensor(np.stack([rng.uniform(0, 1, (H, n)), rng.uniform(0, coast_hi, (H, n)), rng.uniform(-1, 1, (H, n))],
+                                            axis=2).astype(np.float32), device="cuda:0")
+
+            def step_loop():
+                for t in range(H):
+                    base.step(acts[t])
+            forms = {"step loop": step_loop}
+            for m, env in rolls.items():
+                forms[f"M={m}"] = (lambda e: lambda: e.rollout(acts))(env)
+            inner = rolls[0].rollout(acts)["inner_steps"].float()
+            row = dict(envs=n, mix=mix, loop="open", horizon=H, mean_cycle_steps=float(inner.mean()), max_cycle_steps=int(inner.max()),
+                       forms=measure(forms, args.rounds, args.window))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            for label, hidden in (("linear", ()), ("64x64", (64, 64))):
+                actor = actor_for(hidden, coast_hi, 5, base.reset()[0])
+                policy = MLPPolicy.from_actor(actor)
+                handles = {m: env.make_policy(policy) for m, env in rolls.items()}
+
+                def actor_loop():
+                    with torch.no_grad():
+                        obs = base.observe()
+                        for t in range(H):
+                            a, _ = actor(obs, deterministic=True, with_logprob=False)
+                            obs = base.step(a)[0]
+                forms = {"step loop": actor_loop}
+                for m, env in rolls.items():
+                    forms[f"M={m}"] = (lambda e, h: lambda: e.rollout_policy(h, H, want_actions=False))(env, handles[m])
+                envs_of = {"step loop": base, **{f"M={m}": e for m, e in rolls.items()}}
+                rolls[0].reset()
+                inner = rolls[0].rollout_policy(handles[0], H)["inner_steps"].float()
+                row = dict(envs=n, mix=mix, loop=f"closed {label}", horizon=H, mean_cycle_steps=float(inner.mean()),
+                           max_cycle_steps=int(inner.max()),
+                           forms=measure(forms, args.rounds, args.window, before=lambda name: envs_of[name].reset()))
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+                for h in handles.values():
+                    h.close()
+        for e in (base, *rolls.values()):
+            e.close()
+    print("\n| envs | mix | loop | mean / max Euler steps per cycle | " + " | ".join(["step loop"] + [f"M = {m}" for m in PERIODS]) + " | largest spread |")
+    print("|---|---|---|---|" + "---|" * (len(PERIODS) + 2))
+    for r in rows:
+        f = r["forms"]
+        cells = [f"{f[k][0]:.2f}" for k in ["step loop"] + [f"M={m}" for m in PERIODS]]
+        print(f"| {r['envs']} | {r['mix']} | {r['loop']} | {r['mean_cycle_steps']:.0f} / {r['max_cycle_steps']} | " + " | ".join(cells) +
+              f" | {100 * max(v[1] for v in f.values()):.1f} % |")
+    print("(ms per call of H = %d env steps; median of %d alternated rounds)" % (H, args.rounds))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            for r in rows:
+                fh.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()

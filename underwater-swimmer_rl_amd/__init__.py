@@ -16,6 +16,9 @@ def __getattr__(name):  # lazy: the pieces below need torch / the HIP library
     if name in ("ShardedSalpVectorEnv",):
         from . import sharded
         return getattr(sharded, name)
+    if name in ("SalpRobotVectorEnv", "RobotPolicyHandle"):
+        from . import robot_env
+        return getattr(robot_env, name)
     if name in ("compare_actions_with_states", "robot_params", "params_from_robot", "ROBOT_PARAM_NAMES"):
         from . import robot_compare
         return getattr(robot_compare, name)

@@ -1,9 +1,11 @@
-// salp_robot.hip — the C ABI of include/salp_robot.h, the batched HEAD simulator for gfx950: the
+// salp_robot.hip — the C ABI of include/salp_robot.h and include/salp_robot_rollout.h, the batched HEAD simulator for gfx950: the
 // reference's `Robot.step_through_cycle` (src/salp/environments/robot.py) under `SalpRobotEnv.step/reset`
 // (src/salp/environments/salp_robot_env.py), one robot per lane.  Host code only: the handle and the entry points.
 //   salp_robot_kernels.h   every kernel this file launches (and the notes on how the simulator is laid out on the GPU)
 //   salp_robot_params.h    RobotParams and its derivation from a config, the constants, every argument check
 //   salp_host.h            fail, HIP_TRY, DeviceScope, check_device_id, CallFrame, launch_1d, StageBuffer, staged()
+//   salp_policy.h          the in-kernel policy's descriptor ranges, block map and header (host functions, generic in the dimensions)
+//   salp_policy_upload.h   the upload of a policy's weights, shared with salp_vec.hip
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -14,9 +16,11 @@
 #include <vector>
 
 #include "../../include/salp_robot.h"
+#include "../../include/salp_robot_rollout.h"
 #include "salp_robot_params.h"
 #include "salp_robot_kernels.h"
 #include "salp_host.h"
+#include "salp_policy_upload.h"
 
 using namespace salp;
 
@@ -31,6 +35,19 @@ struct salp_robot_vec {
   int32_t* order;     // [n]
   bool schedule;      // walk the envs longest cycle first (see robot_schedule_*)
   int64_t max_steps;  // robot_max_steps(dt), counted at create
+  int period;         // the rollout kernel's service period M, one of kRolloutPeriods (salp_robot_params.h)
+};
+
+struct salp_robot_policy {
+  salp_robot_vec* h;         // the handle it is bound to (its env count fixes env -> policy)
+  salp_policy_desc_t d;
+  int device;
+  int words;                 // public words of one policy
+  int stride;                // words of one policy in the device block (salp_policy.h)
+  float* block;              // device: header + P policies, what the kernel reads
+  float* pub;                // device: staging of the public layout [P][words] (host-pointer create / update)
+  int32_t* map;              // device: word k of a policy in the block <- public word map[k] (-1: zero)
+  mutable hipStream_t last_stream;   // the stream of its most recent upload or rollout: what destroy waits for
 };
 
 // Below this many envs every wavefront has an execution unit to itself and the launch lasts as long as
@@ -54,6 +71,37 @@ static int launch_robot_step(salp_robot_vec* h, const float* act, float* obs, fl
                      final_obs, inner_steps, order, *hist);
   return launch_1d(salp_robot_step_kernel, h->n, kRBlock, st, h->P, h->S, act, obs, reward, terminated, truncated, final_obs,
                    inner_steps, order);
+}
+
+// salp_robot_vec_rollout (ACT = kActRead, source = the actions) and salp_robot_vec_rollout_policy (kActPolicy, source = the
+// policy's device block, which is on the device whatever `flags` says); everything is checked before anything is launched.
+template <int ACT>
+static int robot_rollout_impl(salp_robot_vec_t* h, const float* source, int32_t horizon, float* obs, float* reward,
+                              uint8_t* terminated, uint8_t* truncated, float* final_obs, int32_t* inner_steps, float* act_out,
+                              uint32_t flags, void* stream) {
+  char why[160];
+  if (const int bad = check_rollout_args(h->max_steps, horizon, flags, source != nullptr,
+                                         obs || reward || terminated || truncated, why, sizeof(why)))
+    return fail(bad, why);
+  CallFrame f;
+  if (const int rc = f.enter(h, stream)) return rc;
+  RobotRollout J;
+  J.horizon = horizon; J.max_iters = rollout_max_iters(horizon, h->max_steps, h->period);
+  const size_t n = (size_t)h->n, HN = (size_t)horizon * n;
+  HostStream s[] = {stream_in(ACT == kActRead ? source : nullptr, HN * 3), stream_out(obs, HN * 6), stream_out(reward, HN),
+                    stream_out(terminated, HN), stream_out(truncated, HN), stream_out(final_obs, HN * 6, true),
+                    stream_out(inner_steps, HN), stream_out(act_out, HN * 3)};
+  return staged(h->stage, f.st, flags & 1u, s, [&] {
+    J.act = ACT == kActRead ? s[0].as<const float>() : source;
+    J.obs = s[1].as<float>(); J.reward = s[2].as<float>(); J.terminated = s[3].as<uint8_t>(); J.truncated = s[4].as<uint8_t>();
+    J.final_obs = s[5].as<float>(); J.inner_steps = s[6].as<int32_t>(); J.act_out = s[7].as<float>();
+    switch (h->period) {
+      case 0: return launch_1d(salp_robot_rollout_kernel<ACT, 0>, h->n, kRBlock, f.st, h->P, h->S, J);
+      case 32: return launch_1d(salp_robot_rollout_kernel<ACT, 32>, h->n, kRBlock, f.st, h->P, h->S, J);
+      case 128: return launch_1d(salp_robot_rollout_kernel<ACT, 128>, h->n, kRBlock, f.st, h->P, h->S, J);
+      default: return launch_1d(salp_robot_rollout_kernel<ACT, 512>, h->n, kRBlock, f.st, h->P, h->S, J);
+    }
+  });
 }
 
 extern "C" {
@@ -85,6 +133,10 @@ int salp_robot_vec_create(const salp_robot_config_t* cfg, int64_t n_envs, int de
   h->schedule = n_envs >= kScheduleMinEnvs;
   if (const char* ev = getenv("SALP_ROBOT_SCHEDULE")) h->schedule = ev[0] == '1';
   if (n_envs > INT32_MAX) h->schedule = false;
+  h->period = kRolloutPeriod;     // SALP_ROBOT_ROLLOUT_M=0/32/128/512 overrides (profiles/robot_rollout_perf.py measures them all)
+  if (const char* ev = getenv("SALP_ROBOT_ROLLOUT_M"))
+    for (const int m : kRolloutPeriods)
+      if (atoi(ev) == m) h->period = m;
   const size_t bytes = (size_t)SALP_R_COUNT * (size_t)h->P.pitch * sizeof(double);
   hipError_t e = hipMalloc((void**)&h->S.f, bytes);
   if (e == hipSuccess) e = hipMemset(h->S.f, 0, bytes);
@@ -205,6 +257,105 @@ int salp_robot_vec_trajectory(salp_robot_vec_t* h, const double* params, const d
     J.states = s[3].as<double>(); J.metrics = s[4].as<double>(); J.inner_steps = s[5].as<int32_t>();
     return launch_1d(salp_robot_trajectory_kernel, h->n, kRBlock, f.st, h->P, J);
   });
+}
+
+int salp_robot_vec_rollout(salp_robot_vec_t* h, const float* act, int32_t horizon, float* obs, float* reward,
+                           uint8_t* terminated, uint8_t* truncated, float* final_obs, int32_t* inner_steps,
+                           uint32_t flags, void* stream) {
+  if (!h) return fail(SALP_ERR_INVALID, "handle is NULL");
+  return robot_rollout_impl<kActRead>(h, act, horizon, obs, reward, terminated, truncated, final_obs, inner_steps, nullptr, flags,
+                                      stream);
+}
+
+// The descriptor's ranges for a robot handle (salp_policy.h; obs_dim 6, act_dim 3, and kmax = 3, which those ranges ask of
+// a snake handle).  On success *words = public words of one policy.
+static int check_robot_policy_desc(const salp_robot_vec_t* h, const salp_policy_desc_t* d, int* words) {
+  const char* why = "";
+  const int rc = h ? check_policy_desc(ROBOT_POLICY_OBS, ROBOT_POLICY_ACT, 3, h->n, d, false, words, &why)
+                   : check_policy_desc(0, 0, 0, 0, nullptr, false, words, &why);
+  return rc == SALP_OK ? rc : fail(rc, why);
+}
+
+int salp_robot_policy_words(const salp_robot_vec_t* h, const salp_policy_desc_t* desc) {
+  int words = 0;
+  const int rc = check_robot_policy_desc(h, desc, &words);
+  return rc != SALP_OK ? rc : words;
+}
+
+void salp_robot_policy_destroy(salp_robot_policy_t* pol) {
+  if (!pol) return;
+  DeviceScope dev_scope;
+  (void)dev_scope.enter(pol->device);
+  (void)hipStreamSynchronize(pol->last_stream);     // its uploads and the rollouts that read the block (hipFree does not wait on non-blocking streams)
+  if (pol->block) (void)hipFree(pol->block);
+  if (pol->pub) (void)hipFree(pol->pub);
+  if (pol->map) (void)hipFree(pol->map);
+  delete pol;
+}
+
+static int robot_policy_upload(salp_robot_policy* pol, const float* weights, uint32_t flags, hipStream_t st) {
+  pol->last_stream = st;
+  const PolicyBlock b = {pol->block, pol->pub, pol->map, pol->d.n_policies, pol->words, pol->stride};
+  HIP_TRY(policy_block_upload(b, weights, (flags & 1u) != 0, st));     // salp_policy_upload.h (defined in salp_vec.hip)
+  return SALP_OK;
+}
+
+int salp_robot_policy_create(salp_robot_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags,
+                             void* stream, salp_robot_policy_t** out) {
+  if (!out) return fail(SALP_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  int words = 0;
+  int rc = check_robot_policy_desc(h, desc, &words);
+  if (rc != SALP_OK) return rc;
+  if (!weights) return fail(SALP_ERR_INVALID, "weights is NULL");
+  if (flags & ~1u) return fail(SALP_ERR_INVALID, "unknown flag bits");
+  DeviceScope dev_scope;
+  HIP_TRY(dev_scope.enter(h->device));
+  salp_robot_policy* pol = new (std::nothrow) salp_robot_policy();     // value-initialised: every field zero
+  if (!pol) return fail(SALP_ERR_OOM, "host allocation failed");
+  pol->h = h; pol->d = *desc; pol->device = h->device; pol->words = words;
+  std::vector<int32_t> map;     // word k of a policy in the device block <- public word map[k]: salp_policy.h
+  pol->stride = policy_block_map(ROBOT_POLICY_OBS, ROBOT_POLICY_ACT, *desc, false, map);
+  const size_t block_b = ((size_t)PH_WORDS + (size_t)desc->n_policies * pol->stride) * sizeof(float);
+  const size_t pub_b = (size_t)desc->n_policies * words * sizeof(float), map_b = map.size() * sizeof(int32_t);
+  hipError_t e = hipMalloc((void**)&pol->block, block_b);
+  if (e == hipSuccess) e = hipMalloc((void**)&pol->pub, pub_b);
+  if (e == hipSuccess) e = hipMalloc((void**)&pol->map, map_b);
+  if (e == hipSuccess) e = hipMemcpy(pol->map, map.data(), map_b, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    int32_t hd[PH_WORDS];
+    policy_header(*desc, pol->stride, h->n, false, hd);
+    e = hipMemcpy(pol->block, hd, sizeof(hd), hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) {
+    const std::string m = std::string("hipMalloc/hipMemcpy(policy): ") + hipGetErrorString(e);
+    salp_robot_policy_destroy(pol);
+    return fail(e == hipErrorOutOfMemory ? SALP_ERR_OOM : SALP_ERR_HIP, m);
+  }
+  rc = robot_policy_upload(pol, weights, flags, (hipStream_t)stream);
+  if (rc != SALP_OK) { const std::string m = g_err; salp_robot_policy_destroy(pol); g_err = m; return rc; }
+  *out = pol;
+  return SALP_OK;
+}
+
+int salp_robot_policy_update(salp_robot_policy_t* pol, const float* weights, uint32_t flags, void* stream) {
+  if (!pol || !weights) return fail(SALP_ERR_INVALID, "policy / weights is NULL");
+  if (flags & ~1u) return fail(SALP_ERR_INVALID, "unknown flag bits");
+  DeviceScope dev_scope;
+  HIP_TRY(dev_scope.enter(pol->device));
+  return robot_policy_upload(pol, weights, flags, (hipStream_t)stream);
+}
+
+int salp_robot_vec_rollout_policy(salp_robot_vec_t* h, const salp_robot_policy_t* pol, int32_t horizon, float* obs,
+                                  float* reward, uint8_t* terminated, uint8_t* truncated, float* final_obs,
+                                  int32_t* inner_steps, float* act_out, uint32_t flags, void* stream) {
+  if (!h || !pol) return fail(SALP_ERR_INVALID, "handle / policy is NULL");
+  if (pol->h != h) return fail(SALP_ERR_INVALID, "the policy belongs to another handle");
+  // (the descriptor passed check_policy_desc at create with this handle: one policy per wavefront holds)
+  const int rc = robot_rollout_impl<kActPolicy>(h, pol->block, horizon, obs, reward, terminated, truncated, final_obs, inner_steps,
+                                                act_out, flags, stream);
+  if (rc == SALP_OK) pol->last_stream = (hipStream_t)stream;
+  return rc;
 }
 
 int salp_robot_vec_get_state(salp_robot_vec_t* h, double* state, uint32_t flags, void* stream) {

@@ -1,8 +1,10 @@
 // salp_robot_kernels.h — all device code of the robot library, included by salp_robot.hip alone, which launches it
 // (RobotParams, the constants and schedule_bin are salp_robot_params.h): the robot in
 // registers (Rb) with load / store / rest / reset / observe, the reset kernel, the three kernels of the cycle-length
-// schedule, the history sample store, the two step kernels (salp_robot_step_body.h), the trajectory kernel and the
-// math-probe kernel.  One breathing cycle itself is salp_robot_cycle_body.h.
+// schedule, the history sample store, the two step kernels (salp_robot_step_body.h), the trajectory kernel, the
+// multi-cycle rollout kernel and the math-probe kernel.  One breathing cycle itself is salp_robot_cycle_body.h, made of
+// the pieces salp_robot_cycle_control.h / _consts.h / _start.h and salp_robot_euler_step.h, which the rollout kernel
+// includes one by one.
 //
 // One env step is one whole breathing cycle: up to ~1450 explicit-Euler steps of dt = 0.01 s, each a
 // rigid-body update with diagonal mass / inertia, quadratic + linear drag, a jet force during the
@@ -25,6 +27,7 @@
 #include "salp_robot_params.h"   // RobotParams, kPi, kMaxCycleTime, kSchedBins, the action scales and rates, schedule_bin
 #include "salp_philox.h"         // philox4x32_10, u53
 #include "salp_fp64_math.h"      // sincos_small, sincos_euler, advance_euler_sincos, rcp_nr, sqrt_nr
+#include "salp_robot_policy.h"   // robot_policy_eval and the policy block's header words (salp_policy.h)
 
 namespace {
 
@@ -326,6 +329,172 @@ void salp_robot_trajectory_kernel(RobotParams P0, RobotTrajectory J) {
     const double c = (double)J.cycles;
     m[0] = m[0] / c; m[1] = m[1] / c; m[2] = m[2] / c; m[4] = m[4] / c;
   }
+}
+
+// ---- multi-cycle rollout (salp_robot_vec_rollout, salp_robot_vec_rollout_policy) -----------------------
+// H env steps — H breathing cycles per robot — in one launch, env i on lane i, the robot in registers throughout; the
+// actions are read (kActRead) or computed by the in-kernel MLP policy from the row the step before wrote (kActPolicy,
+// salp_robot_policy.h).  ONE loop over Euler iterations serves the whole launch.  Every lane carries its own step index
+// t, its cycle (cycle_time, total and what the cycle pieces leave) and whether a cycle is in progress; a lane whose cycle
+// is over and whose t is below H is DUE.  At a service point the due lanes, under EXEC masking, finish env step t
+// (salp_robot_step_finish.h / _outputs.h: reward, flags, final_obs, autoreset, the stores of row t), advance t and, if
+// t < H, take their next action and run the cycle's opening (salp_robot_cycle_control.h / _start.h).  A service point
+// happens when no lane of the wavefront has an Euler step left, and on every M-th iteration on which some lane is due;
+// M = 0 means never, which is the synchronised form: every lane waits for the slowest one of its wavefront, cycle by cycle,
+// as a loop of salp_robot_step_kernel launches does.  With M > 0 a lane starts its next cycle at most M iterations after
+// its own cycle ended, so a wavefront lasts about as long as its longest SUM of cycle lengths, not the sum of the longest
+// cycles.  Service is batched because it is dear: the opening alone is several hundred fp64 instructions and a 64 x 64
+// policy 4.7 k fmac, executed for however few lanes are due (DESIGN.md §8f-4 has the measured choice of M).
+// Finished lanes (t == H) and padding lanes neither step nor wait.  The loop ends when no lane has t < H; it also carries the
+// iteration bound rollout_max_iters (salp_robot_params.h), which no input can reach.  The state rows are written once, at the end.
+struct RobotRollout {
+  const float* act;        // kActRead: actions [H][n][3];  kActPolicy: the policy's device block (salp_policy.h)
+  float* obs;              // [H][n][6]
+  float* reward;           // [H][n]
+  uint8_t* terminated;     // [H][n]
+  uint8_t* truncated;      // [H][n]
+  float* final_obs;        // [H][n][6], rows of finished envs only
+  int32_t* inner_steps;    // [H][n]
+  float* act_out;          // [H][n][3], kActPolicy only           (every output nullable)
+  int64_t max_iters;
+  int32_t horizon;
+};
+enum { kActRead = 0, kActPolicy = 1 };
+
+// what the opening of a cycle leaves for the Euler steps of that cycle (the names of the cycle pieces)
+struct RobotCycle {
+  double dir[3], contraction, refill_time, t_jet_end, t_coast_end, total, cycle_time;
+  double mass, inv_m, kd, ktc, ax, I0, I1, I2, iI0, iI1, iI2, sp, cp, st, ct, ss, cs;
+  int steps;
+  bool settled;
+};
+
+// a value that is the same in every lane, in scalar registers
+__device__ __forceinline__ double wave_uniform(double x) {
+  const uint64_t b = (uint64_t)__double_as_longlong(x);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32));
+  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
+template <int ACT, int M>
+__global__ __launch_bounds__(kRBlock) __attribute__((amdgpu_waves_per_eu(SALP_ROBOT_WAVES, SALP_ROBOT_WAVES)))
+void salp_robot_rollout_kernel(RobotParams P, RobotState S, RobotRollout J) {
+  static_assert(M >= 0 && (M & (M - 1)) == 0, "M is 0 (never) or a power of two");
+  constexpr bool kRecord = false;
+  const RobotHistory H = {};
+  const int64_t i0 = (int64_t)blockIdx.x * kRBlock + threadIdx.x;
+  const bool active = i0 < P.n;
+  const int64_t i = active ? i0 : (P.n - 1);
+  const uint64_t genv = P.env_base + (uint64_t)i;
+  const int64_t n = P.n;
+  const int32_t horizon = J.horizon;
+  Rb r;
+  load_robot(r, S, P, i);
+  [[maybe_unused]] uint32_t pol_off = 0;      // a wavefront never mixes policies: its envs lie in one group of PH_GROUP envs
+  if constexpr (ACT == kActPolicy) {
+    const int32_t* hd = reinterpret_cast<const int32_t*>(J.act);
+    pol_off = (uint32_t)(i / (int64_t)hd[PH_GROUP]) * (uint32_t)hd[PH_STRIDE];
+  }
+
+  // The lane's cycle, under the names salp_robot_euler_step.h reads; no cycle yet: nothing to step (cycle_time == total)
+  const double contract_rate = kContractRate, release_rate = kReleaseRate;
+  // The constants of the physical parameters are the same in every lane (P is the kernel argument): they are moved to
+  // scalar registers, where they cost no VGPR across the service code (as VGPRs they were spilled to scratch and read
+  // back inside the Euler step).
+  double uni[4];
+  {
+#include "salp_robot_cycle_consts.h"
+    uni[0] = dt; uni[1] = inv_dt; uni[2] = min_aspect; uni[3] = inv_aspect_span;
+  }
+  const double dt = wave_uniform(uni[0]), inv_dt = wave_uniform(uni[1]), min_aspect = wave_uniform(uni[2]),
+               inv_aspect_span = wave_uniform(uni[3]);
+  double dir[3] = {0.0, 0.0, 0.0};
+  double contraction = 0.0, refill_time = 0.0, t_jet_end = 0.0, t_coast_end = 0.0, total = 0.0, cycle_time = 0.0;
+  double mass = 0, inv_m = 0, kd = 0, ktc = 0, ax = 0, I0 = 0, I1 = 0, I2 = 0, iI0 = 0, iI1 = 0, iI2 = 0;
+  double sp = 0, cp = 1, st = 0, ct = 1, ss = 0, cs = 1;
+  int steps = 0;
+  bool settled = false;
+  // (named by the recording branch of the Euler step, which kRecord = false discards)
+  [[maybe_unused]] const bool rec = false;
+  [[maybe_unused]] const int64_t hj = 0;
+  [[maybe_unused]] int32_t n_samples = 0, until_sample = 0;
+  [[maybe_unused]] const float yaw_f = 0.f;
+
+  int32_t t = active ? 0 : horizon;     // padding lanes are finished from the start
+  bool running = false;                 // a cycle has been opened for env step t and that step is not finished yet
+  // One round per service point: the service code, then Euler iterations up to the next service point.  The Euler
+  // iterations form an inner loop of their own so that the register allocator ranks what they read above what only the
+  // service code reads (as one flat loop it reloaded two of the Euler step's operands from scratch on every iteration).
+  int64_t iter = 0;
+#pragma unroll 1
+  for (;;) {
+    {
+      const bool due = !(cycle_time < total) && t < horizon;
+      if (!__any(t < horizon)) break;
+      if (due) {
+        if (running) {     // env step t is over: due lanes are active lanes
+          const int64_t row = (int64_t)t * n;
+          float* const obs = J.obs ? J.obs + row * 6 : nullptr;
+          float* const reward = J.reward ? J.reward + row : nullptr;
+          uint8_t* const terminated = J.terminated ? J.terminated + row : nullptr;
+          uint8_t* const truncated = J.truncated ? J.truncated + row : nullptr;
+          float* const final_obs = J.final_obs ? J.final_obs + row * 6 : nullptr;
+          int32_t* const inner_steps = J.inner_steps ? J.inner_steps + row : nullptr;
+#include "salp_robot_step_finish.h"
+#include "salp_robot_step_outputs.h"
+          ++t;
+          running = false;
+        }
+        if (t < horizon) {
+          // the action of step t: of the row just written (the entry observation for t = 0), or read
+          float a[3];
+          if constexpr (ACT == kActPolicy) {
+            float x[6];
+            observe_robot(r, x);
+            robot_policy_eval<ROBOT_POLICY_OBS, ROBOT_POLICY_ACT>(J.act, pol_off, x, a);
+            if (J.act_out) {
+              float* ao = J.act_out + ((int64_t)t * n + i) * 3;
+              ao[0] = a[0]; ao[1] = a[1]; ao[2] = a[2];
+            }
+          } else {
+            const float* ai = J.act + ((int64_t)t * n + i) * 3;
+            a[0] = ai[0]; a[1] = ai[1]; a[2] = ai[2];
+          }
+          RobotCycle c;
+          {
+            // _rescale_action (:129-137) in fp64, as in salp_robot_step_body.h
+            const double contraction = (double)a[0] * kActContraction;
+            const double coast_time = (double)a[1] * kActCoast;
+            const double yaw = (double)a[2] * kActYaw;
+#include "salp_robot_cycle_control.h"
+#include "salp_robot_cycle_start.h"
+            c = {{dir[0], dir[1], dir[2]}, contraction, refill_time, t_jet_end, t_coast_end, total, cycle_time,
+                 mass, inv_m, kd, ktc, ax, I0, I1, I2, iI0, iI1, iI2, sp, cp, st, ct, ss, cs, steps, settled};
+          }
+          dir[0] = c.dir[0]; dir[1] = c.dir[1]; dir[2] = c.dir[2];
+          contraction = c.contraction; refill_time = c.refill_time; t_jet_end = c.t_jet_end; t_coast_end = c.t_coast_end;
+          total = c.total; cycle_time = c.cycle_time;
+          mass = c.mass; inv_m = c.inv_m; kd = c.kd; ktc = c.ktc; ax = c.ax; I0 = c.I0; I1 = c.I1; I2 = c.I2;
+          iI0 = c.iI0; iI1 = c.iI1; iI2 = c.iI2; sp = c.sp; cp = c.cp; st = c.st; ct = c.ct; ss = c.ss; cs = c.cs;
+          steps = c.steps; settled = c.settled;
+          running = true;
+        }
+      }
+    }
+    bool service;
+#pragma unroll 1
+    do {
+      if (cycle_time < total) {
+#include "salp_robot_euler_step.h"
+      }
+      ++iter;
+      service = !__any(cycle_time < total);
+      if constexpr (M > 0) service = service || ((iter & (int64_t)(M - 1)) == 0 && __any(!(cycle_time < total) && t < horizon));
+    } while (!service && iter < J.max_iters);
+    if (iter >= J.max_iters) break;
+  }
+  if (active) store_robot(r, S, P, i);
 }
 
 // ---- test support: the fp64 primitives on their own (salp_robot_math_probe, declared in salp_fp64_math.h) ----------

@@ -1,8 +1,8 @@
 // salp_robot_params.h — the parameters of a robot-simulator launch: the launch-parameter block RobotParams, the constants
 // of the cycle (action scales, contract / release rates, the cycle-length cut, the schedule's bins), the list of the
 // physical parameters a trajectory robot may have of its own (SALP_ROBOT_PHYS), and the host functions that derive a
-// RobotParams from a salp_robot_config_t and decide what salp_robot_vec_create, salp_robot_vec_step_history and
-// salp_robot_vec_trajectory refuse.
+// RobotParams from a salp_robot_config_t and decide what salp_robot_vec_create, salp_robot_vec_step_history,
+// salp_robot_vec_trajectory and the two rollout calls refuse (and the rollout kernel's service period and iteration bound).
 //
 // The header compiles in two ways, like salp_params.h and salp_fp64_math.h:
 //   * with hipcc: what salp_robot.hip includes, before salp_robot_kernels.h;
@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include "../../include/salp_robot.h"
+#include "../../include/salp_robot_rollout.h"   // SALP_ROBOT_MAX_ROLLOUT_CYCLES
 #include "../../include/salp_vec.h"   // SALP_OK, SALP_ERR_INVALID
 
 // An unnamed namespace, as in salp_host.h: the kernels of salp_robot_kernels.h live in one, and RobotParams is part of their names.
@@ -168,6 +169,37 @@ inline int check_trajectory_args(int64_t max_steps, int32_t cycles, uint32_t fla
   // the same refusal as the history calls: with such a dt one cycle of the kMaxCycleTime cut exceeds 2^24 Euler steps
   if (max_steps < 0) return refuse_robot_call(msg, msg_size, "dt is too small (more than 2^24 Euler steps per cycle)");
   return (int)SALP_OK;
+}
+
+// The rollout kernel's service period M (salp_robot_kernels.h): a lane whose cycle has ended waits at most M Euler
+// iterations of its wavefront for its next cycle; 0 = never, the synchronised form.  kRolloutPeriod is what the library
+// runs (the measured choice); the others are compiled for profiles/robot_rollout_perf.py and selected
+// with SALP_ROBOT_ROLLOUT_M at create.
+constexpr int kRolloutPeriods[] = {0, 32, 128, 512};
+constexpr int kRolloutPeriod = 128;
+
+// What salp_robot_vec_rollout and salp_robot_vec_rollout_policy refuse once they have a handle (max_steps).
+// has_source: act (or the policy) is not NULL; has_main_output: one of obs, reward, terminated, truncated is not NULL.
+inline int check_rollout_args(int64_t max_steps, int32_t horizon, uint32_t flags, bool has_source, bool has_main_output,
+                              char* msg, size_t msg_size) {
+  if (!has_source) return refuse_robot_call(msg, msg_size, "act / policy is NULL");
+  if (horizon < 1 || horizon > SALP_ROBOT_MAX_ROLLOUT_CYCLES) {
+    snprintf(msg, msg_size, "horizon must be in [1, %d]", (int)SALP_ROBOT_MAX_ROLLOUT_CYCLES);
+    return (int)SALP_ERR_INVALID;
+  }
+  if (flags & ~1u) return refuse_robot_call(msg, msg_size, "unknown flag bits");
+  if (!has_main_output) return refuse_robot_call(msg, msg_size, "one of obs, reward, terminated, truncated is required");
+  // the same refusal as the history and trajectory calls: the loop's iteration bound is counted in Euler steps
+  if (max_steps < 0) return refuse_robot_call(msg, msg_size, "dt is too small (more than 2^24 Euler steps per cycle)");
+  return (int)SALP_OK;
+}
+
+// The iteration bound of the rollout kernel's loop.  A lane's cycle takes at most max_steps iterations, and the lane
+// waits at most `period` iterations for the service point that ends it and opens the next one (period 0: the lanes of
+// a wavefront go cycle by cycle, each round at most max_steps iterations and one service point); horizon cycles and
+// the service point behind the last one, plus one iteration each for the rounds that run no Euler step.
+inline int64_t rollout_max_iters(int32_t horizon, int64_t max_steps, int period) {
+  return ((int64_t)horizon + 1) * (max_steps + (int64_t)period + 1);
 }
 
 // Bin of the cycle-length schedule for the Box action (a0, a1, .): the cycle's length as set_control will compute it,

@@ -9,6 +9,8 @@
 // optimised on its own and then again inside the kernel, and that moved the register allocation and the schedule
 // of salp_robot_step_kernel; included text keeps its instruction stream that of the kernel before recording
 // existed.
+// The end of the step (reward, flags, autoreset; the stores) is salp_robot_step_finish.h and salp_robot_step_outputs.h,
+// which salp_robot_rollout_kernel includes at its service points.
 // No include guard: included once per kernel.
   const int64_t i0 = (int64_t)blockIdx.x * kRBlock + threadIdx.x;
   const bool active = i0 < P.n;
@@ -28,38 +30,8 @@
     if (rec && H.len) H.len[hj] = n_samples;
   }
 
-  // _calculate_reward (:203-243) and termination (:171-185)
-  const double dx = r.pos[0] - r.target[0], dy = r.pos[1] - r.target[1];
-  const double dist = sqrt(dx * dx + dy * dy);
-  const double r_track = (-dist + r.prev_dist) * 100;
-  r.prev_dist = dist;
-  const double ex = -(dx / (dist + 1e-6)), ey = -(dy / (dist + 1e-6));
-  const double vn = sqrt(r.vw[0] * r.vw[0] + r.vw[1] * r.vw[1]);
-  const double r_heading = (r.vw[0] / (vn + 1e-6)) * ex + (r.vw[1] / (vn + 1e-6)) * ey;
-  double rew = r_track + 0.5 * r_heading;
-  bool term = false, trunc = false;
-  if (dist < 0.01) { term = true; rew += 10.0; }
-  else if (dist > 5.0) { trunc = true; rew -= 5.0; }
-  if (r.cycle >= P.max_cycles) trunc = true;
-
-  float o[6];
-  if (term || trunc) {
-    if (final_obs && active) {
-      observe_robot(r, o);
-#pragma unroll
-      for (int k = 0; k < 6; ++k) final_obs[i * 6 + k] = o[k];
-    }
-    reset_robot(r, P, genv);
-  }
+#include "salp_robot_step_finish.h"
   if (active) {
-    observe_robot(r, o);
-    if (obs) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) obs[i * 6 + k] = o[k];
-    }
-    if (reward) reward[i] = (float)rew;
-    if (terminated) terminated[i] = term ? 1 : 0;
-    if (truncated) truncated[i] = trunc ? 1 : 0;
-    if (inner_steps) inner_steps[i] = steps;
+#include "salp_robot_step_outputs.h"
     store_robot(r, S, P, i);
   }

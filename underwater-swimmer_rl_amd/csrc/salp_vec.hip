@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "salp_host.h"
+#include "salp_policy_upload.h"
 #include "salp_rollout_kernel.h"
 #include "salp_service_kernels.h"
 
@@ -178,18 +179,9 @@ int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, Rollout
 }
 
 int policy_upload(salp_policy* pol, const float* weights, uint32_t flags, hipStream_t st) {
-  const size_t pub_b = (size_t)pol->d.n_policies * pol->words * sizeof(float);
   pol->last_stream = st;
-  const float* src = weights;
-  if (!(flags & SALP_DEVICE_PTRS)) {
-    HIP_TRY(hipMemcpyAsync(pol->pub, weights, pub_b, hipMemcpyHostToDevice, st));
-    src = pol->pub;
-  }
-  const int64_t total = (int64_t)pol->d.n_policies * pol->stride;
-  const int rc = launch_1d(salp_policy_relayout_kernel, total, kBlock, st, pol->block, src, (const int32_t*)pol->map, pol->stride,
-                           pol->words, total);
-  if (rc != SALP_OK) return rc;
-  if (!(flags & SALP_DEVICE_PTRS)) HIP_TRY(hipStreamSynchronize(st));
+  const PolicyBlock b = {pol->block, pol->pub, pol->map, pol->d.n_policies, pol->words, pol->stride};
+  HIP_TRY(policy_block_upload(b, weights, (flags & SALP_DEVICE_PTRS) != 0, st));
   return SALP_OK;
 }
 
@@ -203,6 +195,23 @@ int check_record_args(uint32_t flags, uint32_t allowed, const char* bits_msg, co
 const char* const kEvalFlagBits = "unknown flag bits (SALP_DEVICE_PTRS and SALP_EVAL_ACCUMULATE are defined)";
 
 }  // namespace
+
+// salp_policy_upload.h: shared with salp_robot.hip
+hipError_t salp::policy_block_upload(const PolicyBlock& b, const float* weights, bool device_ptrs, hipStream_t st) {
+  const float* src = weights;
+  if (!device_ptrs) {
+    const size_t pub_b = (size_t)b.n_policies * b.words * sizeof(float);
+    const hipError_t e = hipMemcpyAsync(b.pub, weights, pub_b, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    src = b.pub;
+  }
+  const int64_t total = (int64_t)b.n_policies * b.stride;
+  hipLaunchKernelGGL(salp_policy_relayout_kernel, dim3(blocks_for(total, kBlock)), dim3(kBlock), 0, st, b.block, src, b.map, b.stride,
+                     b.words, total);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess || device_ptrs) return e;
+  return hipStreamSynchronize(st);
+}
 
 extern "C" {
 

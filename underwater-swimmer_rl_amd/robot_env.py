@@ -9,6 +9,8 @@ One `step` is one whole breathing cycle of every robot (Robot.set_control + step
 robot.py:335-358, 422-445): `info["inner_steps"]` is the number of Euler steps each robot took.
 `env.record_history(slice(a, b), stride)` adds the per-Euler-step history of those robots to `info`
 (`cycle_history`, `cycle_history_len`, `cycle_history_envs`; `env.history_of(i)` in the reference's shape).
+`env.rollout(actions_HN3)` runs H cycles of every robot in one launch, and `env.rollout_policy(policy, H)` does so with
+every action computed in the kernel by a small MLP policy (`policy.MLPPolicy`, 6 observations -> 3 action components).
 Same conventions as SalpVectorEnv: device tensors, same-step autoreset with `final_observation`,
 no CPU fallback."""
 from __future__ import annotations
@@ -63,6 +65,9 @@ class SalpRobotVectorEnv(ArrayBackend):
         self._rew, self._term, self._trunc = self._empty((n,), np.float32), self._empty((n,), np.uint8), self._empty((n,), np.uint8)
         self._inner = self._empty((n,), np.int32)
         self._hist = None      # (begin, count, stride, capacity, history, history_len) while record_history is on
+        self._bufs = {}        # rollout outputs by name, cached per H
+        self._policies = []    # RobotPolicyHandle objects made on this env
+        self._policy_cache = {}   # id(policy object) -> (policy object, its handle)
 
     _p = staticmethod(_capi.address)
 
@@ -140,6 +145,84 @@ class SalpRobotVectorEnv(ArrayBackend):
             info["cycle_history_envs"] = (self._hist[0], self._hist[1])
         return self._obs, self._rew, term, trunc, info
 
+    # ------------------------------------------------------------------ rollouts: H cycles per robot in one launch
+    def _buf(self, name, shape, dtype):
+        """The env-owned rollout buffer of that name, made again when its shape changes (H)."""
+        b = self._bufs.get(name)
+        if b is None or tuple(b.shape) != tuple(shape):
+            b = self._bufs[name] = self._empty(shape, dtype)
+        return b
+
+    def _rollout_outputs(self, H):
+        n = self.num_envs
+        return (self._buf("obs", (H, n, 6), np.float32), self._buf("reward", (H, n), np.float32),
+                self._buf("terminated", (H, n), np.uint8), self._buf("truncated", (H, n), np.uint8),
+                self._buf("final_obs", (H, n, 6), np.float32), self._buf("inner_steps", (H, n), np.int32))
+
+    def _rollout_result(self, obs, rew, term, trunc, fin, inner, **extra):
+        term, trunc = self._bool_view(term), self._bool_view(trunc)
+        return dict(obs=obs, reward=rew, terminated=term, truncated=trunc, final_observation=fin,
+                    _final_observation=term | trunc, inner_steps=inner, **extra)
+
+    def rollout(self, actions) -> dict:
+        """`H` env steps — H breathing cycles of every robot — in ONE kernel launch (salp_robot_vec_rollout): `actions`
+        [H, N, 3] in the Box.  Returns a dict of time-major blocks, step t holding what `step(actions[t])` returns:
+        `obs` [H, N, 6], `reward` [H, N], `terminated`, `truncated` (bool [H, N]), `final_observation` [H, N, 6] (rows
+        where `_final_observation` is set; the others keep what the buffer held), `_final_observation`, `inner_steps`
+        int32 [H, N].  The blocks are the env's own buffers, cached per H and overwritten by the next rollout.  In the
+        kernel a robot begins its next cycle when its own cycle has ended; results equal the loop of `step` calls up to
+        the coupling of a wavefront's lanes (include/salp_robot_rollout.h, < 1e-12 relative per cycle)."""
+        H = int(actions.shape[0]) if hasattr(actions, "shape") else len(actions)
+        a = self._actions_in(actions, (H, self.num_envs, 3))
+        out = self._rollout_outputs(H)
+        self._call("salp_robot_vec_rollout", a, H, *out, what="rollout")
+        return self._rollout_result(*out)
+
+    def make_policy(self, policy, weights=None) -> "RobotPolicyHandle":
+        """An in-kernel policy of this env for `rollout_policy`: a `policy.MLPPolicy` with obs_dim 6 and act_dim 3, one
+        policy or a population (P policies share the envs in runs of N / P, whole wavefronts each).
+        `MLPPolicy.from_actor(actor)` of a `sac.Actor` built with this env's Box carries the right scale and shift.
+        `handle.update(w)` takes new weights of the same shape in the public layout (`MLPPolicy.pack()`); with a device
+        tensor it is stream-ordered and allocates nothing."""
+        if getattr(policy, "gaussian", False):
+            raise ValueError("the robot rollout runs deterministic policies only (pass policy.mean_policy())")
+        if (policy.obs_dim, policy.act_dim) != (self.obs_dim, self.act_dim):
+            raise ValueError(f"the policy maps {policy.obs_dim} -> {policy.act_dim}, this env {self.obs_dim} -> {self.act_dim}")
+        policy.check_envs(self.num_envs)
+        p = ctypes.c_void_p()
+        w = policy.pack() if weights is None else weights
+        _capi.call(self.L, "salp_robot_policy_create", self._h, ctypes.byref(policy.desc()), w,
+                   0 if weights is None else self._flags, self._stream, ctypes.byref(p), what="make_policy")
+        h = RobotPolicyHandle(self, p, policy.n_policies, int(policy.words))
+        self._policies.append(h)
+        return h
+
+    def _policy_handle(self, policy):
+        """`policy` if it is a handle, else the handle made for that policy object at its first use (kept until close())."""
+        if isinstance(policy, RobotPolicyHandle):
+            return policy
+        if id(policy) not in self._policy_cache:
+            self._policy_cache[id(policy)] = (policy, self.make_policy(policy))
+        return self._policy_cache[id(policy)][1]
+
+    def rollout_policy(self, policy, horizon: int, want_actions: bool = True) -> dict:
+        """`horizon` closed-loop env steps in ONE kernel launch (salp_robot_vec_rollout_policy): every action is `policy`
+        applied to the observation row before it — the first one to the env's current observation (`observe()`), the
+        action of step t + 1 to `obs[t]`.  `policy`: a handle of `make_policy`, or an `MLPPolicy` (a handle is then made
+        and kept for the next call with the same object).  Returns the dict of `rollout` plus `actions` [H, N, 3] (None
+        without `want_actions`).
+        Which form is faster (measured on an MI355X, H = 16, DESIGN.md §8f-4 "Rollouts"): at 4096 envs, where every
+        wavefront has a SIMD to itself and `step` waits for the slowest env of each launch, the rollout takes 0.53-1.02
+        of the time of the loop of actor forward + `step` (the row above 1 lies inside its 7 % spread; open loop
+        0.82-0.89); at 262144 envs the loop of `step` calls is the faster form, by 1.5-2.4x: `step` walks the envs
+        longest cycle first from 32768 envs on and the rollout does not."""
+        handle = self._policy_handle(policy)
+        H = int(horizon)
+        out = self._rollout_outputs(H)
+        aout = self._buf("actions", (H, self.num_envs, 3), np.float32) if want_actions else None
+        self._call("salp_robot_vec_rollout_policy", handle._p, H, *out, aout, what="rollout_policy")
+        return self._rollout_result(*out, actions=aout)
+
     def get_state(self) -> np.ndarray:
         """fp64 [27, N] snapshot, rows R_* (include/salp_robot.h)."""
         s = np.empty((R_COUNT, self.num_envs), np.float64)
@@ -150,8 +233,39 @@ class SalpRobotVectorEnv(ArrayBackend):
 
     def close(self):
         if self._h:
+            for p in list(self._policies):     # a policy goes before its handle
+                p.close()
+            self._policy_cache = {}
             self.L.salp_robot_vec_destroy(self._h)
             self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RobotPolicyHandle:
+    """One salp_robot_policy_t: a policy block on an env's device (SalpRobotVectorEnv.make_policy)."""
+
+    def __init__(self, env: SalpRobotVectorEnv, p, n_policies: int, words: int):
+        self.env, self._p, self.n_policies, self.words = env, p, int(n_policies), int(words)
+
+    def update(self, weights, flags=None, stream=None):
+        """salp_robot_policy_update: float32 [P, words] in the public layout — a numpy array (flags 0), or a device tensor
+        (SALP_DEVICE_PTRS: stream-ordered on `stream`, default the current one, no allocation)."""
+        if flags is None:
+            flags = _capi.SALP_DEVICE_PTRS if hasattr(weights, "data_ptr") else 0
+        _capi.call(self.env.L, "salp_robot_policy_update", self._p, weights, flags,
+                   self.env._stream if stream is None else stream, what="policy update")
+
+    def close(self):
+        if getattr(self, "_p", None):
+            self.env.L.salp_robot_policy_destroy(self._p)
+            self._p = ctypes.c_void_p()
+            if self in self.env._policies:
+                self.env._policies.remove(self)
 
     def __del__(self):
         try:
