@@ -2,6 +2,7 @@
 """Multi-cycle robot rollouts (salp_robot_vec_rollout / salp_robot_vec_rollout_policy) against the host loop they replace,
 and the rollout kernel's service period M (csrc/salp_robot_kernels.h).  On the GPU box.
     python profiles/robot_rollout_perf.py [--envs 4096,262144] [--horizon 16] [--rounds 5] [--window 0.5] [--out FILE]
+    python profiles/robot_rollout_perf.py --sampled [--envs 4096] ...      the sampled rollout against its deterministic twin
 
 Rows: env count x action mix (Box-wide: coast 0-10 s; short: coast <= 1 s) x loop (open: recorded actions; closed: a linear
 and a 64 x 64 tanh policy).  Forms of a row, each on an env of its own (same seed):
@@ -14,7 +15,17 @@ form is warmed up first; the forms of a row are ALTERNATED inside each of `--rou
 over the rounds and the spread (max - min) / median of each form's identical repeats.  Closed-loop envs are reset before every
 window so that every form starts its episodes from rest; the policies' output layers are scaled up so that their actions
 spread over the Box (the mean and the largest cycle length of a row are printed).  M is read by the library at create
-(SALP_ROBOT_ROLLOUT_M), which is how one process holds all four."""
+(SALP_ROBOT_ROLLOUT_M), which is how one process holds all four.
+
+--sampled: salp_robot_vec_rollout_policy_sampled against salp_robot_vec_rollout_policy at the library's default M, same
+method (alternated rounds, envs reset before every window).  Forms of a row, each on an env of its own (same seed), all
+with `want_actions=False`:
+    mean              the deterministic rollout on the Gaussian policy's handle
+    sampled, sd -> 0  the sampled rollout with every log-std bias at -25 (clamped to -20: a standard deviation of 2e-9), so
+                      that the actions, the cycle lengths and the simulator's work are the mean run's and the difference is
+                      what sampling itself costs: two Philox blocks, three Box-Muller draws, the log-std head, the
+                      log-probability and the logp store
+    sampled, ls = -1  log-std biases of -1: other actions, so other cycle lengths (printed) — what a learner would run"""
 import argparse
 import json
 import os
@@ -83,6 +94,48 @@ def measure(forms, rounds, window, before=None):
     return {name: (float(np.median(v)), float((max(v) - min(v)) / np.median(v)), calls[name]) for name, v in samples.items()}
 
 
+def sampled_rows(args):
+    """The rows of --sampled (see the top of the file)."""
+    import torch
+    from underwater_swimmer_rl_amd.policy import GaussianPolicy
+    H, rows = args.horizon, []
+    for n in (int(x) for x in args.envs.split(",")):
+        envs = {k: make_env(n) for k in ("mean", "sampled, sd -> 0", "sampled, ls = -1")}
+        for mix, coast_hi in MIXES.items():
+            for label, hidden in (("linear", ()), ("64x64", (64, 64))):
+                actor = actor_for(hidden, coast_hi, 5, envs["mean"].reset()[0])
+                handles, forms = {}, {}
+                for k, env in envs.items():
+                    with torch.no_grad():
+                        actor.log_std.weight.zero_()
+                        actor.log_std.bias.fill_(-1.0 if k.endswith("-1") else -25.0)
+                    handles[k] = env.make_policy(GaussianPolicy.from_actor(actor))
+                    forms[k] = (lambda e, h, s: lambda: e.rollout_policy(h, H, want_actions=False, sample=s))(env, handles[k], k != "mean")
+                cycles = {}
+                for k, env in envs.items():
+                    env.reset()
+                    inner = env.rollout_policy(handles[k], H, sample=k != "mean")["inner_steps"].float()
+                    cycles[k] = (float(inner.mean()), int(inner.max()))
+                row = dict(envs=n, mix=mix, loop=f"closed {label}", horizon=H, cycle_steps=cycles,
+                           forms=measure(forms, args.rounds, args.window, before=lambda name: envs[name].reset()))
+                f = row["forms"]
+                row["sampled_over_mean"] = f["sampled, sd -> 0"][0] / f["mean"][0]
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+                for h in handles.values():
+                    h.close()
+        for e in envs.values():
+            e.close()
+    print("\n| envs | mix | policy | mean | sampled, sd -> 0 | ratio | sampled, ls = -1 (mean / max Euler steps per cycle) | largest spread |")
+    print("|---|---|---|---|---|---|---|---|")
+    for r in rows:
+        f, c = r["forms"], r["cycle_steps"]["sampled, ls = -1"]
+        print(f"| {r['envs']} | {r['mix']} | {r['loop']} | {f['mean'][0]:.2f} | {f['sampled, sd -> 0'][0]:.2f} | {r['sampled_over_mean']:.3f} | "
+              f"{f['sampled, ls = -1'][0]:.2f} ({c[0]:.0f} / {c[1]}) | {100 * max(v[1] for v in f.values()):.1f} % |")
+    print("(ms per call of H = %d env steps; median of %d alternated rounds)" % (H, args.rounds))
+    return rows
+
+
 def main():
     import torch
     from underwater_swimmer_rl_amd.policy import MLPPolicy
@@ -92,10 +145,13 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sampled", action="store_true", help="the sampled rollout against its deterministic twin")
     args = ap.parse_args()
     H = args.horizon
     rows = []
-    for n in (int(x) for x in args.envs.split(",")):
+    if args.sampled:
+        rows = sampled_rows(args)
+    for n in (() if args.sampled else (int(x) for x in args.envs.split(","))):
         base = make_env(n)
         rolls = {m: make_env(n, m) for m in PERIODS}
         for mix, coast_hi in MIXES.items():
@@ -140,14 +196,16 @@ def main():
                     h.close()
         for e in (base, *rolls.values()):
             e.close()
-    print("\n| envs | mix | loop | mean / max Euler steps per cycle | " + " | ".join(["step loop"] + [f"M = {m}" for m in PERIODS]) + " | largest spread |")
-    print("|---|---|---|---|" + "---|" * (len(PERIODS) + 2))
-    for r in rows:
+    if not args.sampled:
+        print("\n| envs | mix | loop | mean / max Euler steps per cycle | " + " | ".join(["step loop"] + [f"M = {m}" for m in PERIODS]) + " | largest spread |")
+        print("|---|---|---|---|" + "---|" * (len(PERIODS) + 2))
+    for r in ([] if args.sampled else rows):
         f = r["forms"]
         cells = [f"{f[k][0]:.2f}" for k in ["step loop"] + [f"M={m}" for m in PERIODS]]
         print(f"| {r['envs']} | {r['mix']} | {r['loop']} | {r['mean_cycle_steps']:.0f} / {r['max_cycle_steps']} | " + " | ".join(cells) +
               f" | {100 * max(v[1] for v in f.values()):.1f} % |")
-    print("(ms per call of H = %d env steps; median of %d alternated rounds)" % (H, args.rounds))
+    if not args.sampled:
+        print("(ms per call of H = %d env steps; median of %d alternated rounds)" % (H, args.rounds))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as fh:

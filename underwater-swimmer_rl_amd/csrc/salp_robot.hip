@@ -1,4 +1,4 @@
-// salp_robot.hip — the C ABI of include/salp_robot.h and include/salp_robot_rollout.h, the batched HEAD simulator for gfx950: the
+// salp_robot.hip — the C ABI of include/salp_robot.h, include/salp_robot_rollout.h and include/salp_robot_sampled.h, the batched HEAD simulator for gfx950: the
 // reference's `Robot.step_through_cycle` (src/salp/environments/robot.py) under `SalpRobotEnv.step/reset`
 // (src/salp/environments/salp_robot_env.py), one robot per lane.  Host code only: the handle and the entry points.
 //   salp_robot_kernels.h   every kernel this file launches (and the notes on how the simulator is laid out on the GPU)
@@ -17,6 +17,7 @@
 
 #include "../../include/salp_robot.h"
 #include "../../include/salp_robot_rollout.h"
+#include "../../include/salp_robot_sampled.h"
 #include "salp_robot_params.h"
 #include "salp_robot_kernels.h"
 #include "salp_host.h"
@@ -47,7 +48,8 @@ struct salp_robot_policy {
   float* block;              // device: header + P policies, what the kernel reads
   float* pub;                // device: staging of the public layout [P][words] (host-pointer create / update)
   int32_t* map;              // device: word k of a policy in the block <- public word map[k] (-1: zero)
-  mutable hipStream_t last_stream;   // the stream of its most recent upload or rollout: what destroy waits for
+  int gaussian;              // salp_robot_policy_create_gaussian: a log-std head behind the mean head, a noise step in the header
+  mutable hipStream_t last_stream;   // the stream of its most recent upload, rollout or noise-step write: what destroy waits for
 };
 
 // Below this many envs every wavefront has an execution unit to itself and the launch lasts as long as
@@ -73,12 +75,14 @@ static int launch_robot_step(salp_robot_vec* h, const float* act, float* obs, fl
                    inner_steps, order);
 }
 
-// salp_robot_vec_rollout (ACT = kActRead, source = the actions) and salp_robot_vec_rollout_policy (kActPolicy, source = the
-// policy's device block, which is on the device whatever `flags` says); everything is checked before anything is launched.
+// salp_robot_vec_rollout (ACT = kActRead, source = the actions), salp_robot_vec_rollout_policy (kActPolicy, source = the
+// policy's device block, which is on the device whatever `flags` says) and salp_robot_vec_rollout_policy_sampled
+// (kActPolicySampled, the same source; behind the rollout kernel the block's noise step goes on by the horizon, in the
+// host-pointer form before the copies out); everything is checked before anything is launched.
 template <int ACT>
 static int robot_rollout_impl(salp_robot_vec_t* h, const float* source, int32_t horizon, float* obs, float* reward,
                               uint8_t* terminated, uint8_t* truncated, float* final_obs, int32_t* inner_steps, float* act_out,
-                              uint32_t flags, void* stream) {
+                              uint32_t flags, void* stream, float* logp_out = nullptr) {
   char why[160];
   if (const int bad = check_rollout_args(h->max_steps, horizon, flags, source != nullptr,
                                          obs || reward || terminated || truncated, why, sizeof(why)))
@@ -90,17 +94,23 @@ static int robot_rollout_impl(salp_robot_vec_t* h, const float* source, int32_t 
   const size_t n = (size_t)h->n, HN = (size_t)horizon * n;
   HostStream s[] = {stream_in(ACT == kActRead ? source : nullptr, HN * 3), stream_out(obs, HN * 6), stream_out(reward, HN),
                     stream_out(terminated, HN), stream_out(truncated, HN), stream_out(final_obs, HN * 6, true),
-                    stream_out(inner_steps, HN), stream_out(act_out, HN * 3)};
-  return staged(h->stage, f.st, flags & 1u, s, [&] {
-    J.act = ACT == kActRead ? s[0].as<const float>() : source;
-    J.obs = s[1].as<float>(); J.reward = s[2].as<float>(); J.terminated = s[3].as<uint8_t>(); J.truncated = s[4].as<uint8_t>();
-    J.final_obs = s[5].as<float>(); J.inner_steps = s[6].as<int32_t>(); J.act_out = s[7].as<float>();
+                    stream_out(inner_steps, HN), stream_out(act_out, HN * 3), stream_out(logp_out, HN)};
+  const auto launch = [&] {
     switch (h->period) {
       case 0: return launch_1d(salp_robot_rollout_kernel<ACT, 0>, h->n, kRBlock, f.st, h->P, h->S, J);
       case 32: return launch_1d(salp_robot_rollout_kernel<ACT, 32>, h->n, kRBlock, f.st, h->P, h->S, J);
       case 128: return launch_1d(salp_robot_rollout_kernel<ACT, 128>, h->n, kRBlock, f.st, h->P, h->S, J);
       default: return launch_1d(salp_robot_rollout_kernel<ACT, 512>, h->n, kRBlock, f.st, h->P, h->S, J);
     }
+  };
+  return staged(h->stage, f.st, flags & 1u, s, [&] {
+    J.act = ACT == kActRead ? s[0].as<const float>() : source;
+    J.obs = s[1].as<float>(); J.reward = s[2].as<float>(); J.terminated = s[3].as<uint8_t>(); J.truncated = s[4].as<uint8_t>();
+    J.final_obs = s[5].as<float>(); J.inner_steps = s[6].as<int32_t>(); J.act_out = s[7].as<float>();
+    J.logp_out = s[8].as<float>();
+    const int rc = launch();
+    if (ACT != kActPolicySampled || rc != SALP_OK) return rc;
+    return launch_1d(salp_robot_policy_noise_kernel, 1, 1, f.st, const_cast<float*>(source), (uint64_t)horizon, (uint64_t)0, 0);
   });
 }
 
@@ -269,10 +279,10 @@ int salp_robot_vec_rollout(salp_robot_vec_t* h, const float* act, int32_t horizo
 
 // The descriptor's ranges for a robot handle (salp_policy.h; obs_dim 6, act_dim 3, and kmax = 3, which those ranges ask of
 // a snake handle).  On success *words = public words of one policy.
-static int check_robot_policy_desc(const salp_robot_vec_t* h, const salp_policy_desc_t* d, int* words) {
+static int check_robot_policy_desc(const salp_robot_vec_t* h, const salp_policy_desc_t* d, int* words, bool gaussian = false) {
   const char* why = "";
-  const int rc = h ? check_policy_desc(ROBOT_POLICY_OBS, ROBOT_POLICY_ACT, 3, h->n, d, false, words, &why)
-                   : check_policy_desc(0, 0, 0, 0, nullptr, false, words, &why);
+  const int rc = h ? check_policy_desc(ROBOT_POLICY_OBS, ROBOT_POLICY_ACT, 3, h->n, d, gaussian, words, &why)
+                   : check_policy_desc(0, 0, 0, 0, nullptr, gaussian, words, &why);
   return rc == SALP_OK ? rc : fail(rc, why);
 }
 
@@ -300,12 +310,13 @@ static int robot_policy_upload(salp_robot_policy* pol, const float* weights, uin
   return SALP_OK;
 }
 
-int salp_robot_policy_create(salp_robot_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags,
-                             void* stream, salp_robot_policy_t** out) {
+// salp_robot_policy_create (gaussian = false) and salp_robot_policy_create_gaussian
+static int robot_policy_create_impl(salp_robot_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags,
+                                    void* stream, salp_robot_policy_t** out, bool gaussian) {
   if (!out) return fail(SALP_ERR_INVALID, "out is NULL");
   *out = nullptr;
   int words = 0;
-  int rc = check_robot_policy_desc(h, desc, &words);
+  int rc = check_robot_policy_desc(h, desc, &words, gaussian);
   if (rc != SALP_OK) return rc;
   if (!weights) return fail(SALP_ERR_INVALID, "weights is NULL");
   if (flags & ~1u) return fail(SALP_ERR_INVALID, "unknown flag bits");
@@ -313,9 +324,9 @@ int salp_robot_policy_create(salp_robot_vec_t* h, const salp_policy_desc_t* desc
   HIP_TRY(dev_scope.enter(h->device));
   salp_robot_policy* pol = new (std::nothrow) salp_robot_policy();     // value-initialised: every field zero
   if (!pol) return fail(SALP_ERR_OOM, "host allocation failed");
-  pol->h = h; pol->d = *desc; pol->device = h->device; pol->words = words;
+  pol->h = h; pol->d = *desc; pol->device = h->device; pol->words = words; pol->gaussian = gaussian ? 1 : 0;
   std::vector<int32_t> map;     // word k of a policy in the device block <- public word map[k]: salp_policy.h
-  pol->stride = policy_block_map(ROBOT_POLICY_OBS, ROBOT_POLICY_ACT, *desc, false, map);
+  pol->stride = policy_block_map(ROBOT_POLICY_OBS, ROBOT_POLICY_ACT, *desc, gaussian, map);
   const size_t block_b = ((size_t)PH_WORDS + (size_t)desc->n_policies * pol->stride) * sizeof(float);
   const size_t pub_b = (size_t)desc->n_policies * words * sizeof(float), map_b = map.size() * sizeof(int32_t);
   hipError_t e = hipMalloc((void**)&pol->block, block_b);
@@ -324,7 +335,7 @@ int salp_robot_policy_create(salp_robot_vec_t* h, const salp_policy_desc_t* desc
   if (e == hipSuccess) e = hipMemcpy(pol->map, map.data(), map_b, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     int32_t hd[PH_WORDS];
-    policy_header(*desc, pol->stride, h->n, false, hd);
+    policy_header(*desc, pol->stride, h->n, gaussian, hd);
     e = hipMemcpy(pol->block, hd, sizeof(hd), hipMemcpyHostToDevice);
   }
   if (e != hipSuccess) {
@@ -335,6 +346,43 @@ int salp_robot_policy_create(salp_robot_vec_t* h, const salp_policy_desc_t* desc
   rc = robot_policy_upload(pol, weights, flags, (hipStream_t)stream);
   if (rc != SALP_OK) { const std::string m = g_err; salp_robot_policy_destroy(pol); g_err = m; return rc; }
   *out = pol;
+  return SALP_OK;
+}
+
+int salp_robot_policy_create(salp_robot_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags,
+                             void* stream, salp_robot_policy_t** out) {
+  return robot_policy_create_impl(h, desc, weights, flags, stream, out, false);
+}
+
+int salp_robot_policy_words_gaussian(const salp_robot_vec_t* h, const salp_policy_desc_t* desc) {
+  int words = 0;
+  const int rc = check_robot_policy_desc(h, desc, &words, true);
+  return rc != SALP_OK ? rc : words;
+}
+
+int salp_robot_policy_create_gaussian(salp_robot_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags,
+                                      void* stream, salp_robot_policy_t** out) {
+  return robot_policy_create_impl(h, desc, weights, flags, stream, out, true);
+}
+
+int salp_robot_policy_set_noise_step(salp_robot_policy_t* pol, uint64_t n, void* stream) {
+  if (!pol) return fail(SALP_ERR_INVALID, "policy is NULL");
+  if (!pol->gaussian) return fail(SALP_ERR_INVALID, "the policy is not Gaussian: it has no noise step");
+  DeviceScope dev_scope;
+  HIP_TRY(dev_scope.enter(pol->device));
+  pol->last_stream = (hipStream_t)stream;
+  return launch_1d(salp_robot_policy_noise_kernel, 1, 1, (hipStream_t)stream, pol->block, (uint64_t)0, n, 1);
+}
+
+int salp_robot_policy_noise_step(salp_robot_policy_t* pol, uint64_t* n) {
+  if (!pol || !n) return fail(SALP_ERR_INVALID, "policy / n is NULL");
+  if (!pol->gaussian) return fail(SALP_ERR_INVALID, "the policy is not Gaussian: it has no noise step");
+  DeviceScope dev_scope;
+  HIP_TRY(dev_scope.enter(pol->device));
+  HIP_TRY(hipStreamSynchronize(pol->last_stream));
+  uint32_t w[2] = {0u, 0u};
+  HIP_TRY(hipMemcpy(w, reinterpret_cast<const uint32_t*>(pol->block) + PH_NOISE, sizeof(w), hipMemcpyDeviceToHost));
+  *n = ((uint64_t)w[1] << 32) | w[0];
   return SALP_OK;
 }
 
@@ -354,6 +402,20 @@ int salp_robot_vec_rollout_policy(salp_robot_vec_t* h, const salp_robot_policy_t
   // (the descriptor passed check_policy_desc at create with this handle: one policy per wavefront holds)
   const int rc = robot_rollout_impl<kActPolicy>(h, pol->block, horizon, obs, reward, terminated, truncated, final_obs, inner_steps,
                                                 act_out, flags, stream);
+  if (rc == SALP_OK) pol->last_stream = (hipStream_t)stream;
+  return rc;
+}
+
+// The policy arrives const (the signature mirrors the deterministic twin's), yet the call advances its noise word in device
+// memory and writes its last_stream (`mutable`): include/salp_robot_sampled.h says so.
+int salp_robot_vec_rollout_policy_sampled(salp_robot_vec_t* h, const salp_robot_policy_t* pol, int32_t horizon, float* obs,
+                                          float* reward, uint8_t* terminated, uint8_t* truncated, float* final_obs,
+                                          int32_t* inner_steps, float* act_out, float* logp_out, uint32_t flags, void* stream) {
+  if (!h || !pol) return fail(SALP_ERR_INVALID, "handle / policy is NULL");
+  if (pol->h != h) return fail(SALP_ERR_INVALID, "the policy belongs to another handle");
+  if (!pol->gaussian) return fail(SALP_ERR_INVALID, "sampling needs a Gaussian policy (salp_robot_policy_create_gaussian)");
+  const int rc = robot_rollout_impl<kActPolicySampled>(h, pol->block, horizon, obs, reward, terminated, truncated, final_obs,
+                                                       inner_steps, act_out, flags, stream, logp_out);
   if (rc == SALP_OK) pol->last_stream = (hipStream_t)stream;
   return rc;
 }

@@ -2,9 +2,9 @@
 // (RobotParams, the constants and schedule_bin are salp_robot_params.h): the robot in
 // registers (Rb) with load / store / rest / reset / observe, the reset kernel, the three kernels of the cycle-length
 // schedule, the history sample store, the two step kernels (salp_robot_step_body.h), the trajectory kernel, the
-// multi-cycle rollout kernel and the math-probe kernel.  One breathing cycle itself is salp_robot_cycle_body.h, made of
-// the pieces salp_robot_cycle_control.h / _consts.h / _start.h and salp_robot_euler_step.h, which the rollout kernel
-// includes one by one.
+// multi-cycle rollout kernel, the policy's noise-step kernel and the math-probe kernel.  One breathing cycle itself is
+// salp_robot_cycle_body.h, made of the pieces salp_robot_cycle_control.h / _consts.h / _start.h and
+// salp_robot_euler_step.h, which the rollout kernel includes one by one.
 //
 // One env step is one whole breathing cycle: up to ~1450 explicit-Euler steps of dt = 0.01 s, each a
 // rigid-body update with diagonal mass / inertia, quadratic + linear drag, a jet force during the
@@ -331,10 +331,10 @@ void salp_robot_trajectory_kernel(RobotParams P0, RobotTrajectory J) {
   }
 }
 
-// ---- multi-cycle rollout (salp_robot_vec_rollout, salp_robot_vec_rollout_policy) -----------------------
+// ---- multi-cycle rollout (salp_robot_vec_rollout, salp_robot_vec_rollout_policy, _policy_sampled) ------
 // H env steps — H breathing cycles per robot — in one launch, env i on lane i, the robot in registers throughout; the
-// actions are read (kActRead) or computed by the in-kernel MLP policy from the row the step before wrote (kActPolicy,
-// salp_robot_policy.h).  ONE loop over Euler iterations serves the whole launch.  Every lane carries its own step index
+// actions are read (kActRead) or computed by the in-kernel MLP policy from the row the step before wrote (kActPolicy; or
+// sampled from its Gaussian form, kActPolicySampled; salp_robot_policy.h).  ONE loop over Euler iterations serves the whole launch.  Every lane carries its own step index
 // t, its cycle (cycle_time, total and what the cycle pieces leave) and whether a cycle is in progress; a lane whose cycle
 // is over and whose t is below H is DUE.  At a service point the due lanes, under EXEC masking, finish env step t
 // (salp_robot_step_finish.h / _outputs.h: reward, flags, final_obs, autoreset, the stores of row t), advance t and, if
@@ -355,11 +355,17 @@ struct RobotRollout {
   uint8_t* truncated;      // [H][n]
   float* final_obs;        // [H][n][6], rows of finished envs only
   int32_t* inner_steps;    // [H][n]
-  float* act_out;          // [H][n][3], kActPolicy only           (every output nullable)
+  float* act_out;          // [H][n][3], kActPolicy / kActPolicySampled only           (every output nullable)
   int64_t max_iters;
   int32_t horizon;
+  float* logp_out;         // [H][n], kActPolicySampled only
 };
-enum { kActRead = 0, kActPolicy = 1 };
+// kActPolicySampled (salp_robot_vec_rollout_policy_sampled, include/salp_robot_sampled.h): the closed loop with the
+// stochastic form of a Gaussian policy.  The policy's noise step n0 is read once at entry (wave-uniform); a lane served
+// for its own env step t draws the Philox blocks (genv, n0 + t, 3) and (genv, n0 + t, 4) — a function of (env, t) alone,
+// whichever iteration the lane is served on — and stores the sampled action and its log-probability for step t.
+enum { kActRead = 0, kActPolicy = 1, kActPolicySampled = 2 };
+enum { kRobotNoiseStream = 3 };     // fourth counter word of component 0 / 1's block; component 2's is one above
 
 // what the opening of a cycle leaves for the Euler steps of that cycle (the names of the cycle pieces)
 struct RobotCycle {
@@ -392,9 +398,20 @@ void salp_robot_rollout_kernel(RobotParams P, RobotState S, RobotRollout J) {
   Rb r;
   load_robot(r, S, P, i);
   [[maybe_unused]] uint32_t pol_off = 0;      // a wavefront never mixes policies: its envs lie in one group of PH_GROUP envs
-  if constexpr (ACT == kActPolicy) {
+  if constexpr (ACT == kActPolicy || ACT == kActPolicySampled) {
     const int32_t* hd = reinterpret_cast<const int32_t*>(J.act);
     pol_off = (uint32_t)(i / (int64_t)hd[PH_GROUP]) * (uint32_t)hd[PH_STRIDE];
+  }
+  [[maybe_unused]] uint32_t noise0 = 0u;      // kActPolicySampled: low word of the policy's noise step at entry (wave-uniform)
+  if constexpr (ACT == kActPolicySampled) {
+    // the two PH_NOISE words, scalar loads through the constant address space like the weights (salp_policy.h); only the
+    // low word enters the draw: n is the low 32 bits of n0 + t, and t < 2^31
+    const uint64_t adr = (uint64_t)(uintptr_t)J.act;
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)adr);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(adr >> 32));
+    pol_int* hd = (pol_int*)(uintptr_t)(((uint64_t)hi << 32) | lo);
+    const uint64_t n0 = ((uint64_t)(uint32_t)hd[PH_NOISE + 1] << 32) | (uint32_t)hd[PH_NOISE];
+    noise0 = (uint32_t)n0;
   }
 
   // The lane's cycle, under the names salp_robot_euler_step.h reads; no cycle yet: nothing to step (cycle_time == total)
@@ -457,6 +474,22 @@ void salp_robot_rollout_kernel(RobotParams P, RobotState S, RobotRollout J) {
               float* ao = J.act_out + ((int64_t)t * n + i) * 3;
               ao[0] = a[0]; ao[1] = a[1]; ao[2] = a[2];
             }
+          } else if constexpr (ACT == kActPolicySampled) {
+            float x[6];
+            observe_robot(r, x);
+            // the draws of (env, step t): components 0 and 1 from the block of stream word 3, component 2 from the first
+            // two words of the block of stream word 4 (include/salp_robot_sampled.h); the env's own counter is not consumed
+            const uint32_t nt = noise0 + (uint32_t)t;
+            const U4 w0 = philox4x32_10((uint32_t)genv, (uint32_t)(genv >> 32), nt, (uint32_t)kRobotNoiseStream, P.seed_lo, P.seed_hi);
+            const U4 w1 = philox4x32_10((uint32_t)genv, (uint32_t)(genv >> 32), nt, (uint32_t)kRobotNoiseStream + 1u, P.seed_lo, P.seed_hi);
+            const float z[3] = {policy_normal(w0.x, w0.y), policy_normal(w0.z, w0.w), policy_normal(w1.x, w1.y)};
+            float lp;
+            robot_policy_eval_sampled<ROBOT_POLICY_OBS, ROBOT_POLICY_ACT>(J.act, pol_off, x, z, a, lp);
+            if (J.act_out) {
+              float* ao = J.act_out + ((int64_t)t * n + i) * 3;
+              ao[0] = a[0]; ao[1] = a[1]; ao[2] = a[2];
+            }
+            if (J.logp_out) J.logp_out[(int64_t)t * n + i] = lp;
           } else {
             const float* ai = J.act + ((int64_t)t * n + i) * 3;
             a[0] = ai[0]; a[1] = ai[1]; a[2] = ai[2];
@@ -495,6 +528,15 @@ void salp_robot_rollout_kernel(RobotParams P, RobotState S, RobotRollout J) {
     if (iter >= J.max_iters) break;
   }
   if (active) store_robot(r, S, P, i);
+}
+
+// The policy's noise step (header words PH_NOISE, PH_NOISE + 1 of its device block): one thread, behind the launches that
+// read it.  The robot library's own copy of the snake library's kernel (salp_service_kernels.h is salp_vec.hip's alone).
+__global__ void salp_robot_policy_noise_kernel(float* block, uint64_t add, uint64_t set, int do_set) {
+  uint32_t* const w = reinterpret_cast<uint32_t*>(block) + PH_NOISE;
+  const uint64_t v = do_set ? set : ((((uint64_t)w[1] << 32) | w[0]) + add);
+  w[0] = (uint32_t)v;
+  w[1] = (uint32_t)(v >> 32);
 }
 
 // ---- test support: the fp64 primitives on their own (salp_robot_math_probe, declared in salp_fp64_math.h) ----------

@@ -237,13 +237,14 @@ def _key_words(key) -> Tuple[int, int]:
     return int(key) & 0xFFFFFFFF, (int(key) >> 32) & 0xFFFFFFFF
 
 
-def noise_words(key, env_index, n) -> np.ndarray:
-    """The policy-noise blocks, uint32 [..., 4]: Philox4x32-10(counter = (env_lo, env_hi, n mod 2^32, 3), key); `env_index`
-    (global) and `n` (noise step) broadcast against each other."""
+def noise_words(key, env_index, n, stream: int = NOISE_STREAM) -> np.ndarray:
+    """The policy-noise blocks, uint32 [..., 4]: Philox4x32-10(counter = (env_lo, env_hi, n mod 2^32, stream), key);
+    `env_index` (global) and `n` (noise step) broadcast against each other.  `stream`: the fourth counter word, 3 for the
+    block of action components 0 and 1, 4 for the block of component 2 (include/salp_robot_sampled.h)."""
     env = np.asarray(env_index, dtype=np.uint64)
     nn = np.asarray(n).astype(np.uint64) & np.uint64(0xFFFFFFFF)
     env, nn = np.broadcast_arrays(env, nn)
-    ctr = np.stack([env & np.uint64(0xFFFFFFFF), env >> np.uint64(32), nn, np.full(env.shape, NOISE_STREAM, np.uint64)], axis=-1)
+    ctr = np.stack([env & np.uint64(0xFFFFFFFF), env >> np.uint64(32), nn, np.full(env.shape, int(stream), np.uint64)], axis=-1)
     return philox4x32_10(ctr, np.array(_key_words(key), np.uint64))
 
 
@@ -320,14 +321,19 @@ class GaussianPolicy(MLPPolicy):
 
     # ------------------------------------------------------------------ noise
     @staticmethod
-    def noise_words(key, env_index, n) -> np.ndarray:
-        return noise_words(key, env_index, n)
+    def noise_words(key, env_index, n, stream: int = NOISE_STREAM) -> np.ndarray:
+        return noise_words(key, env_index, n, stream)
 
     def noise(self, key, env_index, n) -> np.ndarray:
-        """float64 z [..., act_dim] of the definition (include/salp_vec.h "Randomness"): component j from words
-        (w[2j], w[2j+1]) of block(env, n).  `key`: the handle's seed; `env_index` (global) and `n` broadcast."""
-        w = noise_words(key, env_index, n)
-        return np.stack([normal_from_words(w[..., 2 * j], w[..., 2 * j + 1]) for j in range(self.act_dim)], axis=-1)
+        """float64 z [..., act_dim] of the definition (include/salp_vec.h "Randomness", include/salp_robot_sampled.h):
+        component j from words (w[2 (j % 2)], w[2 (j % 2) + 1]) of the block of stream word 3 + j // 2 — components 0 and 1
+        from block(env, n) of stream 3, component 2 from the first two words of the block of stream 4.  `key`: the handle's
+        seed; `env_index` (global) and `n` broadcast."""
+        if self.act_dim > 3:
+            raise ValueError(f"the noise is defined for up to 3 action components, not {self.act_dim}")
+        w = [noise_words(key, env_index, n, NOISE_STREAM + k) for k in range((self.act_dim + 1) // 2)]
+        return np.stack([normal_from_words(w[j // 2][..., 2 * (j % 2)], w[j // 2][..., 2 * (j % 2) + 1])
+                         for j in range(self.act_dim)], axis=-1)
 
     # ------------------------------------------------------------------ evaluation
     def _sampled(self, x, z, with_bound: bool):

@@ -10,7 +10,8 @@ robot.py:335-358, 422-445): `info["inner_steps"]` is the number of Euler steps e
 `env.record_history(slice(a, b), stride)` adds the per-Euler-step history of those robots to `info`
 (`cycle_history`, `cycle_history_len`, `cycle_history_envs`; `env.history_of(i)` in the reference's shape).
 `env.rollout(actions_HN3)` runs H cycles of every robot in one launch, and `env.rollout_policy(policy, H)` does so with
-every action computed in the kernel by a small MLP policy (`policy.MLPPolicy`, 6 observations -> 3 action components).
+every action computed in the kernel by a small MLP policy (`policy.MLPPolicy`, 6 observations -> 3 action components);
+with a `policy.GaussianPolicy` and `sample=True` the kernel samples the tanh-Gaussian action and returns its log-probability.
 Same conventions as SalpVectorEnv: device tensors, same-step autoreset with `final_observation`,
 no CPU fallback."""
 from __future__ import annotations
@@ -180,20 +181,23 @@ class SalpRobotVectorEnv(ArrayBackend):
 
     def make_policy(self, policy, weights=None) -> "RobotPolicyHandle":
         """An in-kernel policy of this env for `rollout_policy`: a `policy.MLPPolicy` with obs_dim 6 and act_dim 3, one
-        policy or a population (P policies share the envs in runs of N / P, whole wavefronts each).
-        `MLPPolicy.from_actor(actor)` of a `sac.Actor` built with this env's Box carries the right scale and shift.
-        `handle.update(w)` takes new weights of the same shape in the public layout (`MLPPolicy.pack()`); with a device
+        policy or a population (P policies share the envs in runs of N / P, whole wavefronts each), or a
+        `policy.GaussianPolicy` of those dimensions (salp_robot_policy_create_gaussian: `rollout_policy(..., sample=True)`
+        samples from it, `sample=False` runs its mean).
+        `MLPPolicy.from_actor(actor)` / `GaussianPolicy.from_actor(actor)` of a `sac.Actor` built with this env's Box
+        carries the right scale and shift.
+        `handle.update(w)` takes new weights of the same shape in the public layout (`policy.pack()`); with a device
         tensor it is stream-ordered and allocates nothing."""
-        if getattr(policy, "gaussian", False):
-            raise ValueError("the robot rollout runs deterministic policies only (pass policy.mean_policy())")
+        gauss = bool(getattr(policy, "gaussian", False))
         if (policy.obs_dim, policy.act_dim) != (self.obs_dim, self.act_dim):
             raise ValueError(f"the policy maps {policy.obs_dim} -> {policy.act_dim}, this env {self.obs_dim} -> {self.act_dim}")
         policy.check_envs(self.num_envs)
         p = ctypes.c_void_p()
         w = policy.pack() if weights is None else weights
-        _capi.call(self.L, "salp_robot_policy_create", self._h, ctypes.byref(policy.desc()), w,
-                   0 if weights is None else self._flags, self._stream, ctypes.byref(p), what="make_policy")
-        h = RobotPolicyHandle(self, p, policy.n_policies, int(policy.words))
+        _capi.call(self.L, "salp_robot_policy_create_gaussian" if gauss else "salp_robot_policy_create", self._h,
+                   ctypes.byref(policy.desc()), w, 0 if weights is None else self._flags, self._stream, ctypes.byref(p),
+                   what="make_policy")
+        h = RobotPolicyHandle(self, p, policy.n_policies, int(policy.words), gauss)
         self._policies.append(h)
         return h
 
@@ -205,12 +209,16 @@ class SalpRobotVectorEnv(ArrayBackend):
             self._policy_cache[id(policy)] = (policy, self.make_policy(policy))
         return self._policy_cache[id(policy)][1]
 
-    def rollout_policy(self, policy, horizon: int, want_actions: bool = True) -> dict:
+    def rollout_policy(self, policy, horizon: int, want_actions: bool = True, sample: bool = False) -> dict:
         """`horizon` closed-loop env steps in ONE kernel launch (salp_robot_vec_rollout_policy): every action is `policy`
         applied to the observation row before it — the first one to the env's current observation (`observe()`), the
         action of step t + 1 to `obs[t]`.  `policy`: a handle of `make_policy`, or an `MLPPolicy` (a handle is then made
         and kept for the next call with the same object).  Returns the dict of `rollout` plus `actions` [H, N, 3] (None
         without `want_actions`).
+        `sample=True` (salp_robot_vec_rollout_policy_sampled, a `GaussianPolicy` or its handle): every action is the
+        tanh-Gaussian sample of include/salp_robot_sampled.h, drawn from the policy's own Philox stream at noise step
+        `handle.noise_step` + t; the dict gains `logp` [H, N], and the noise step advances by `horizon` behind the launch.
+        `sample=False` on a Gaussian policy runs its mean and leaves the noise step alone.
         Which form is faster (measured on an MI355X, H = 16, DESIGN.md §8f-4 "Rollouts"): at 4096 envs, where every
         wavefront has a SIMD to itself and `step` waits for the slowest env of each launch, the rollout takes 0.53-1.02
         of the time of the loop of actor forward + `step` (the row above 1 lies inside its 7 % spread; open loop
@@ -220,6 +228,12 @@ class SalpRobotVectorEnv(ArrayBackend):
         H = int(horizon)
         out = self._rollout_outputs(H)
         aout = self._buf("actions", (H, self.num_envs, 3), np.float32) if want_actions else None
+        if sample:
+            if not handle.gaussian:
+                raise ValueError("sample=True needs a GaussianPolicy (or the handle of one)")
+            logp = self._buf("logp", (H, self.num_envs), np.float32)
+            self._call("salp_robot_vec_rollout_policy_sampled", handle._p, H, *out, aout, logp, what="rollout_policy (sampled)")
+            return self._rollout_result(*out, actions=aout, logp=logp)
         self._call("salp_robot_vec_rollout_policy", handle._p, H, *out, aout, what="rollout_policy")
         return self._rollout_result(*out, actions=aout)
 
@@ -249,8 +263,21 @@ class SalpRobotVectorEnv(ArrayBackend):
 class RobotPolicyHandle:
     """One salp_robot_policy_t: a policy block on an env's device (SalpRobotVectorEnv.make_policy)."""
 
-    def __init__(self, env: SalpRobotVectorEnv, p, n_policies: int, words: int):
+    def __init__(self, env: SalpRobotVectorEnv, p, n_policies: int, words: int, gaussian: bool = False):
         self.env, self._p, self.n_policies, self.words = env, p, int(n_policies), int(words)
+        self.gaussian = bool(gaussian)
+
+    @property
+    def noise_step(self) -> int:
+        """salp_robot_policy_noise_step: the Gaussian policy's noise step (waits for the policy's last stream)."""
+        n = ctypes.c_uint64()
+        _capi.call(self.env.L, "salp_robot_policy_noise_step", self._p, ctypes.byref(n), what="noise_step")
+        return int(n.value)
+
+    def set_noise_step(self, n: int, stream=None):
+        """salp_robot_policy_set_noise_step: stream-ordered on `stream` (default: the env's current one)."""
+        _capi.call(self.env.L, "salp_robot_policy_set_noise_step", self._p, int(n) & 0xFFFFFFFFFFFFFFFF,
+                   self.env._stream if stream is None else stream, what="set_noise_step")
 
     def update(self, weights, flags=None, stream=None):
         """salp_robot_policy_update: float32 [P, words] in the public layout — a numpy array (flags 0), or a device tensor

@@ -427,8 +427,10 @@ def collect_in_kernel(env, agent: SAC, buffer: DeviceReplayBuffer, horizon: int,
     transitions go to `buffer` in step order: `obs` = the row each action saw (the current observation, then obs[t - 1]),
     `next_obs` = obs[t].  Transitions whose step was TRUNCATED are left out — the policy kernels return no terminal
     observation, and after the same-step autoreset obs[t] is the next episode's first row; terminated ones are kept (the
-    target ignores their next_obs).  Returns the policy handle: pass it back as `handle` and the next call only uploads the
-    actor's new weights (`handle.update`)."""
+    target ignores their next_obs).  A robot env (`SalpRobotVectorEnv`) returns `final_observation` from its rollout: there
+    `next_obs` is the terminal row wherever an episode ended (terminated or truncated) and obs[t] elsewhere, and all H x N
+    transitions are stored, as `train_sac` stores them.  Returns the policy handle: pass it back as `handle` and the next
+    call only uploads the actor's new weights (`handle.update`)."""
     from .policy import GaussianPolicy
     wide = [h for h in agent.cfg.hidden_sizes if h > IN_KERNEL_HIDDEN_MAX]
     if wide or len(agent.cfg.hidden_sizes) > 2:
@@ -443,6 +445,11 @@ def collect_in_kernel(env, agent: SAC, buffer: DeviceReplayBuffer, horizon: int,
     first = env.observe().clone()
     out = env.rollout_policy(handle, H, sample=True)
     seen = torch.cat([first[None], out["obs"][:-1]])
+    if "final_observation" in out:     # the robot rollout keeps terminal rows: nothing is left out
+        whole = lambda t: t.reshape((H * n,) + tuple(t.shape[2:]))
+        next_obs = torch.where(out["_final_observation"][..., None], out["final_observation"], out["obs"])
+        buffer.add(whole(seen), whole(out["actions"]), whole(out["reward"]), whole(next_obs), whole(out["terminated"]))
+        return handle
     keep = (out["truncated"] == 0).reshape(-1)
     flat = lambda t: t.reshape((H * n,) + tuple(t.shape[2:]))[keep]
     buffer.add(flat(seen), flat(out["actions"]), flat(out["reward"]), flat(out["obs"]), flat(out["terminated"]))
