@@ -1,8 +1,8 @@
 // policy_host.cpp — host twin of the in-kernel policy's layout and of the set_state ranges (TEST INFRASTRUCTURE).
 // Compiles the host sections of csrc/salp_policy.h and csrc/salp_params.h as plain C++ (oracle/Makefile, the flags of the
 // parameter twin) and exports what salp_policy_create and salp_vec_set_state decide before they touch a GPU: the ranges of
-// a policy descriptor, the map from the public weight layout to the device block, the block's header words, and the
-// ranges of a host snapshot.
+// a policy descriptor, the map from the public weight layout to the device block, the block's header words, the byte
+// counts of a policy object's allocations, and the ranges of a host snapshot.
 #include <stdio.h>
 
 #pragma GCC diagnostic push
@@ -44,6 +44,12 @@ void salp_policy_host_header(const salp_policy_desc_t* d, int stride, int64_t n_
   int32_t w[PH_WORDS];
   policy_header(*d, stride, n_envs, gaussian != 0, w);
   for (int i = 0; i < PH_WORDS; ++i) hd[i] = w[i];
+}
+
+// policy_bytes(): the byte counts of the block, the public staging and the map, in this order
+void salp_policy_host_bytes(const salp_policy_desc_t* d, int words, int stride, uint64_t bytes[3]) {
+  const PolicyBytes b = policy_bytes(*d, words, stride);
+  bytes[0] = b.block; bytes[1] = b.pub; bytes[2] = b.map;
 }
 
 // The status of check_snapshot(); the message goes to msg (msg_size bytes), "" when the snapshot is accepted.

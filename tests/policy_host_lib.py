@@ -2,7 +2,7 @@
 
 oracle/libsalp_policy_host.so is tests/policy_host.cpp: the host sections of csrc/salp_policy.h and csrc/salp_params.h
 compiled as plain C++.  What salp_policy_create and salp_vec_set_state decide before they touch a GPU is callable here
-without one: check_policy_desc(), policy_block_map(), policy_header() and check_snapshot().
+without one: check_policy_desc(), policy_block_map(), policy_header(), policy_bytes() and check_snapshot().
 """
 import ctypes
 import os
@@ -35,6 +35,8 @@ def lib():
         L.salp_policy_host_map.argtypes = [ctypes.c_int, ctypes.c_int, desc, ctypes.c_int, i32p, ctypes.c_int]
         L.salp_policy_host_header.argtypes = [desc, ctypes.c_int, ctypes.c_int64, ctypes.c_int, i32p]
         L.salp_policy_host_header.restype = None
+        L.salp_policy_host_bytes.argtypes = [desc, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
+        L.salp_policy_host_bytes.restype = None
         L.salp_policy_host_check_snapshot.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
         L.salp_policy_host_max_angle.restype = ctypes.c_double
         _lib = L
@@ -85,6 +87,13 @@ def header(d, stride, n_envs, gaussian=False) -> np.ndarray:
     hd = np.full(lib().salp_policy_host_header_words(), -2, np.int32)
     lib().salp_policy_host_header(ctypes.byref(d), stride, n_envs, int(gaussian), hd.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
     return hd
+
+
+def alloc_bytes(d, words, stride) -> tuple:
+    """policy_bytes(): the byte counts (block, pub, map) of a policy object's three device allocations."""
+    b = (ctypes.c_uint64 * 3)()
+    lib().salp_policy_host_bytes(ctypes.byref(d), words, stride, b)
+    return tuple(int(v) for v in b)
 
 
 def check_snapshot(n, f64, i32):

@@ -1,8 +1,9 @@
 """Where every weight of an in-kernel policy sits in its device block is decided on the host, by the map that
 salp_policy_create hands to the relayout kernel; a wrong entry evaluates another network with no error.  The host section
-of csrc/salp_policy.h (check_policy_desc, policy_block_map, policy_header) and check_snapshot of csrc/salp_params.h compile
-as plain C++ (tests/policy_host.cpp), so the map is checked here against the layout that the header's comment states, the
-descriptor's and the snapshot's ranges at their edges, and the header words, all without a GPU."""
+of csrc/salp_policy.h (check_policy_desc, policy_block_map, policy_header, policy_bytes) and check_snapshot of
+csrc/salp_params.h compile as plain C++ (tests/policy_host.cpp), so the map is checked here against the layout that the
+header's comment states, the descriptor's and the snapshot's ranges at their edges, the header words and the byte counts of
+the three device allocations, all without a GPU."""
 import ctypes
 import itertools
 import math
@@ -186,6 +187,39 @@ def test_words_are_those_of_the_python_policies():
     for act_dim, hidden, gaussian in SHAPES:
         p = counting_policy(act_dim, hidden, gaussian)
         assert ph.check(p.desc(), OBS_DIM, act_dim, gaussian=gaussian)[1] == p.words == p.pack().shape[1]
+
+
+def zero_policy(obs_dim, act_dim, hidden, P, gaussian):
+    """P policies of that shape, every weight zero: only `words` and `desc()` are read."""
+    layers, d = [], obs_dim
+    for o in hidden + (act_dim,):
+        layers.append((np.zeros((P, o, d), np.float32), np.zeros((P, o), np.float32)))
+        d = o
+    d = hidden[-1] if hidden else obs_dim
+    ones = np.ones((P, act_dim), np.float32)
+    if gaussian:
+        return GaussianPolicy(layers, (np.zeros((P, act_dim, d), np.float32), np.zeros((P, act_dim), np.float32)), ones, ones)
+    return MLPPolicy(layers, ones, ones)
+
+
+# no hidden layer with one policy, one hidden layer with four, two hidden layers; snake (24 -> 1, 24 -> 2) and robot (6 -> 3) dimensions
+BYTE_SHAPES = list(itertools.product([(24, 1), (24, 2), (6, 3)], [((), 1), ((16,), 4), ((32, 32), 2)], [False, True]))
+
+
+@pytest.mark.parametrize("dims,shape,gaussian", BYTE_SHAPES,
+                         ids=[f"{o}to{a}-{'x'.join(map(str, h)) or 'linear'}-P{P}-{'gauss' if g else 'plain'}"
+                              for (o, a), (h, P), g in BYTE_SHAPES])
+def test_the_three_allocations_have_the_sizes_the_layout_needs(dims, shape, gaussian):
+    """policy_bytes(): what policy create hands to hipMalloc for the block, the public staging and the map."""
+    (obs_dim, act_dim), (hidden, P) = dims, shape
+    p = zero_policy(obs_dim, act_dim, hidden, P, gaussian)
+    assert p.n_policies == P and p.pack().shape == (P, p.words)
+    d = p.desc()
+    stride = len(ph.block_map(d, obs_dim, act_dim, gaussian))
+    words = ph.check(d, obs_dim, act_dim, n_envs=256, gaussian=gaussian)[1]
+    assert words == p.words
+    header_words = ph.header_slots()["WORDS"]
+    assert ph.alloc_bytes(d, words, stride) == (4 * (header_words + P * stride), 4 * P * p.words, 4 * stride)
 
 
 # ---------------------------------------------------------------------- check_snapshot (the ranges of salp_vec_set_state)

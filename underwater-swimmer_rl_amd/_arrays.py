@@ -1,5 +1,6 @@
-"""The array backend of the env shims (vector_env.py, robot_env.py): device tensors with `output="torch"`, host numpy
-arrays with `output="numpy"`.  PyTorch is used for device buffers and streams only."""
+"""What the env shims (vector_env.py, robot_env.py) share.  The array backend: device tensors with `output="torch"`, host
+numpy arrays with `output="numpy"`; PyTorch is used for device buffers and streams only.  The policy cache: an env's
+in-kernel policies by policy object."""
 from __future__ import annotations
 
 import numpy as np
@@ -81,3 +82,23 @@ class ArrayBackend:
         if tuple(out.shape) != tuple(shape):
             raise ValueError(f"out must be an {np.dtype(dtype).name} [{shape[0]}, {shape[1]}] block")
         return out
+
+
+class PolicyCache:
+    """Mixin: the in-kernel policies of an env.  The env names the handle class of its library (`_handle_class`), keeps
+    `_policy_cache` (id(policy object) -> (policy object, its handle)) and makes handles in `make_policy`."""
+    _handle_class = None
+
+    def _check_policy(self, policy):
+        """What `make_policy` checks of a policy object before the library sees it."""
+        if (policy.obs_dim, policy.act_dim) != (self.obs_dim, self.act_dim):
+            raise ValueError(f"the policy maps {policy.obs_dim} -> {policy.act_dim}, this env {self.obs_dim} -> {self.act_dim}")
+        policy.check_envs(self.num_envs)
+
+    def _policy_handle(self, policy):
+        """`policy` if it is a handle, else the handle made for that policy object at its first use (kept until close())."""
+        if isinstance(policy, self._handle_class):
+            return policy
+        if id(policy) not in self._policy_cache:
+            self._policy_cache[id(policy)] = (policy, self.make_policy(policy))
+        return self._policy_cache[id(policy)][1]

@@ -275,7 +275,7 @@ class SalpLib:
 
     def policy_update(self, handle: "PolicyHandle", weights, flags=0, stream=0):
         """salp_policy_update: float32 [P, words] in the public layout; with SALP_DEVICE_PTRS stream-ordered, no allocation."""
-        call(self.lib, "salp_policy_update", handle._p, weights, flags, stream)
+        handle.update(weights, flags, stream)
 
     def rollout_policy(self, handle: "PolicyHandle", horizon, obs, reward, term, trunc, act_out, flags, stream=0):
         """salp_vec_rollout_policy: the four main outputs are required, act_out may be None."""
@@ -354,30 +354,37 @@ class SalpLib:
         return int(self.lib.salp_vec_global_step(self._h))
 
 
-class PolicyHandle:
-    """One salp_policy_t: a policy block on a handle's device (SalpLib.policy_create)."""
+class PolicyHandleBase:
+    """One policy block on a handle's device.  The subclass names its library by the prefix of its functions; `owner` is
+    what made the handle: it has the loaded library (`lib`) and lists its live handles (`_policies`)."""
+    _prefix = ""
+    _what = {}      # function (without the prefix) -> the call's name in an error message, default the function's own
 
-    def __init__(self, owner: SalpLib, p, n_policies: int, words: int, gaussian: bool = False):
+    def __init__(self, owner, p, n_policies: int, words: int, gaussian: bool = False):
         self.owner, self._p, self.n_policies, self.words = owner, p, int(n_policies), int(words)
         self.gaussian = bool(gaussian)
 
+    def _call(self, name, *args):
+        call(self.owner.lib, self._prefix + name, self._p, *args, what=self._what.get(name))
+
     @property
     def noise_step(self) -> int:
-        """salp_policy_noise_step: the Gaussian policy's noise step (waits for the policy's last stream)."""
+        """*_policy_noise_step: the Gaussian policy's noise step (waits for the policy's last stream)."""
         n = ctypes.c_uint64()
-        call(self.owner.lib, "salp_policy_noise_step", self._p, ctypes.byref(n))
+        self._call("noise_step", ctypes.byref(n))
         return int(n.value)
 
     def set_noise_step(self, n: int, stream=0):
-        """salp_policy_set_noise_step: stream-ordered."""
-        call(self.owner.lib, "salp_policy_set_noise_step", self._p, int(n) & 0xFFFFFFFFFFFFFFFF, stream)
+        """*_policy_set_noise_step: stream-ordered."""
+        self._call("set_noise_step", int(n) & 0xFFFFFFFFFFFFFFFF, stream)
 
     def update(self, weights, flags=0, stream=0):
-        self.owner.policy_update(self, weights, flags, stream)
+        """*_policy_update: float32 [P, words] in the public layout; with SALP_DEVICE_PTRS stream-ordered, no allocation."""
+        self._call("update", weights, flags, stream)
 
     def close(self):
         if getattr(self, "_p", None):
-            self.owner.lib.salp_policy_destroy(self._p)
+            getattr(self.owner.lib, self._prefix + "destroy")(self._p)
             self._p = ctypes.c_void_p()
             if self in self.owner._policies:
                 self.owner._policies.remove(self)
@@ -387,3 +394,8 @@ class PolicyHandle:
             self.close()
         except Exception:
             pass
+
+
+class PolicyHandle(PolicyHandleBase):
+    """One salp_policy_t (SalpLib.policy_create)."""
+    _prefix = "salp_policy_"

@@ -1,7 +1,8 @@
 // salp_host.h — host-only support shared by the two C ABI files, salp_vec.hip and salp_robot.hip: the error string and
 // HIP_TRY, DeviceScope, the device-id check of the create calls, the frame every call on a handle opens with (CallFrame),
 // launch_1d() and the one body that serves the host-pointer and the device-pointer form of a call (StageBuffer,
-// HostStream, staged()).  Everything here has internal linkage, so each of the two translation units has an
+// HostStream, staged()).  The policy object of both files builds on it (salp_policy_object.h, included after this
+// header).  Everything here has internal linkage, so each of the two translation units has an
 // error string of its own (salp_last_error and salp_robot_last_error stay independent).  No device code; the rollout
 // kernel units do not include it.  What the two files refuse is decided in headers that do not know fail() and compile
 // without HIP (salp_params.h, salp_policy.h, salp_robot_params.h); the ABI file hands the reason to fail().

@@ -29,9 +29,10 @@
 // group of 16, wave-uniform).
 //
 // The header has a host section and a device section.  The host section — the descriptor's ranges, the map from the public
-// layout (include/salp_vec.h) to the block above, and the header words — is plain C++17 with no HIP call and no fail(), like
+// layout (include/salp_vec.h) to the block above, the header words and the allocations' byte counts — is plain C++17 with no HIP call and no fail(), like
 // the host functions of salp_params.h: tests/policy_host.cpp compiles it with g++, so the layout is under test without a GPU.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include <vector>
@@ -119,6 +120,14 @@ inline void policy_header(const salp_policy_desc_t& d, int stride, int64_t n_env
   hd[PH_NHIDDEN] = d.n_hidden; hd[PH_H0] = d.hidden[0]; hd[PH_H1] = d.hidden[1]; hd[PH_OUT] = d.out_activation;
   hd[PH_STRIDE] = stride; hd[PH_COUNT] = d.n_policies; hd[PH_GAUSS] = gaussian ? 1 : 0;
   hd[PH_GROUP] = d.n_policies > 1 ? (int32_t)(n_envs / d.n_policies) : 0x7FFFFFFF;
+}
+
+// The byte counts of a policy object's three device allocations: the block (header + d.n_policies policies of `stride`
+// words), the staging of the public layout ([n_policies][words]) and the map ([stride]).
+struct PolicyBytes { size_t block, pub, map; };
+inline PolicyBytes policy_bytes(const salp_policy_desc_t& d, int words, int stride) {
+  return {((size_t)PH_WORDS + (size_t)d.n_policies * stride) * sizeof(float), (size_t)d.n_policies * words * sizeof(float),
+          (size_t)stride * sizeof(int32_t)};
 }
 
 // ------------------------------------------------------------------ device side

@@ -5,7 +5,8 @@
 //   salp_robot_params.h    RobotParams and its derivation from a config, the constants, every argument check
 //   salp_host.h            fail, HIP_TRY, DeviceScope, check_device_id, CallFrame, launch_1d, StageBuffer, staged()
 //   salp_policy.h          the in-kernel policy's descriptor ranges, block map and header (host functions, generic in the dimensions)
-//   salp_policy_upload.h   the upload of a policy's weights, shared with salp_vec.hip
+//   salp_policy_object.h   the policy object behind a salp_robot_policy_t and its whole life, shared with salp_vec.hip
+//   salp_policy_upload.h   the upload of a policy's weights and the write of its noise step: kernels of salp_vec.hip's unit
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -21,7 +22,7 @@
 #include "salp_robot_params.h"
 #include "salp_robot_kernels.h"
 #include "salp_host.h"
-#include "salp_policy_upload.h"
+#include "salp_policy_object.h"
 
 using namespace salp;
 
@@ -39,18 +40,15 @@ struct salp_robot_vec {
   int period;         // the rollout kernel's service period M, one of kRolloutPeriods (salp_robot_params.h)
 };
 
-struct salp_robot_policy {
-  salp_robot_vec* h;         // the handle it is bound to (its env count fixes env -> policy)
-  salp_policy_desc_t d;
-  int device;
-  int words;                 // public words of one policy
-  int stride;                // words of one policy in the device block (salp_policy.h)
-  float* block;              // device: header + P policies, what the kernel reads
-  float* pub;                // device: staging of the public layout [P][words] (host-pointer create / update)
-  int32_t* map;              // device: word k of a policy in the block <- public word map[k] (-1: zero)
-  int gaussian;              // salp_robot_policy_create_gaussian: a log-std head behind the mean head, a noise step in the header
-  mutable hipStream_t last_stream;   // the stream of its most recent upload, rollout or noise-step write: what destroy waits for
+struct salp_robot_policy : PolicyObject {     // salp_policy_object.h; last_stream: its most recent upload, rollout or noise-step write
+  salp_robot_vec* h;         // the handle it is bound to
 };
+
+// What a policy of this handle is checked against and made for: obs_dim 6, act_dim 3, and kmax = 3, which the descriptor's
+// ranges ask of a snake handle; a NULL handle: zeros.
+static PolicyDims policy_dims(const salp_robot_vec* h) {
+  return h ? PolicyDims{ROBOT_POLICY_OBS, ROBOT_POLICY_ACT, 3, h->n, h->device} : PolicyDims{};
+}
 
 // Below this many envs every wavefront has an execution unit to itself and the launch lasts as long as
 // its slowest env whatever the order.  SALP_ROBOT_SCHEDULE=0/1 overrides (tests run both ways).
@@ -110,7 +108,7 @@ static int robot_rollout_impl(salp_robot_vec_t* h, const float* source, int32_t 
     J.logp_out = s[8].as<float>();
     const int rc = launch();
     if (ACT != kActPolicySampled || rc != SALP_OK) return rc;
-    return launch_1d(salp_robot_policy_noise_kernel, 1, 1, f.st, const_cast<float*>(source), (uint64_t)horizon, (uint64_t)0, 0);
+    return policy_noise_advance(const_cast<float*>(source), horizon, f.st);
   });
 }
 
@@ -277,87 +275,26 @@ int salp_robot_vec_rollout(salp_robot_vec_t* h, const float* act, int32_t horizo
                                       stream);
 }
 
-// The descriptor's ranges for a robot handle (salp_policy.h; obs_dim 6, act_dim 3, and kmax = 3, which those ranges ask of
-// a snake handle).  On success *words = public words of one policy.
-static int check_robot_policy_desc(const salp_robot_vec_t* h, const salp_policy_desc_t* d, int* words, bool gaussian = false) {
-  const char* why = "";
-  const int rc = h ? check_policy_desc(ROBOT_POLICY_OBS, ROBOT_POLICY_ACT, 3, h->n, d, gaussian, words, &why)
-                   : check_policy_desc(0, 0, 0, 0, nullptr, gaussian, words, &why);
-  return rc == SALP_OK ? rc : fail(rc, why);
-}
-
-int salp_robot_policy_words(const salp_robot_vec_t* h, const salp_policy_desc_t* desc) {
-  int words = 0;
-  const int rc = check_robot_policy_desc(h, desc, &words);
-  return rc != SALP_OK ? rc : words;
-}
+// The policy object's calls: salp_policy_object.h.
+int salp_robot_policy_words(const salp_robot_vec_t* h, const salp_policy_desc_t* desc) { return policy_words(policy_dims(h), desc, false); }
+int salp_robot_policy_words_gaussian(const salp_robot_vec_t* h, const salp_policy_desc_t* desc) { return policy_words(policy_dims(h), desc, true); }
 
 void salp_robot_policy_destroy(salp_robot_policy_t* pol) {
-  if (!pol) return;
-  DeviceScope dev_scope;
-  (void)dev_scope.enter(pol->device);
-  (void)hipStreamSynchronize(pol->last_stream);     // its uploads and the rollouts that read the block (hipFree does not wait on non-blocking streams)
-  if (pol->block) (void)hipFree(pol->block);
-  if (pol->pub) (void)hipFree(pol->pub);
-  if (pol->map) (void)hipFree(pol->map);
-  delete pol;
-}
-
-static int robot_policy_upload(salp_robot_policy* pol, const float* weights, uint32_t flags, hipStream_t st) {
-  pol->last_stream = st;
-  const PolicyBlock b = {pol->block, pol->pub, pol->map, pol->d.n_policies, pol->words, pol->stride};
-  HIP_TRY(policy_block_upload(b, weights, (flags & 1u) != 0, st));     // salp_policy_upload.h (defined in salp_vec.hip)
-  return SALP_OK;
+  if (pol) policy_free(pol, nullptr);     // its uploads and the rollouts that read the block are all on its own last_stream
 }
 
 // salp_robot_policy_create (gaussian = false) and salp_robot_policy_create_gaussian
 static int robot_policy_create_impl(salp_robot_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags,
                                     void* stream, salp_robot_policy_t** out, bool gaussian) {
-  if (!out) return fail(SALP_ERR_INVALID, "out is NULL");
-  *out = nullptr;
-  int words = 0;
-  int rc = check_robot_policy_desc(h, desc, &words, gaussian);
-  if (rc != SALP_OK) return rc;
-  if (!weights) return fail(SALP_ERR_INVALID, "weights is NULL");
-  if (flags & ~1u) return fail(SALP_ERR_INVALID, "unknown flag bits");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(h->device));
-  salp_robot_policy* pol = new (std::nothrow) salp_robot_policy();     // value-initialised: every field zero
-  if (!pol) return fail(SALP_ERR_OOM, "host allocation failed");
-  pol->h = h; pol->d = *desc; pol->device = h->device; pol->words = words; pol->gaussian = gaussian ? 1 : 0;
-  std::vector<int32_t> map;     // word k of a policy in the device block <- public word map[k]: salp_policy.h
-  pol->stride = policy_block_map(ROBOT_POLICY_OBS, ROBOT_POLICY_ACT, *desc, gaussian, map);
-  const size_t block_b = ((size_t)PH_WORDS + (size_t)desc->n_policies * pol->stride) * sizeof(float);
-  const size_t pub_b = (size_t)desc->n_policies * words * sizeof(float), map_b = map.size() * sizeof(int32_t);
-  hipError_t e = hipMalloc((void**)&pol->block, block_b);
-  if (e == hipSuccess) e = hipMalloc((void**)&pol->pub, pub_b);
-  if (e == hipSuccess) e = hipMalloc((void**)&pol->map, map_b);
-  if (e == hipSuccess) e = hipMemcpy(pol->map, map.data(), map_b, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    int32_t hd[PH_WORDS];
-    policy_header(*desc, pol->stride, h->n, gaussian, hd);
-    e = hipMemcpy(pol->block, hd, sizeof(hd), hipMemcpyHostToDevice);
-  }
-  if (e != hipSuccess) {
-    const std::string m = std::string("hipMalloc/hipMemcpy(policy): ") + hipGetErrorString(e);
-    salp_robot_policy_destroy(pol);
-    return fail(e == hipErrorOutOfMemory ? SALP_ERR_OOM : SALP_ERR_HIP, m);
-  }
-  rc = robot_policy_upload(pol, weights, flags, (hipStream_t)stream);
-  if (rc != SALP_OK) { const std::string m = g_err; salp_robot_policy_destroy(pol); g_err = m; return rc; }
-  *out = pol;
-  return SALP_OK;
+  // of `flags`, bit 0 (device pointers) is the known one: any other is refused, behind out, the descriptor and weights
+  const int rc = policy_create(policy_dims(h), desc, weights, flags, 1u, stream, gaussian, out);
+  if (rc == SALP_OK) (*out)->h = h;
+  return rc;
 }
 
 int salp_robot_policy_create(salp_robot_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags,
                              void* stream, salp_robot_policy_t** out) {
   return robot_policy_create_impl(h, desc, weights, flags, stream, out, false);
-}
-
-int salp_robot_policy_words_gaussian(const salp_robot_vec_t* h, const salp_policy_desc_t* desc) {
-  int words = 0;
-  const int rc = check_robot_policy_desc(h, desc, &words, true);
-  return rc != SALP_OK ? rc : words;
 }
 
 int salp_robot_policy_create_gaussian(salp_robot_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags,
@@ -367,31 +304,18 @@ int salp_robot_policy_create_gaussian(salp_robot_vec_t* h, const salp_policy_des
 
 int salp_robot_policy_set_noise_step(salp_robot_policy_t* pol, uint64_t n, void* stream) {
   if (!pol) return fail(SALP_ERR_INVALID, "policy is NULL");
-  if (!pol->gaussian) return fail(SALP_ERR_INVALID, "the policy is not Gaussian: it has no noise step");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(pol->device));
-  pol->last_stream = (hipStream_t)stream;
-  return launch_1d(salp_robot_policy_noise_kernel, 1, 1, (hipStream_t)stream, pol->block, (uint64_t)0, n, 1);
+  return policy_set_noise_step(*pol, n, stream);
 }
 
 int salp_robot_policy_noise_step(salp_robot_policy_t* pol, uint64_t* n) {
-  if (!pol || !n) return fail(SALP_ERR_INVALID, "policy / n is NULL");
-  if (!pol->gaussian) return fail(SALP_ERR_INVALID, "the policy is not Gaussian: it has no noise step");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(pol->device));
-  HIP_TRY(hipStreamSynchronize(pol->last_stream));
-  uint32_t w[2] = {0u, 0u};
-  HIP_TRY(hipMemcpy(w, reinterpret_cast<const uint32_t*>(pol->block) + PH_NOISE, sizeof(w), hipMemcpyDeviceToHost));
-  *n = ((uint64_t)w[1] << 32) | w[0];
-  return SALP_OK;
+  if (!pol || !n) return fail(SALP_ERR_INVALID, "policy/n is NULL");
+  return policy_noise_step(*pol, n);
 }
 
 int salp_robot_policy_update(salp_robot_policy_t* pol, const float* weights, uint32_t flags, void* stream) {
-  if (!pol || !weights) return fail(SALP_ERR_INVALID, "policy / weights is NULL");
+  if (!pol || !weights) return fail(SALP_ERR_INVALID, "policy/weights is NULL");
   if (flags & ~1u) return fail(SALP_ERR_INVALID, "unknown flag bits");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(pol->device));
-  return robot_policy_upload(pol, weights, flags, (hipStream_t)stream);
+  return policy_update(*pol, weights, (flags & 1u) != 0, stream);
 }
 
 int salp_robot_vec_rollout_policy(salp_robot_vec_t* h, const salp_robot_policy_t* pol, int32_t horizon, float* obs,

@@ -2,7 +2,8 @@
 // (RobotParams, the constants and schedule_bin are salp_robot_params.h): the robot in
 // registers (Rb) with load / store / rest / reset / observe, the reset kernel, the three kernels of the cycle-length
 // schedule, the history sample store, the two step kernels (salp_robot_step_body.h), the trajectory kernel, the
-// multi-cycle rollout kernel, the policy's noise-step kernel and the math-probe kernel.  One breathing cycle itself is
+// multi-cycle rollout kernel and the math-probe kernel (a policy's relayout and noise-step kernels are salp_vec.hip's,
+// reached through salp_policy_upload.h).  One breathing cycle itself is
 // salp_robot_cycle_body.h, made of the pieces salp_robot_cycle_control.h / _consts.h / _start.h and
 // salp_robot_euler_step.h, which the rollout kernel includes one by one.
 //
@@ -528,15 +529,6 @@ void salp_robot_rollout_kernel(RobotParams P, RobotState S, RobotRollout J) {
     if (iter >= J.max_iters) break;
   }
   if (active) store_robot(r, S, P, i);
-}
-
-// The policy's noise step (header words PH_NOISE, PH_NOISE + 1 of its device block): one thread, behind the launches that
-// read it.  The robot library's own copy of the snake library's kernel (salp_service_kernels.h is salp_vec.hip's alone).
-__global__ void salp_robot_policy_noise_kernel(float* block, uint64_t add, uint64_t set, int do_set) {
-  uint32_t* const w = reinterpret_cast<uint32_t*>(block) + PH_NOISE;
-  const uint64_t v = do_set ? set : ((((uint64_t)w[1] << 32) | w[0]) + add);
-  w[0] = (uint32_t)v;
-  w[1] = (uint32_t)(v >> 32);
 }
 
 // ---- test support: the fp64 primitives on their own (salp_robot_math_probe, declared in salp_fp64_math.h) ----------

@@ -4,14 +4,16 @@
 // reached through their rollout_unit_fn functions.  What is decided before a GPU is touched lives in host functions that
 // are under test without one: the config's defaults and ranges, the launch parameters derived from it and the ranges of
 // a snapshot (default_config, validate, make_params, is_std, check_snapshot: salp_params.h); a policy descriptor's ranges,
-// the map from the public weight layout to the device block and the block's header (salp_policy.h).
+// the map from the public weight layout to the device block, the block's header and the allocations' sizes (salp_policy.h).
+// The policy object behind a salp_policy_t, shared with salp_robot.hip, is salp_policy_object.h; the two functions through
+// which the robot library reaches this unit's policy kernels are defined here (salp_policy_upload.h).
 #include <new>
 #include <string>
 #include <type_traits>
 #include <vector>
 
 #include "salp_host.h"
-#include "salp_policy_upload.h"
+#include "salp_policy_object.h"
 #include "salp_rollout_kernel.h"
 #include "salp_service_kernels.h"
 
@@ -42,18 +44,8 @@ struct salp_vec {
   const void* last_kernel;   // the main (else the predicated) kernel of the most recent launch: salp_vec_last_kernel_resources
 };
 
-struct salp_policy {
+struct salp_policy : PolicyObject {     // salp_policy_object.h; last_stream: create / update / noise-step writes, sampled calls included
   salp_vec* h;               // the handle it is bound to
-  salp_policy_desc_t d;
-  int device, obs_dim, act_dim;
-  int64_t n;                 // the handle's env count (fixes env -> policy)
-  int words;                 // public words of one policy
-  int stride;                // words of one policy in the device block (salp_policy.h)
-  float* block;              // device: header + P policies, what the kernel reads
-  float* pub;                // device: staging of the public layout [P][words] (host-pointer create / update)
-  int32_t* map;              // device: word k of a policy in the block <- public word map[k] (-1: zero)
-  int gaussian;              // salp_policy_create_gaussian: a log-std head behind the mean head, a noise step in the header
-  mutable hipStream_t last_stream;   // the stream of the most recent create / update / noise-step write (sampled calls included)
 };
 
 namespace {
@@ -65,13 +57,8 @@ int validate(const salp_config_t* c) {
   return rc == SALP_OK ? rc : fail(rc, why);
 }
 
-// The descriptor's ranges for this handle: salp_policy.h (likewise).  On success *words = public words of one policy.
-int check_policy_desc(const salp_vec* h, const salp_policy_desc_t* d, int* words, bool gaussian) {
-  const char* why = "";
-  const int rc = h ? salp::check_policy_desc(h->obs_dim, h->act_dim, h->kmax, h->n, d, gaussian, words, &why)
-                   : salp::check_policy_desc(0, 0, 0, 0, nullptr, gaussian, words, &why);     // one refusal, one text, for either NULL
-  return rc == SALP_OK ? rc : fail(rc, why);
-}
+// What a policy of this handle is checked against and made for (salp_policy_object.h); a NULL handle: zeros.
+PolicyDims policy_dims(const salp_vec* h) { return h ? PolicyDims{h->obs_dim, h->act_dim, h->kmax, h->n, h->device} : PolicyDims{}; }
 
 typedef void (*reset_fn)(DevParams, DevState, const uint8_t*, float*, int);
 
@@ -178,13 +165,6 @@ int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, Rollout
   return SALP_OK;
 }
 
-int policy_upload(salp_policy* pol, const float* weights, uint32_t flags, hipStream_t st) {
-  pol->last_stream = st;
-  const PolicyBlock b = {pol->block, pol->pub, pol->map, pol->d.n_policies, pol->words, pol->stride};
-  HIP_TRY(policy_block_upload(b, weights, (flags & SALP_DEVICE_PTRS) != 0, st));
-  return SALP_OK;
-}
-
 // What the record calls (packed, summary, navigation) check of `flags` and of a device `rec`: no bit outside `allowed`,
 // and 16-byte alignment, as the kernels write a record in 16-byte stores.
 int check_record_args(uint32_t flags, uint32_t allowed, const char* bits_msg, const void* rec, const char* align_msg) {
@@ -211,6 +191,11 @@ hipError_t salp::policy_block_upload(const PolicyBlock& b, const float* weights,
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess || device_ptrs) return e;
   return hipStreamSynchronize(st);
+}
+
+hipError_t salp::policy_noise_write(float* block, uint64_t value, bool set, hipStream_t st) {
+  hipLaunchKernelGGL(salp_policy_noise_kernel, dim3(1), dim3(1), 0, st, block, set ? (uint64_t)0 : value, set ? value : (uint64_t)0, set ? 1 : 0);
+  return hipGetLastError();
 }
 
 extern "C" {
@@ -384,7 +369,7 @@ int salp_vec_observe(salp_vec_t* h, float* obs, uint32_t flags, void* stream) {
 // but the noise step where it was — the caller must set it (salp_policy_set_noise_step) before sampling on.
 static int advance_noise(const salp_policy_t* pol, int H, hipStream_t st) {
   pol->last_stream = st;
-  return launch_1d(salp_policy_noise_kernel, 1, 1, st, pol->block, (uint64_t)H, (uint64_t)0, 0);
+  return policy_noise_advance(pol->block, H, st);
 }
 
 // Device-generated actions of the next H steps into act_out when given, else into the handle's own buffer (grown on demand).
@@ -505,61 +490,16 @@ int salp_vec_rollout_packed(salp_vec_t* h, const float* act, int32_t horizon, fl
   return packed_impl(h, act, horizon, rec, act_out, flags, stream);
 }
 
-int salp_policy_words(const salp_vec_t* h, const salp_policy_desc_t* desc) {
-  int words = 0;
-  const int rc = check_policy_desc(h, desc, &words, false);
-  return rc != SALP_OK ? rc : words;
-}
-
-void salp_policy_destroy(salp_policy_t* pol) {
-  if (!pol) return;
-  DeviceScope dev_scope;
-  (void)dev_scope.enter(pol->device);
-  (void)hipStreamSynchronize(pol->last_stream);        // the policy's own uploads ...
-  (void)hipStreamSynchronize(pol->h->last_stream);     // ... and the handle's launches that read the block (hipFree does not wait on non-blocking streams)
-  if (pol->block) (void)hipFree(pol->block);
-  if (pol->pub) (void)hipFree(pol->pub);
-  if (pol->map) (void)hipFree(pol->map);
-  delete pol;
-}
+// The policy object's calls: salp_policy_object.h.
+int salp_policy_words(const salp_vec_t* h, const salp_policy_desc_t* desc) { return policy_words(policy_dims(h), desc, false); }
+int salp_policy_words_gaussian(const salp_vec_t* h, const salp_policy_desc_t* desc) { return policy_words(policy_dims(h), desc, true); }
 
 static int policy_create_impl(salp_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags, void* stream,
                               salp_policy_t** out, bool gaussian) {
-  if (!out) return fail(SALP_ERR_INVALID, "out is NULL");
-  *out = nullptr;
-  int words = 0;
-  int rc = check_policy_desc(h, desc, &words, gaussian);
-  if (rc != SALP_OK) return rc;
-  if (!weights) return fail(SALP_ERR_INVALID, "weights is NULL");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(h->device));
-  salp_policy* pol = new (std::nothrow) salp_policy();
-  if (!pol) return fail(SALP_ERR_OOM, "host allocation failed");
-  memset(pol, 0, sizeof(*pol));
-  pol->h = h; pol->d = *desc; pol->device = h->device; pol->obs_dim = h->obs_dim; pol->act_dim = h->act_dim; pol->n = h->n;
-  pol->words = words; pol->gaussian = gaussian ? 1 : 0;
-  std::vector<int32_t> map;     // word k of a policy in the device block <- public word map[k]: salp_policy.h
-  pol->stride = policy_block_map(h->obs_dim, h->act_dim, *desc, gaussian, map);
-  const size_t block_b = ((size_t)PH_WORDS + (size_t)desc->n_policies * pol->stride) * sizeof(float);
-  const size_t pub_b = (size_t)desc->n_policies * words * sizeof(float), map_b = map.size() * sizeof(int32_t);
-  hipError_t e = hipMalloc((void**)&pol->block, block_b);
-  if (e == hipSuccess) e = hipMalloc((void**)&pol->pub, pub_b);
-  if (e == hipSuccess) e = hipMalloc((void**)&pol->map, map_b);
-  if (e == hipSuccess) e = hipMemcpy(pol->map, map.data(), map_b, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    int32_t hd[PH_WORDS];
-    policy_header(*desc, pol->stride, h->n, gaussian, hd);
-    e = hipMemcpy(pol->block, hd, sizeof(hd), hipMemcpyHostToDevice);
-  }
-  if (e != hipSuccess) {
-    const std::string m = std::string("hipMalloc/hipMemcpy(policy): ") + hipGetErrorString(e);
-    salp_policy_destroy(pol);
-    return fail(e == hipErrorOutOfMemory ? SALP_ERR_OOM : SALP_ERR_HIP, m);
-  }
-  rc = policy_upload(pol, weights, flags, (hipStream_t)stream);
-  if (rc != SALP_OK) { const std::string m = g_err; salp_policy_destroy(pol); g_err = m; return rc; }
-  *out = pol;
-  return SALP_OK;
+  // of `flags`, create and update read bit 0 (SALP_DEVICE_PTRS) and ignore the rest: every bit is a known one
+  const int rc = policy_create(policy_dims(h), desc, weights, flags, ~0u, stream, gaussian, out);
+  if (rc == SALP_OK) (*out)->h = h;
+  return rc;
 }
 
 int salp_policy_create(salp_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags, void* stream,
@@ -567,43 +507,28 @@ int salp_policy_create(salp_vec_t* h, const salp_policy_desc_t* desc, const floa
   return policy_create_impl(h, desc, weights, flags, stream, out, false);
 }
 
-int salp_policy_words_gaussian(const salp_vec_t* h, const salp_policy_desc_t* desc) {
-  int words = 0;
-  const int rc = check_policy_desc(h, desc, &words, true);
-  return rc != SALP_OK ? rc : words;
-}
-
 int salp_policy_create_gaussian(salp_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags, void* stream,
                                 salp_policy_t** out) {
   return policy_create_impl(h, desc, weights, flags, stream, out, true);
 }
 
-int salp_policy_set_noise_step(salp_policy_t* pol, uint64_t n, void* stream) {
-  if (!pol) return fail(SALP_ERR_INVALID, "policy is NULL");
-  if (!pol->gaussian) return fail(SALP_ERR_INVALID, "the policy is not Gaussian: it has no noise step");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(pol->device));
-  pol->last_stream = (hipStream_t)stream;
-  return launch_1d(salp_policy_noise_kernel, 1, 1, (hipStream_t)stream, pol->block, (uint64_t)0, n, 1);
-}
-
-int salp_policy_noise_step(salp_policy_t* pol, uint64_t* n) {
-  if (!pol || !n) return fail(SALP_ERR_INVALID, "policy/n is NULL");
-  if (!pol->gaussian) return fail(SALP_ERR_INVALID, "the policy is not Gaussian: it has no noise step");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(pol->device));
-  HIP_TRY(hipStreamSynchronize(pol->last_stream));
-  uint32_t w[2] = {0u, 0u};
-  HIP_TRY(hipMemcpy(w, reinterpret_cast<const uint32_t*>(pol->block) + PH_NOISE, sizeof(w), hipMemcpyDeviceToHost));
-  *n = ((uint64_t)w[1] << 32) | w[0];
-  return SALP_OK;
+void salp_policy_destroy(salp_policy_t* pol) {
+  if (pol) policy_free(pol, &pol->h->last_stream);     // its own uploads, and the handle's launches that read the block
 }
 
 int salp_policy_update(salp_policy_t* pol, const float* weights, uint32_t flags, void* stream) {
   if (!pol || !weights) return fail(SALP_ERR_INVALID, "policy/weights is NULL");
-  DeviceScope dev_scope;
-  HIP_TRY(dev_scope.enter(pol->device));
-  return policy_upload(pol, weights, flags, (hipStream_t)stream);
+  return policy_update(*pol, weights, (flags & SALP_DEVICE_PTRS) != 0, stream);
+}
+
+int salp_policy_set_noise_step(salp_policy_t* pol, uint64_t n, void* stream) {
+  if (!pol) return fail(SALP_ERR_INVALID, "policy is NULL");
+  return policy_set_noise_step(*pol, n, stream);
+}
+
+int salp_policy_noise_step(salp_policy_t* pol, uint64_t* n) {
+  if (!pol || !n) return fail(SALP_ERR_INVALID, "policy/n is NULL");
+  return policy_noise_step(*pol, n);
 }
 
 // What every call that runs a policy checks first.  (The descriptor cannot fail once the policy is known to be the handle's:
@@ -614,7 +539,7 @@ static int check_policy_call(const salp_vec_t* h, const salp_policy_t* pol, bool
   if (sampled && !pol->gaussian) return fail(SALP_ERR_INVALID, "sampling needs a Gaussian policy (salp_policy_create_gaussian)");
   if (pol->h != h || pol->device != h->device || pol->obs_dim != h->obs_dim || pol->act_dim != h->act_dim || pol->n != h->n)
     return fail(SALP_ERR_INVALID, "the policy belongs to another handle (or other dimensions)");
-  return check_policy_desc(h, &pol->d, nullptr, pol->gaussian != 0);
+  return check_policy_dims(policy_dims(h), &pol->d, pol->gaussian != 0, nullptr);
 }
 
 // salp_vec_rollout_policy (sampled = false, logp_out = NULL) and salp_vec_rollout_policy_sampled

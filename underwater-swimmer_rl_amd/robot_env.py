@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 
 from . import _capi
-from ._arrays import ArrayBackend, device_index
+from ._arrays import ArrayBackend, PolicyCache, device_index
 from ._capi import ROBOT_EXPORTS, CRobotConfig  # noqa: F401  (imported from here by tests and robot_compare.py)
 from .spaces import Box, batch_space
 
@@ -38,10 +38,30 @@ HISTORY_CHANNELS = {"position_history": (H_POS, 3), "velocity_history": (H_VEL, 
                     "nozzle_yaw_history": (H_NOZZLE_YAW, None)}
 
 
-class SalpRobotVectorEnv(ArrayBackend):
+class RobotPolicyHandle(_capi.PolicyHandleBase):
+    """One salp_robot_policy_t (SalpRobotVectorEnv.make_policy); `env` made it."""
+    _prefix = "salp_robot_policy_"
+    _what = {"noise_step": "noise_step", "set_noise_step": "set_noise_step", "update": "policy update"}
+    env = property(lambda self: self.owner)
+
+    def set_noise_step(self, n: int, stream=None):
+        """salp_robot_policy_set_noise_step: stream-ordered on `stream` (default: the env's current one)."""
+        super().set_noise_step(n, self.env._stream if stream is None else stream)
+
+    def update(self, weights, flags=None, stream=None):
+        """salp_robot_policy_update: float32 [P, words] in the public layout — a numpy array (flags 0), or a device tensor
+        (SALP_DEVICE_PTRS: stream-ordered on `stream`, default the current one, no allocation)."""
+        if flags is None:
+            flags = _capi.SALP_DEVICE_PTRS if hasattr(weights, "data_ptr") else 0
+        super().update(weights, flags, self.env._stream if stream is None else stream)
+
+
+class SalpRobotVectorEnv(ArrayBackend, PolicyCache):
+    _handle_class = RobotPolicyHandle
+
     def __init__(self, num_envs: int = 4096, device="cuda:0", seed: int = 0, env_index_base: int = 0,
                  output: str = "torch", **robot_params):
-        self.L = _capi.load_library()
+        self.L = self.lib = _capi.load_library()     # `lib`: the name a policy handle asks its owner for, as SalpLib has it
         self.num_envs = int(num_envs)
         cfg = CRobotConfig()
         _capi.call(self.L, "salp_robot_config_default", ctypes.byref(cfg))
@@ -189,9 +209,7 @@ class SalpRobotVectorEnv(ArrayBackend):
         `handle.update(w)` takes new weights of the same shape in the public layout (`policy.pack()`); with a device
         tensor it is stream-ordered and allocates nothing."""
         gauss = bool(getattr(policy, "gaussian", False))
-        if (policy.obs_dim, policy.act_dim) != (self.obs_dim, self.act_dim):
-            raise ValueError(f"the policy maps {policy.obs_dim} -> {policy.act_dim}, this env {self.obs_dim} -> {self.act_dim}")
-        policy.check_envs(self.num_envs)
+        self._check_policy(policy)
         p = ctypes.c_void_p()
         w = policy.pack() if weights is None else weights
         _capi.call(self.L, "salp_robot_policy_create_gaussian" if gauss else "salp_robot_policy_create", self._h,
@@ -200,14 +218,6 @@ class SalpRobotVectorEnv(ArrayBackend):
         h = RobotPolicyHandle(self, p, policy.n_policies, int(policy.words), gauss)
         self._policies.append(h)
         return h
-
-    def _policy_handle(self, policy):
-        """`policy` if it is a handle, else the handle made for that policy object at its first use (kept until close())."""
-        if isinstance(policy, RobotPolicyHandle):
-            return policy
-        if id(policy) not in self._policy_cache:
-            self._policy_cache[id(policy)] = (policy, self.make_policy(policy))
-        return self._policy_cache[id(policy)][1]
 
     def rollout_policy(self, policy, horizon: int, want_actions: bool = True, sample: bool = False) -> dict:
         """`horizon` closed-loop env steps in ONE kernel launch (salp_robot_vec_rollout_policy): every action is `policy`
@@ -252,47 +262,6 @@ class SalpRobotVectorEnv(ArrayBackend):
             self._policy_cache = {}
             self.L.salp_robot_vec_destroy(self._h)
             self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class RobotPolicyHandle:
-    """One salp_robot_policy_t: a policy block on an env's device (SalpRobotVectorEnv.make_policy)."""
-
-    def __init__(self, env: SalpRobotVectorEnv, p, n_policies: int, words: int, gaussian: bool = False):
-        self.env, self._p, self.n_policies, self.words = env, p, int(n_policies), int(words)
-        self.gaussian = bool(gaussian)
-
-    @property
-    def noise_step(self) -> int:
-        """salp_robot_policy_noise_step: the Gaussian policy's noise step (waits for the policy's last stream)."""
-        n = ctypes.c_uint64()
-        _capi.call(self.env.L, "salp_robot_policy_noise_step", self._p, ctypes.byref(n), what="noise_step")
-        return int(n.value)
-
-    def set_noise_step(self, n: int, stream=None):
-        """salp_robot_policy_set_noise_step: stream-ordered on `stream` (default: the env's current one)."""
-        _capi.call(self.env.L, "salp_robot_policy_set_noise_step", self._p, int(n) & 0xFFFFFFFFFFFFFFFF,
-                   self.env._stream if stream is None else stream, what="set_noise_step")
-
-    def update(self, weights, flags=None, stream=None):
-        """salp_robot_policy_update: float32 [P, words] in the public layout — a numpy array (flags 0), or a device tensor
-        (SALP_DEVICE_PTRS: stream-ordered on `stream`, default the current one, no allocation)."""
-        if flags is None:
-            flags = _capi.SALP_DEVICE_PTRS if hasattr(weights, "data_ptr") else 0
-        _capi.call(self.env.L, "salp_robot_policy_update", self._p, weights, flags,
-                   self.env._stream if stream is None else stream, what="policy update")
-
-    def close(self):
-        if getattr(self, "_p", None):
-            self.env.L.salp_robot_policy_destroy(self._p)
-            self._p = ctypes.c_void_p()
-            if self in self.env._policies:
-                self.env._policies.remove(self)
 
     def __del__(self):
         try:

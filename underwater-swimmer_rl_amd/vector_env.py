@@ -31,7 +31,7 @@ from typing import Any, Dict, Optional, Sequence, Union
 import numpy as np
 
 from . import _capi
-from ._arrays import ArrayBackend, device_index
+from ._arrays import ArrayBackend, PolicyCache, device_index
 from ._capi import SalpLib
 from .config import SalpSnakeConfig, load_env_config
 from .spaces import batch_space, single_action_space, single_observation_space
@@ -47,8 +47,9 @@ def _as_config(cfg: ConfigLike, **overrides) -> SalpSnakeConfig:
     return SalpSnakeConfig(**{**cfg, **overrides})
 
 
-class SalpVectorEnv(ArrayBackend):
+class SalpVectorEnv(ArrayBackend, PolicyCache):
     metadata = {"render_modes": [], "autoreset_mode": "same-step"}
+    _handle_class = _capi.PolicyHandle
 
     def __init__(self, config: ConfigLike = "single_food", num_envs: int = 4096, device: Union[str, int] = "cuda:0",
                  seed: int = 0, env_index_base: int = 0, output: str = "torch", **overrides):
@@ -112,14 +113,6 @@ class SalpVectorEnv(ArrayBackend):
             raise ValueError("horizon is required when actions is None")
         H = int(horizon)
         return None, self._buf("r_actions", (H, self.num_envs, self.act_dim), np.float32), H
-
-    def _policy_handle(self, policy):
-        """`policy` if it is a handle, else the handle made for that policy object at its first use (kept until close())."""
-        if isinstance(policy, _capi.PolicyHandle):
-            return policy
-        if id(policy) not in self._policy_cache:
-            self._policy_cache[id(policy)] = (policy, self.make_policy(policy))
-        return self._policy_cache[id(policy)][1]
 
     def _record_block(self, out, words):
         """The int32 [N, words] block of an evaluation call: `out` (a block, or the dict returned earlier) or a new one."""
@@ -267,9 +260,7 @@ class SalpVectorEnv(ArrayBackend):
         """An in-kernel policy of this env (`policy.MLPPolicy` or `policy.GaussianPolicy`, one policy or a population): a
         `_capi.PolicyHandle` for `rollout_policy` (a Gaussian one also for `sample=True`; it carries `noise_step`).  `handle.update(w, flags, stream)` takes new weights of the same shape in the public layout
         (`MLPPolicy.pack()`); with a device tensor and SALP_DEVICE_PTRS it is stream-ordered and allocates nothing."""
-        if (policy.obs_dim, policy.act_dim) != (self.obs_dim, self.act_dim):
-            raise ValueError(f"the policy maps {policy.obs_dim} -> {policy.act_dim}, this env {self.obs_dim} -> {self.act_dim}")
-        policy.check_envs(self.num_envs)
+        self._check_policy(policy)
         return self._lib.policy_create(policy, weights, 0 if weights is None else self._flags, self._stream)
 
     def rollout_policy(self, policy, horizon: int, want_actions: bool = True, out: Optional[dict] = None, sample: bool = False) -> dict:
