@@ -70,7 +70,7 @@ def test_the_block_holds_every_public_word_exactly_once(hidden):
     assert len(m) % 16 == 0
     used = m[m >= 0]
     assert np.array_equal(np.sort(used), np.arange(words)), "a public word is missing from the block or held twice"
-    # what csrc/salp_robot_policy.h reads: per hidden chunk of the first layer 16 biases, then 16 weights per input
+    # what policy_eval_impl<6, 3> of csrc/salp_policy.h reads: per hidden chunk of the first layer 16 biases, then 16 weights per input
     off = 0
     if hidden:
         h0, Wp, bp = hidden[0], 0, hidden[0] * 6

@@ -1,13 +1,18 @@
-// salp_policy.h — the in-kernel MLP policy of salp_vec_rollout_policy (include/salp_vec.h "Policy"): the device block's
-// layout, shared by the host (which builds it) and the rollout kernel (which evaluates it once per env-step).
+// salp_policy.h — the in-kernel MLP policy of salp_vec_rollout_policy and salp_robot_vec_rollout_policy (include/salp_vec.h
+// "Policy"): the device block's layout, shared by the host (which builds it) and the rollout kernels (which evaluate it:
+// the snake's once per env-step, the robot's once per breathing cycle), and the one evaluation function of both.  Two
+// shapes run: the snake's 24 observations and 1 or 2 action components, the robot's 6 and 3.
 //
 // Device block, 32-bit words:  [PH_WORDS header][policy 0][policy 1]...  each policy `stride` words, a multiple of 16, so
 // that every 16-word group below starts on a 64-byte boundary.  One policy (IN = obs_dim for the first layer, else the
 // width of the layer before):
 //   per hidden layer, per chunk c of 16 output units:   b[16 c .. 16 c + 15], then for i = 0 .. IN-1 the 16 weights
-//                                                        W[16 c + j][i], j = 0 .. 15        (16 (IN + 1) words per chunk)
-//   tail (16 words):                                     b_last[A], scale[A], shift[A], zero padding
+//                                                        W[16 c + j][i], j = 0 .. 15        (16 (IN + 1) words per chunk:
+//                                                        16 (obs_dim + 1) in the first layer, 400 or 112 words)
+//   tail (16 words):                                     b_last[A], scale[A], shift[A] in its first 3 A words (3, 6 or 9),
+//                                                        zero padding
 //   last layer, per action a:                            W_last[a][0 .. IN-1], zero-padded to a multiple of 16 words
+//                                                        (without a hidden layer: 24 -> 32, 6 -> 16)
 // A Gaussian policy (salp_policy_create_gaussian; header word PH_GAUSS then holds the value 1 — a mark for whoever inspects a block,
 // no kernel reads it: the host decides from its own record which kernels a policy may run) carries its log-std head behind that, in the
 // same form:
@@ -158,7 +163,7 @@ __device__ __forceinline__ void policy_chunk_regs(pol_float* wc, const float (&x
 
 // u[a] += sum_j W_last[a][16 c + j] relu'd[j]: the last layer's share of one chunk of its input
 template <int AD>
-__device__ __forceinline__ void policy_last_chunk(pol_float* wl, int row_stride, int c, const float (&v)[POLICY_CHUNK], float (&u)[2]) {
+__device__ __forceinline__ void policy_last_chunk(pol_float* wl, int row_stride, int c, const float (&v)[POLICY_CHUNK], float (&u)[AD]) {
 #pragma unroll
   for (int a = 0; a < AD; ++a) {
     const pol_v16 w = pol_load16(wl + a * row_stride + POLICY_CHUNK * c);
@@ -167,18 +172,53 @@ __device__ __forceinline__ void policy_last_chunk(pol_float* wl, int row_stride,
   }
 }
 
-// The action of one env from its observation row `x` (OD = 24 floats in registers).  `blk`: the device block;
-// `pol_off`: word offset of this wavefront's policy behind the header (wave-uniform).
-// SAMPLED: the tanh-Gaussian sample of include/salp_vec.h "Sampled actions" from the standard normal draws z0, z1; `logp`
-// receives its log-probability.  The mean's arithmetic is that of the deterministic evaluation, unit by unit.
-template <int OD, int AD, bool SAMPLED>
-__device__ __forceinline__ void policy_eval_impl(const float* blk, uint32_t pol_off, const float (&x)[OD], float& c0, float& c1,
-                                                 [[maybe_unused]] float z0, [[maybe_unused]] float z1, [[maybe_unused]] float& logp) {
-  static_assert(OD == 24, "the policy kernels exist for max_observed_food == 3");
+// This block's header through scalar loads: the address, the same in every lane, moved to scalar registers and into the
+// constant address space
+__device__ __forceinline__ pol_int* policy_block_header(const float* blk) {
   const uint64_t adr = (uint64_t)(uintptr_t)blk;
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)adr);
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(adr >> 32));
-  pol_int* hd = (pol_int*)(uintptr_t)(((uint64_t)hi << 32) | lo);
+  return (pol_int*)(uintptr_t)(((uint64_t)hi << 32) | lo);
+}
+
+// The tail's first 3 AD words (b_last, scale, shift; b_ls of the log-std tail) in the narrowest load that holds them
+template <int AD>
+__device__ __forceinline__ auto policy_load_tail(pol_float* p) {
+  if constexpr (3 * AD <= 8) return pol_load8(p); else return pol_load16(p);
+}
+
+// u[a] += sum_i W_last[a][i] x[i]: the last layer of a policy without hidden layers.  A row is its OD words zero-padded to
+// POLICY_ROW<OD>: one 16-word group, or 16 + 8 words of 32 for the snake's 24 observations
+template <int OD> constexpr int POLICY_ROW = (OD + POLICY_CHUNK - 1) / POLICY_CHUNK * POLICY_CHUNK;
+template <int OD, int AD>
+__device__ __forceinline__ void policy_last_rows(pol_float* wl, const float (&x)[OD], float (&u)[AD]) {
+#pragma unroll
+  for (int a = 0; a < AD; ++a) {
+    const pol_v16 wa = pol_load16(wl + a * POLICY_ROW<OD>);
+    if constexpr (OD <= 16) {
+#pragma unroll
+      for (int i = 0; i < OD; ++i) u[a] = __builtin_fmaf(wa[i], x[i], u[a]);
+    } else {
+      const pol_v8 wb = pol_load8(wl + a * POLICY_ROW<OD> + 16);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) u[a] = __builtin_fmaf(wa[i], x[i], u[a]);
+#pragma unroll
+      for (int i = 0; i < OD - 16; ++i) u[a] = __builtin_fmaf(wb[i], x[16 + i], u[a]);
+    }
+  }
+}
+
+// The action of one env from its observation row `x` (OD floats in registers).  `blk`: the device block; `pol_off`: word
+// offset of this wavefront's policy behind the header (wave-uniform).  The scalar loads serve whichever lanes are on.
+// SAMPLED: the tanh-Gaussian sample of include/salp_vec.h "Sampled actions" from the standard normal draws z[a]; `logp`
+// receives its log-probability.  The mean's arithmetic is that of the deterministic evaluation, unit by unit.
+template <int OD, int AD, bool SAMPLED>
+__device__ __forceinline__ void policy_eval_impl(const float* blk, uint32_t pol_off, const float (&x)[OD], float (&act)[AD],
+                                                 [[maybe_unused]] const float (&z)[AD], [[maybe_unused]] float& logp) {
+  static_assert(OD == 24 || OD <= POLICY_CHUNK, "a last-layer row without hidden layers is read as 16 + 8 words (24 observations) or as one 16-word group");
+  static_assert(OD != 24 || AD <= 2, "24 observations are the snake's (max_observed_food == 3): 1 or 2 action components");
+  static_assert(3 * AD <= POLICY_TAIL_WORDS, "b_last, scale and shift share the tail's one 16-word group");
+  pol_int* hd = policy_block_header(blk);
   asm volatile("" : "+s"(hd));
   const int nh = hd[PH_NHIDDEN], h0 = hd[PH_H0], h1 = hd[PH_H1], out_act = hd[PH_OUT];
   pol_float* w = (pol_float*)hd + PH_WORDS + (uint32_t)__builtin_amdgcn_readfirstlane((int)pol_off);
@@ -188,40 +228,24 @@ __device__ __forceinline__ void policy_eval_impl(const float* blk, uint32_t pol_
   const int l1_words = c1n * POLICY_CHUNK * (h0 + 1);
   pol_float* tail = w + (nh >= 1 ? l0_words : 0) + (nh >= 2 ? l1_words : 0);
   pol_float* wl = tail + POLICY_TAIL_WORDS;
-  const pol_v8 tl = pol_load8(tail);      // b_last[AD], scale[AD], shift[AD]
-  float u[2] = {tl[0], AD == 2 ? tl[1] : 0.f};
-  [[maybe_unused]] float ls[2] = {0.f, 0.f};        // SAMPLED: the log-std head's sums
+  const auto tl = policy_load_tail<AD>(tail);      // b_last[AD], scale[AD], shift[AD]
+  float u[AD];
+#pragma unroll
+  for (int a = 0; a < AD; ++a) u[a] = tl[a];
+  [[maybe_unused]] float ls[AD];                   // SAMPLED: the log-std head's sums
   [[maybe_unused]] pol_float* wl2 = wl;
   if constexpr (SAMPLED) {
-    const int rs = nh == 0 ? 2 * POLICY_CHUNK : (nh == 1 ? h0 : h1);      // row stride of the last layer
+    const int rs = nh == 0 ? POLICY_ROW<OD> : (nh == 1 ? h0 : h1);      // row stride of the last layer
     pol_float* tail2 = wl + AD * rs;
     wl2 = tail2 + POLICY_TAIL_WORDS;
-    const pol_v8 t2 = pol_load8(tail2);    // b_ls[AD]
-    ls[0] = t2[0];
-    if (AD == 2) ls[1] = t2[1];
+    const auto t2 = policy_load_tail<AD>(tail2);   // b_ls[AD]
+#pragma unroll
+    for (int a = 0; a < AD; ++a) ls[a] = t2[a];
   }
 
   if (nh == 0) {
-#pragma unroll
-    for (int a = 0; a < AD; ++a) {
-      const pol_v16 wa = pol_load16(wl + a * 32);
-      const pol_v8 wb = pol_load8(wl + a * 32 + 16);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) u[a] = __builtin_fmaf(wa[i], x[i], u[a]);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) u[a] = __builtin_fmaf(wb[i], x[16 + i], u[a]);
-    }
-    if constexpr (SAMPLED) {
-#pragma unroll
-      for (int a = 0; a < AD; ++a) {
-        const pol_v16 wa = pol_load16(wl2 + a * 32);
-        const pol_v8 wb = pol_load8(wl2 + a * 32 + 16);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) ls[a] = __builtin_fmaf(wa[i], x[i], ls[a]);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) ls[a] = __builtin_fmaf(wb[i], x[16 + i], ls[a]);
-      }
-    }
+    policy_last_rows<OD, AD>(wl, x, u);
+    if constexpr (SAMPLED) policy_last_rows<OD, AD>(wl2, x, ls);
   } else if (nh == 1) {
 #pragma unroll 1
     for (int c = 0; c < c0n; ++c) {
@@ -273,42 +297,54 @@ __device__ __forceinline__ void policy_eval_impl(const float* blk, uint32_t pol_
       if constexpr (SAMPLED) policy_last_chunk<AD>(wl2, h1, c, acc, ls);
     }
   }
+  // How the results are passed: the snake's are formed in u[] and copied out, the robot's go to act[] as they are formed.
+  // Each kernel's machine code changes when it is written the other one's way (profiles/robot_rollout_notes.md).
+  float (&r)[AD] = OD == 24 ? u : act;
   if constexpr (SAMPLED) {
     // a Gaussian policy's output activation is tanh (salp_policy_create_gaussian); the log-probability's terms are added
     // in component order, each a fixed sequence of fp32 roundings (include/salp_vec.h "Sampled actions")
     float lp = 0.f;
 #pragma unroll
     for (int a = 0; a < AD; ++a) {
-      const float z = a == 0 ? z0 : z1;
       const float l = fminf(fmaxf(ls[a], -20.0f), 2.0f);
       const float sd = expf(l);
-      const float s = __builtin_fmaf(sd, z, u[a]);
+      const float s = __builtin_fmaf(sd, z[a], u[a]);
       const float m2 = -2.0f * s;
       const float sp = fmaxf(m2, 0.f) + log1pf(expf(-fabsf(m2)));
       const float c = (0.693147180559945309f - s) - sp;
-      float g = -0.5f * (z * z);
+      float g = -0.5f * (z[a] * z[a]);
       g = g - l;
       g = g - 0.918938533204672742f;
       g = g - 2.0f * c;
       lp = lp + g;
-      u[a] = tanhf(s) * tl[AD + a] + tl[2 * AD + a];
+      r[a] = tanhf(s) * tl[AD + a] + tl[2 * AD + a];
     }
     logp = lp;
   } else {
 #pragma unroll
     for (int a = 0; a < AD; ++a) {
       const float v = out_act ? fminf(fmaxf(u[a], -1.0f), 1.0f) : tanhf(u[a]);
-      u[a] = v * tl[AD + a] + tl[2 * AD + a];
+      r[a] = v * tl[AD + a] + tl[2 * AD + a];
     }
   }
-  c0 = u[0];
-  if (AD == 2) c1 = u[1];
+  if constexpr (OD == 24) {
+#pragma unroll
+    for (int a = 0; a < AD; ++a) act[a] = u[a];
+  }
 }
 
 template <int OD, int AD>
-__device__ __forceinline__ void policy_eval(const float* blk, uint32_t pol_off, const float (&x)[OD], float& c0, float& c1) {
+__device__ __forceinline__ void policy_eval(const float* blk, uint32_t pol_off, const float (&x)[OD], float (&act)[AD]) {
+  const float z[AD] = {};
   float unused = 0.f;
-  policy_eval_impl<OD, AD, false>(blk, pol_off, x, c0, c1, 0.f, 0.f, unused);
+  policy_eval_impl<OD, AD, false>(blk, pol_off, x, act, z, unused);
+}
+
+// The sampled action and its log-probability from the draws z (one per component)
+template <int OD, int AD>
+__device__ __forceinline__ void policy_eval_sampled(const float* blk, uint32_t pol_off, const float (&x)[OD], const float (&z)[AD],
+                                                    float (&act)[AD], float& logp) {
+  policy_eval_impl<OD, AD, true>(blk, pol_off, x, act, z, logp);
 }
 
 // One standard normal draw from two words of the policy's noise block (include/salp_vec.h "Randomness"): Box-Muller on

@@ -28,7 +28,7 @@
 #include "salp_robot_params.h"   // RobotParams, kPi, kMaxCycleTime, kSchedBins, the action scales and rates, schedule_bin
 #include "salp_philox.h"         // philox4x32_10, u53
 #include "salp_fp64_math.h"      // sincos_small, sincos_euler, advance_euler_sincos, rcp_nr, sqrt_nr
-#include "salp_robot_policy.h"   // robot_policy_eval and the policy block's header words (salp_policy.h)
+#include "salp_policy.h"         // policy_eval, policy_eval_sampled and the policy block's header words
 
 namespace {
 
@@ -335,7 +335,7 @@ void salp_robot_trajectory_kernel(RobotParams P0, RobotTrajectory J) {
 // ---- multi-cycle rollout (salp_robot_vec_rollout, salp_robot_vec_rollout_policy, _policy_sampled) ------
 // H env steps — H breathing cycles per robot — in one launch, env i on lane i, the robot in registers throughout; the
 // actions are read (kActRead) or computed by the in-kernel MLP policy from the row the step before wrote (kActPolicy; or
-// sampled from its Gaussian form, kActPolicySampled; salp_robot_policy.h).  ONE loop over Euler iterations serves the whole launch.  Every lane carries its own step index
+// sampled from its Gaussian form, kActPolicySampled; salp_policy.h).  ONE loop over Euler iterations serves the whole launch.  Every lane carries its own step index
 // t, its cycle (cycle_time, total and what the cycle pieces leave) and whether a cycle is in progress; a lane whose cycle
 // is over and whose t is below H is DUE.  At a service point the due lanes, under EXEC masking, finish env step t
 // (salp_robot_step_finish.h / _outputs.h: reward, flags, final_obs, autoreset, the stores of row t), advance t and, if
@@ -367,6 +367,7 @@ struct RobotRollout {
 // whichever iteration the lane is served on — and stores the sampled action and its log-probability for step t.
 enum { kActRead = 0, kActPolicy = 1, kActPolicySampled = 2 };
 enum { kRobotNoiseStream = 3 };     // fourth counter word of component 0 / 1's block; component 2's is one above
+enum { ROBOT_POLICY_OBS = 6, ROBOT_POLICY_ACT = 3 };     // the policy's shape: salp_policy.h with 6 inputs and 3 components
 
 // what the opening of a cycle leaves for the Euler steps of that cycle (the names of the cycle pieces)
 struct RobotCycle {
@@ -407,10 +408,7 @@ void salp_robot_rollout_kernel(RobotParams P, RobotState S, RobotRollout J) {
   if constexpr (ACT == kActPolicySampled) {
     // the two PH_NOISE words, scalar loads through the constant address space like the weights (salp_policy.h); only the
     // low word enters the draw: n is the low 32 bits of n0 + t, and t < 2^31
-    const uint64_t adr = (uint64_t)(uintptr_t)J.act;
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)adr);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(adr >> 32));
-    pol_int* hd = (pol_int*)(uintptr_t)(((uint64_t)hi << 32) | lo);
+    pol_int* hd = policy_block_header(J.act);
     const uint64_t n0 = ((uint64_t)(uint32_t)hd[PH_NOISE + 1] << 32) | (uint32_t)hd[PH_NOISE];
     noise0 = (uint32_t)n0;
   }
@@ -467,30 +465,28 @@ void salp_robot_rollout_kernel(RobotParams P, RobotState S, RobotRollout J) {
         if (t < horizon) {
           // the action of step t: of the row just written (the entry observation for t = 0), or read
           float a[3];
-          if constexpr (ACT == kActPolicy) {
+          if constexpr (ACT == kActPolicy || ACT == kActPolicySampled) {
             float x[6];
             observe_robot(r, x);
-            robot_policy_eval<ROBOT_POLICY_OBS, ROBOT_POLICY_ACT>(J.act, pol_off, x, a);
+            [[maybe_unused]] float lp;
+            if constexpr (ACT == kActPolicySampled) {
+              // the draws of (env, step t): components 0 and 1 from the block of stream word 3, component 2 from the first
+              // two words of the block of stream word 4 (include/salp_robot_sampled.h); the env's own counter is not consumed
+              const uint32_t nt = noise0 + (uint32_t)t;
+              const U4 w0 = philox4x32_10((uint32_t)genv, (uint32_t)(genv >> 32), nt, (uint32_t)kRobotNoiseStream, P.seed_lo, P.seed_hi);
+              const U4 w1 = philox4x32_10((uint32_t)genv, (uint32_t)(genv >> 32), nt, (uint32_t)kRobotNoiseStream + 1u, P.seed_lo, P.seed_hi);
+              const float z[3] = {policy_normal(w0.x, w0.y), policy_normal(w0.z, w0.w), policy_normal(w1.x, w1.y)};
+              policy_eval_sampled<ROBOT_POLICY_OBS, ROBOT_POLICY_ACT>(J.act, pol_off, x, z, a, lp);
+            } else {
+              policy_eval<ROBOT_POLICY_OBS, ROBOT_POLICY_ACT>(J.act, pol_off, x, a);
+            }
             if (J.act_out) {
               float* ao = J.act_out + ((int64_t)t * n + i) * 3;
               ao[0] = a[0]; ao[1] = a[1]; ao[2] = a[2];
             }
-          } else if constexpr (ACT == kActPolicySampled) {
-            float x[6];
-            observe_robot(r, x);
-            // the draws of (env, step t): components 0 and 1 from the block of stream word 3, component 2 from the first
-            // two words of the block of stream word 4 (include/salp_robot_sampled.h); the env's own counter is not consumed
-            const uint32_t nt = noise0 + (uint32_t)t;
-            const U4 w0 = philox4x32_10((uint32_t)genv, (uint32_t)(genv >> 32), nt, (uint32_t)kRobotNoiseStream, P.seed_lo, P.seed_hi);
-            const U4 w1 = philox4x32_10((uint32_t)genv, (uint32_t)(genv >> 32), nt, (uint32_t)kRobotNoiseStream + 1u, P.seed_lo, P.seed_hi);
-            const float z[3] = {policy_normal(w0.x, w0.y), policy_normal(w0.z, w0.w), policy_normal(w1.x, w1.y)};
-            float lp;
-            robot_policy_eval_sampled<ROBOT_POLICY_OBS, ROBOT_POLICY_ACT>(J.act, pol_off, x, z, a, lp);
-            if (J.act_out) {
-              float* ao = J.act_out + ((int64_t)t * n + i) * 3;
-              ao[0] = a[0]; ao[1] = a[1]; ao[2] = a[2];
+            if constexpr (ACT == kActPolicySampled) {
+              if (J.logp_out) J.logp_out[(int64_t)t * n + i] = lp;
             }
-            if (J.logp_out) J.logp_out[(int64_t)t * n + i] = lp;
           } else {
             const float* ai = J.act + ((int64_t)t * n + i) * 3;
             a[0] = ai[0]; a[1] = ai[1]; a[2] = ai[2];

@@ -114,6 +114,16 @@ constexpr bool kExpStoreOnly = false;
 #define SALP_RARE_TAKEN(cond) __any(cond)
 #endif
 
+// The kernel's action variables from the array that policy_eval (salp_policy.h) fills.  A function, not two assignments,
+// on purpose: a0 and a1 then stay address-taken until the inliner has run, as they were when policy_eval took them by
+// reference, and the kernels keep the order of their loop-carried values and with it their machine code
+// (profiles/robot_rollout_notes.md "One evaluation function").
+template <int AD>
+__device__ __forceinline__ void take_actions(const float (&av)[AD], float& a0, float& a1) {
+  a0 = av[0];
+  if (AD == 2) a1 = av[1];
+}
+
 // The kernel.  What each switch of T means, and why it has its value: RolloutTraits (salp_rollout_traits.h).  The order of
 // events: the launch geometry, the tile and its flush plan; load the state; load the record (SUMMARY / NAV); the first action;
 // the loop — action, step, per-step outputs, record update, rare region, observation, flush, next action; store the state and
@@ -345,12 +355,16 @@ __global__ __launch_bounds__(kBlock, (RolloutTraits<FMAX, KMAX, FORCED, STD, SIG
         }
         observe<FMAX, KMAX, STD>(e, P, r0, have_rel0, rel0, ob0);
       }
+      float av[AD];
       if constexpr (T::SAMPLED) {
         const U4 nw = philox4x32_10((uint32_t)genv, (uint32_t)(genv >> 32), noise0, 3u, P.seed[0], P.seed[1]);
-        policy_eval_impl<T::OBS, FORCED ? 1 : 2, true>(io.act, pol_off, ob0, a0, a1, policy_normal(nw.x, nw.y),
-                                                               FORCED ? 0.f : policy_normal(nw.z, nw.w), lp);
+        float zv[AD];
+        zv[0] = policy_normal(nw.x, nw.y);
+        if constexpr (!FORCED) zv[1] = policy_normal(nw.z, nw.w);
+        policy_eval_sampled<T::OBS, AD>(io.act, pol_off, ob0, zv, av, lp);
       } else
-      policy_eval<T::OBS, FORCED ? 1 : 2>(io.act, pol_off, ob0, a0, a1);
+      policy_eval<T::OBS, AD>(io.act, pol_off, ob0, av);
+      take_actions(av, a0, a1);
     }
   }
   // Everything loaded so far is complete before the loop is entered: otherwise the waitcnt pass keeps
@@ -704,14 +718,18 @@ __global__ __launch_bounds__(kBlock, (RolloutTraits<FMAX, KMAX, FORCED, STD, SIG
       }
       // the next step's action from this step's row, while the row stores are in flight (the last step needs none)
       if constexpr (T::POLICY) {
-        if constexpr (T::SAMPLED) {
-          if (T::SUMMARY || t + 1 < Hrun) {
+        if (T::SUMMARY || t + 1 < Hrun) {
+          float av[AD];
+          if constexpr (T::SAMPLED) {
             const U4 nw = philox4x32_10((uint32_t)genv, (uint32_t)(genv >> 32), noise0 + (uint32_t)(t + 1), 3u, P.seed[0], P.seed[1]);
-            policy_eval_impl<T::OBS, FORCED ? 1 : 2, true>(io.act, pol_off, ob, a0, a1, policy_normal(nw.x, nw.y),
-                                                                   FORCED ? 0.f : policy_normal(nw.z, nw.w), lp);
-          }
-        } else
-        if (T::SUMMARY || t + 1 < Hrun) policy_eval<T::OBS, FORCED ? 1 : 2>(io.act, pol_off, ob, a0, a1);
+            float zv[AD];
+            zv[0] = policy_normal(nw.x, nw.y);
+            if constexpr (!FORCED) zv[1] = policy_normal(nw.z, nw.w);
+            policy_eval_sampled<T::OBS, AD>(io.act, pol_off, ob, zv, av, lp);
+          } else
+          policy_eval<T::OBS, AD>(io.act, pol_off, ob, av);
+          take_actions(av, a0, a1);
+        }
       }
     }
     // One-food kernel (write-bound): drain this step's stores before the next step.  Measured
