@@ -7,41 +7,32 @@ the list of literal constants (SALP_STD_CONSTS) that StdConsts and is_std() are 
 import ctypes
 import os
 import re
-import subprocess
 
+import native_lib
+from native_lib import cint, dbl, i64, ptr, text, u64, vp
 from underwater_swimmer_rl_amd.config import CConfig
 
-_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_SO = os.path.join(_ROOT, "oracle", "libsalp_params_host.so")
-_II = os.path.join(_ROOT, "oracle", "salp_params_host.ii")
+_II = os.path.join(native_lib.ORACLE_DIR, "salp_params_host.ii")     # made with the library
 
-_lib = None
+
+# every function tests/params_host.cpp exports, in its order
+PROTOTYPES = {
+    "salp_params_host_default": (None, [ptr(CConfig)]),
+    "salp_params_host_validate": (cint, [ptr(CConfig), ptr(text)]),
+    "salp_params_host_sizeof": (cint, []),
+    "salp_params_host_make": (None, [ptr(CConfig), i64, i64, u64, i64, vp]),
+    "salp_params_host_is_std": (cint, [vp]),
+    "salp_params_host_const_count": (cint, []),
+    "salp_params_host_const_type": (text, [cint]),
+    "salp_params_host_const_name": (text, [cint]),
+    "salp_params_host_const_text": (text, [cint]),
+    "salp_params_host_const_literal": (dbl, [cint]),
+    "salp_params_host_const_value": (dbl, [vp, cint]),
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        deps = [os.path.join(_ROOT, "tests", "params_host.cpp"), os.path.join(_ROOT, "include", "salp_vec.h"),
-                os.path.join(_ROOT, "underwater-swimmer_rl_amd", "csrc", "salp_params.h")]
-        if not (os.path.isfile(_SO) and os.path.isfile(_II)) or os.path.getmtime(_SO) < max(os.path.getmtime(d) for d in deps):
-            subprocess.run(["make", "-C", os.path.join(_ROOT, "oracle"), "-s", "-B", "libsalp_params_host.so"], check=True)
-        L = ctypes.CDLL(_SO)
-        vp, cfg = ctypes.c_void_p, ctypes.POINTER(CConfig)
-        L.salp_params_host_default.argtypes = [cfg]
-        L.salp_params_host_default.restype = None
-        L.salp_params_host_validate.argtypes = [cfg, ctypes.POINTER(ctypes.c_char_p)]
-        L.salp_params_host_make.argtypes = [cfg, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64, vp]
-        L.salp_params_host_make.restype = None
-        L.salp_params_host_is_std.argtypes = [vp]
-        for f in ("type", "name", "text"):
-            getattr(L, "salp_params_host_const_" + f).argtypes = [ctypes.c_int]
-            getattr(L, "salp_params_host_const_" + f).restype = ctypes.c_char_p
-        L.salp_params_host_const_literal.argtypes = [ctypes.c_int]
-        L.salp_params_host_const_literal.restype = ctypes.c_double
-        L.salp_params_host_const_value.argtypes = [vp, ctypes.c_int]
-        L.salp_params_host_const_value.restype = ctypes.c_double
-        _lib = L
-    return _lib
+    return native_lib.load("libsalp_params_host.so", PROTOTYPES)
 
 
 def default_config() -> CConfig:

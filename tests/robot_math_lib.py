@@ -1,39 +1,30 @@
 """ctypes bindings of the robot kernels' fp64 primitives — TEST INFRASTRUCTURE.
 
-host(function, ...)    oracle/libsalp_math_host.so: tests/robot_math_host.cpp, csrc/salp_fp64_math.h compiled for the host
+host(function, ...)    oracle/libsalp_robot_math_host.so: tests/robot_math_host.cpp, csrc/salp_fp64_math.h compiled for the host
 device(function, ...)  salp_robot_math_probe of libsalp_hip.so: the same header on the GPU, element i on thread i
 Both take and return float64 arrays in the layouts listed in csrc/salp_fp64_math.h.
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_SO = os.path.join(_ROOT, "oracle", "libsalp_math_host.so")
+import native_lib
+from native_lib import cint, dbl, i32, i64, vp
 
 SINCOS_SMALL, SINCOS_EULER, ROTATE, CHAIN, RCP_NR, SQRT_NR = range(6)
 _ROWS_OUT = {SINCOS_SMALL: 2, SINCOS_EULER: 2, ROTATE: 2, CHAIN: 3, RCP_NR: 1, SQRT_NR: 1}
 WAVE = 64
 
-_lib = None
+# every function tests/robot_math_host.cpp exports, in its order
+PROTOTYPES = {
+    "salp_math_host_rotate_max_step": (dbl, []),
+    "salp_math_host_euler_fold_above": (dbl, []),
+    "salp_math_host": (cint, [cint, vp, vp, i64, i32, vp]),
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        deps = [os.path.join(_ROOT, "tests", "robot_math_host.cpp"),
-                os.path.join(_ROOT, "underwater-swimmer_rl_amd", "csrc", "salp_fp64_math.h")]
-        if not os.path.isfile(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(d) for d in deps):
-            subprocess.run(["make", "-C", os.path.join(_ROOT, "oracle"), "-s", "libsalp_math_host.so"], check=True)
-        L = ctypes.CDLL(_SO)
-        vp = ctypes.c_void_p
-        L.salp_math_host.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int64, ctypes.c_int32, vp]
-        L.salp_math_host_rotate_max_step.restype = ctypes.c_double
-        L.salp_math_host_euler_fold_above.restype = ctypes.c_double
-        _lib = L
-    return _lib
+    return native_lib.load("libsalp_robot_math_host.so", PROTOTYPES)
 
 
 def rotate_max_step() -> float:
@@ -68,8 +59,7 @@ def host(function, arrays, steps=0, want_exact_steps=False):
 def device(function, arrays, steps=0, device_id=0):
     from underwater_swimmer_rl_amd import _capi
     L = _capi.load_library()
-    vp = ctypes.c_void_p
-    L.salp_robot_math_probe.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int64, ctypes.c_int32]
+    L.salp_robot_math_probe.argtypes = [cint, cint, vp, vp, i64, i32]
     L.salp_robot_last_error.restype = ctypes.c_char_p
     a, n, out = _args(function, arrays, steps)
     rc = L.salp_robot_math_probe(device_id, function, a.ctypes.data, out.ctypes.data, n, steps)

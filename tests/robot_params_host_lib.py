@@ -7,54 +7,43 @@ history_capacity(), check_history_args(), check_trajectory_args(), schedule_bin(
 (SALP_ROBOT_PHYS) that the copy, the trajectory kernel's table load and the row check are generated from.
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
+import native_lib
+from native_lib import cint, dbl, i32, i64, ptr, text, u32, u64, vp
 from underwater_swimmer_rl_amd._capi import CRobotConfig
 
-_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_SO = os.path.join(_ROOT, "oracle", "libsalp_robot_params_host.so")
 DERIVED = ("dt", "x_min", "x_span", "y_min", "y_span", "max_cycles", "seed_lo", "seed_hi", "env_base", "n", "pitch")
 CONSTANTS = ("kPi", "kActContraction", "kActCoast", "kActYaw", "kContractRate", "kReleaseRate", "kMaxCycleTime", "kSchedBins",
              "kMaxHistorySteps")
 
-_lib = None
+
+
+# every function tests/robot_params_host.cpp exports, in its order
+PROTOTYPES = {
+    "salp_robot_params_host_config_sizeof": (cint, []),
+    "salp_robot_params_host_default": (None, [ptr(CRobotConfig)]),
+    "salp_robot_params_host_check_create": (cint, [ptr(CRobotConfig), i64, i64, ptr(text)]),
+    "salp_robot_params_host_phys_count": (cint, []),
+    "salp_robot_params_host_phys_field": (text, [cint]),
+    "salp_robot_params_host_phys_row": (text, [cint]),
+    "salp_robot_params_host_phys_member": (text, [cint]),
+    "salp_robot_params_host_phys_row_value": (cint, [cint]),
+    "salp_robot_params_host_make_count": (cint, []),
+    "salp_robot_params_host_make": (None, [ptr(CRobotConfig), i64, u64, i64, vp]),
+    "salp_robot_params_host_constants": (None, [vp]),
+    "salp_robot_params_host_max_steps": (i64, [dbl]),
+    "salp_robot_params_host_history_capacity": (i64, [i64, i32]),
+    "salp_robot_params_host_check_history": (cint, [i64, i64, i64, i64, i32, i32, vp, u32, ptr(cint), text, cint]),
+    "salp_robot_params_host_check_trajectory": (cint, [i64, i32, u32, cint, cint, text, cint]),
+    "salp_robot_params_host_max_trajectory_cycles": (cint, []),
+    "salp_robot_params_host_schedule_bins": (None, [vp, i64, vp]),
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        deps = [os.path.join(_ROOT, "tests", "robot_params_host.cpp"), os.path.join(_ROOT, "include", "salp_robot.h"),
-                os.path.join(_ROOT, "include", "salp_vec.h"),
-                os.path.join(_ROOT, "underwater-swimmer_rl_amd", "csrc", "salp_robot_params.h")]
-        if not os.path.isfile(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(d) for d in deps):
-            subprocess.run(["make", "-C", os.path.join(_ROOT, "oracle"), "-s", "-B", "libsalp_robot_params_host.so"], check=True)
-        L = ctypes.CDLL(_SO)
-        vp, cfg, i64, i32, u32 = ctypes.c_void_p, ctypes.POINTER(CRobotConfig), ctypes.c_int64, ctypes.c_int32, ctypes.c_uint32
-        L.salp_robot_params_host_default.argtypes = [cfg]
-        L.salp_robot_params_host_default.restype = None
-        L.salp_robot_params_host_check_create.argtypes = [cfg, i64, i64, ctypes.POINTER(ctypes.c_char_p)]
-        for f in ("field", "row", "member"):
-            getattr(L, "salp_robot_params_host_phys_" + f).argtypes = [ctypes.c_int]
-            getattr(L, "salp_robot_params_host_phys_" + f).restype = ctypes.c_char_p
-        L.salp_robot_params_host_phys_row_value.argtypes = [ctypes.c_int]
-        L.salp_robot_params_host_make.argtypes = [cfg, i64, ctypes.c_uint64, i64, vp]
-        L.salp_robot_params_host_make.restype = None
-        L.salp_robot_params_host_constants.argtypes = [vp]
-        L.salp_robot_params_host_constants.restype = None
-        L.salp_robot_params_host_max_steps.argtypes = [ctypes.c_double]
-        L.salp_robot_params_host_max_steps.restype = i64
-        L.salp_robot_params_host_history_capacity.argtypes = [i64, i32]
-        L.salp_robot_params_host_history_capacity.restype = i64
-        L.salp_robot_params_host_check_history.argtypes = [i64, i64, i64, i64, i32, i32, vp, u32, ctypes.POINTER(ctypes.c_int),
-                                                           ctypes.c_char_p, ctypes.c_int]
-        L.salp_robot_params_host_check_trajectory.argtypes = [i64, i32, u32, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
-        L.salp_robot_params_host_schedule_bins.argtypes = [vp, i64, vp]
-        L.salp_robot_params_host_schedule_bins.restype = None
-        _lib = L
-    return _lib
+    return native_lib.load("libsalp_robot_params_host.so", PROTOTYPES)
 
 
 def config_sizeof() -> int:

@@ -1,39 +1,26 @@
 """ctypes bindings of the robot rollout's argument checks on the host — TEST INFRASTRUCTURE.
 
-tests/robot_rollout_host.cpp is csrc/salp_robot_params.h compiled as plain C++ (g++, the flags of oracle/Makefile's host
-twins; the library is built next to them, into oracle/).  What salp_robot_vec_rollout and salp_robot_vec_rollout_policy
-decide before they touch a GPU is callable here without one: check_rollout_args(), rollout_max_iters() and the constants.
+oracle/libsalp_robot_rollout_host.so is tests/robot_rollout_host.cpp: csrc/salp_robot_params.h compiled as plain C++.  What
+salp_robot_vec_rollout and salp_robot_vec_rollout_policy decide before they touch a GPU is callable here without one:
+check_rollout_args(), rollout_max_iters() and the constants.
 """
 import ctypes
-import os
-import subprocess
 
-_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_SRC = os.path.join(_ROOT, "tests", "robot_rollout_host.cpp")
-_SO = os.path.join(_ROOT, "oracle", "libsalp_robot_rollout_host.so")
-CXXFLAGS = ["-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wextra"]
+import native_lib
+from native_lib import cint, dbl, i32, i64, ptr, text, u32
 
-_lib = None
+# every function tests/robot_rollout_host.cpp exports, in its order
+PROTOTYPES = {
+    "salp_robot_rollout_host_check": (cint, [i64, i32, u32, cint, cint, text, cint]),
+    "salp_robot_rollout_host_max_cycles": (cint, []),
+    "salp_robot_rollout_host_max_iters": (i64, [i32, i64, cint]),
+    "salp_robot_rollout_host_max_steps": (i64, [dbl]),
+    "salp_robot_rollout_host_periods": (cint, [ptr(i32), cint, ptr(i32)]),
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        deps = [_SRC, os.path.join(_ROOT, "include", "salp_robot.h"), os.path.join(_ROOT, "include", "salp_robot_rollout.h"),
-                os.path.join(_ROOT, "include", "salp_vec.h"),
-                os.path.join(_ROOT, "underwater-swimmer_rl_amd", "csrc", "salp_robot_params.h")]
-        if not os.path.isfile(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(d) for d in deps):
-            subprocess.run([os.environ.get("CXX", "g++")] + CXXFLAGS + ["-shared", "-o", _SO, _SRC, "-lm"], check=True)
-        L = ctypes.CDLL(_SO)
-        i64, i32, u32 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint32
-        L.salp_robot_rollout_host_check.argtypes = [i64, i32, u32, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
-        L.salp_robot_rollout_host_max_iters.argtypes = [i32, i64, ctypes.c_int]
-        L.salp_robot_rollout_host_max_iters.restype = i64
-        L.salp_robot_rollout_host_max_steps.argtypes = [ctypes.c_double]
-        L.salp_robot_rollout_host_max_steps.restype = i64
-        L.salp_robot_rollout_host_periods.argtypes = [ctypes.POINTER(i32), ctypes.c_int, ctypes.POINTER(i32)]
-        _lib = L
-    return _lib
+    return native_lib.load("libsalp_robot_rollout_host.so", PROTOTYPES)
 
 
 def check_rollout(max_steps, horizon, flags=0, source=True, main_output=True, msg_size=200):
