@@ -6,7 +6,12 @@ generations (`handle.update`, no re-allocation).  A policy is a = clip(W obs + b
 (contraction, coast time, nozzle yaw), 21 parameters; its score is the mean over its robots of the summed reward (progress
 towards the target, heading, the bonus for reaching it).  No pass threshold: it prints the scores per generation and the
 score of a policy that always jets straight ahead, on the same episodes.  Needs the GPU.
-    python examples/evaluate_robot_policy.py [--policies P] [--robots-per-policy E] [--generations G] [--cycles T]"""
+`--whole-episodes` scores a policy the way the reference's test_robot.py does — one episode per robot, run to its end, at
+most 500 cycles — with `evaluate_policy(handle, 500, first_episode=True)`: no per-step output, one summary record per
+robot, and a robot whose episode has ended is not simulated any further.  It prints the mean first-episode return, the
+fraction of robots that reached their target and the Euler steps spent.
+    python examples/evaluate_robot_policy.py [--policies P] [--robots-per-policy E] [--generations G] [--cycles T]
+                                             [--whole-episodes]"""
 import argparse
 import os
 import sys
@@ -35,6 +40,7 @@ def main():
     ap.add_argument("--generations", type=int, default=6)
     ap.add_argument("--cycles", type=int, default=24)
     ap.add_argument("--elite", type=float, default=0.125)
+    ap.add_argument("--whole-episodes", action="store_true", help="score by each robot's first whole episode (at most 500 cycles)")
     args = ap.parse_args()
     P, E, T = args.policies, args.robots_per_policy, args.cycles
     env = SalpRobotVectorEnv(num_envs=P * E, seed=0)
@@ -48,6 +54,15 @@ def main():
         out = env.rollout_policy(handle, T, want_actions=False)
         return out["reward"].sum(0).view(P, E).mean(1), int(out["inner_steps"].sum())
 
+    def episode_scores():
+        env.reset()
+        v = env.evaluate_policy(handle, 500, first_episode=True)
+        print(f"    whole episodes: mean first-episode return {float(v['first_return'].mean()):8.2f}, reached "
+              f"{float((v['first_end'] == 1).double().mean()):.3f}, {int(v['euler_steps'].sum())} Euler steps", flush=True)
+        return v["first_return"].view(P, E).mean(1).float(), int(v["euler_steps"].sum())
+
+    if args.whole_episodes:
+        scores, T = episode_scores, 500
     n_elite = max(2, int(args.elite * P))
     t0, euler = time.perf_counter(), 0
     for g in range(args.generations):

@@ -32,7 +32,8 @@
  * and act_dim 3 — the same descriptor salp_policy_desc_t, the same public weight layout (per layer W[out][in] row-major,
  * then b[out]; then scale[3], shift[3]) and the same fixed fp32 arithmetic: every unit starts from its bias and adds its
  * inputs in index order with one fmaf each; relu; tanhf or the clamp to [-1, 1]; one multiply by scale, one add of shift.
- * The Gaussian head and sampled actions are declared in salp_robot_sampled.h.
+ * The Gaussian head and sampled actions are declared in salp_robot_sampled.h, the evaluation form of the closed loop (one
+ * summary record per robot and no per-step output) in salp_robot_evaluate.h.
  *   - the action of step 0 is the policy applied to the env's current observation: six float casts of the state, the row
  *     salp_robot_vec_reset with a zero mask returns.  The action of step t + 1 is the policy applied to the row written
  *     to obs[t] (after an autoreset: the first row of the new episode).  act_out (nullable) float [H][n][3] receives them.

@@ -25,7 +25,17 @@ with `want_actions=False`:
                       that the actions, the cycle lengths and the simulator's work are the mean run's and the difference is
                       what sampling itself costs: two Philox blocks, three Box-Muller draws, the log-std head, the
                       log-probability and the logp store
-    sampled, ls = -1  log-std biases of -1: other actions, so other cycle lengths (printed) — what a learner would run"""
+    sampled, ls = -1  log-std biases of -1: other actions, so other cycle lengths (printed) — what a learner would run
+
+--evaluate [--envs 4096] [--parent-lib LIB.so] [--launches 25] [--episode-cycles 500] [--episode-launches 5]:
+salp_robot_vec_evaluate_policy (include/salp_robot_evaluate.h).  One GPU process; every launch is timed on its own with
+device events, the forms alternated, each env reset before each launch; a row reports the median, the spread
+(max - min) / median and the interquartile range / median.
+    row 1   the 64 x 64 policy, Box-wide coast: `rollout_policy(..., want_actions=False)["reward"].sum(0)` — on the library
+            given by --parent-lib, a build of the commit before the evaluation calls — against `evaluate_policy`; the row
+            also says whether the records were, bit for bit, `summarize_robot_rollout` of the per-step blocks
+    row 2   the population of examples/evaluate_robot_policy.py (64 linear policies x 64 robots) for 500 cycles:
+            `evaluate_policy` with and without `first_episode`, and the Euler steps each simulated"""
 import argparse
 import json
 import os
@@ -136,10 +146,102 @@ def sampled_rows(args):
     return rows
 
 
+def per_launch(forms, launches, before):
+    """forms: name -> callable; every launch timed on its own (device events), the forms alternated, `before(name)` ahead
+    of each.  Returns name -> (median ms, (max - min) / median, interquartile range / median, launches)."""
+    import torch
+    for name, run in forms.items():
+        before(name)
+        run()
+    torch.cuda.synchronize()
+    samples = {name: [] for name in forms}
+    for _ in range(launches):
+        for name, run in forms.items():
+            before(name)
+            samples[name].append(timed(run, 1))
+    out = {}
+    for name, v in samples.items():
+        q1, med, q3 = np.percentile(v, [25, 50, 75])
+        out[name] = (float(med), float((max(v) - min(v)) / med), float((q3 - q1) / med), launches)
+    return out
+
+
+def evaluate_rows(args):
+    """The rows of --evaluate (see the top of the file)."""
+    import torch
+    from underwater_swimmer_rl_amd import _capi
+    from underwater_swimmer_rl_amd.policy import MLPPolicy, summarize_robot_rollout
+    H, rows = args.horizon, []
+
+    def env_on(n, lib=None):
+        """An env on the library at `lib` (an older build: a library without the evaluation calls loads too)."""
+        if lib is None:
+            return make_env(n)
+        own, _capi._lib = _capi._lib, _capi.load_library(lib)
+        try:
+            return make_env(n)
+        finally:
+            _capi._lib = own
+
+    # (a) rollout_policy + reward.sum(0) against (b) evaluate_policy: 64 x 64 policy, same start, every launch timed alone
+    for n in (int(x) for x in args.envs.split(",")):
+        a_env, b_env = env_on(n, args.parent_lib), env_on(n)
+        a_env.reset()          # (the two envs see the same sequence of resets: the same targets, the same work)
+        policy = MLPPolicy.from_actor(actor_for((64, 64), 1.0, 5, b_env.reset()[0]))
+        a_h, b_h = a_env.make_policy(policy), b_env.make_policy(policy)
+        forms = {"rollout_policy + reward.sum(0)": lambda: a_env.rollout_policy(a_h, H, want_actions=False)["reward"].sum(0),
+                 "evaluate_policy": lambda: b_env.evaluate_policy(b_h, H)}
+        envs_of = dict(zip(forms, (a_env, b_env)))
+        a_env.reset(), b_env.reset()
+        want = a_env.rollout_policy(a_h, H, want_actions=False)
+        got = b_env.evaluate_policy(b_h, H)
+        fold = summarize_robot_rollout(*(want[k].cpu().numpy() for k in ("reward", "terminated", "truncated", "inner_steps")))
+        same = got["record"].cpu().numpy().tobytes() == fold.tobytes()
+        row = dict(envs=n, horizon=H, policy="64x64", per_step_library=args.parent_lib or "this build",
+                   euler_steps=int(got["euler_steps"].sum()), same_records=same,
+                   forms=per_launch(forms, args.launches, before=lambda name: envs_of[name].reset()))
+        f = row["forms"]
+        row["evaluate_over_rollout"] = f["evaluate_policy"][0] / f["rollout_policy + reward.sum(0)"][0]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        for e in (a_env, b_env):
+            e.close()
+    if args.episode_launches < 1:
+        return rows
+    # whole episodes: the population of examples/evaluate_robot_policy.py, 500 cycles, with and without the stop
+    P, E, T = 64, 64, args.episode_cycles
+    scale, shift = np.array([0.5, 0.05, 1.0], np.float32), np.array([0.5, 0.05, 0.0], np.float32)
+    theta = np.random.default_rng(0).standard_normal((P, 3, 7)).astype(np.float32)
+    population = MLPPolicy([(theta[..., :6], theta[..., 6])], np.tile(scale, (P, 1)), np.tile(shift, (P, 1)), "clip")
+    envs_of = {"evaluate_policy": make_env(P * E), "evaluate_policy, first_episode": make_env(P * E)}      # the same episodes
+    forms = {name: (lambda e, h, stop: lambda: e.evaluate_policy(h, T, first_episode=stop))(e, e.make_policy(population), "first" in name)
+             for name, e in envs_of.items()}
+    steps = {}
+    for name, run in forms.items():
+        envs_of[name].reset()
+        v = run()
+        steps[name] = dict(euler_steps=int(v["euler_steps"].sum()), finished=float((v["first_end"] != 0).float().mean()),
+                           reached=float((v["first_end"] == 1).float().mean()), mean_first_length=float(v["first_length"].float().mean()))
+    row = dict(envs=P * E, horizon=T, policy="64 linear policies x 64 robots", totals=steps,
+               forms=per_launch(forms, args.episode_launches, before=lambda name: envs_of[name].reset()))
+    f = row["forms"]
+    row["stop_over_full"] = f["evaluate_policy, first_episode"][0] / f["evaluate_policy"][0]
+    rows.append(row)
+    print(json.dumps(row), flush=True)
+    for e in envs_of.values():
+        e.close()
+    return rows
+
+
 def main():
     import torch
     from underwater_swimmer_rl_amd.policy import MLPPolicy
     ap = argparse.ArgumentParser()
+    ap.add_argument("--evaluate", action="store_true", help="evaluate_policy against rollout_policy + reward.sum(0), and the first-episode stop")
+    ap.add_argument("--parent-lib", default=None, help="--evaluate: the library the per-step form runs on (default: this build)")
+    ap.add_argument("--launches", type=int, default=25)
+    ap.add_argument("--episode-cycles", type=int, default=500)
+    ap.add_argument("--episode-launches", type=int, default=5)
     ap.add_argument("--envs", default="4096,262144")
     ap.add_argument("--horizon", type=int, default=16)
     ap.add_argument("--rounds", type=int, default=5)
@@ -151,7 +253,10 @@ def main():
     rows = []
     if args.sampled:
         rows = sampled_rows(args)
-    for n in (() if args.sampled else (int(x) for x in args.envs.split(","))):
+    if args.evaluate:
+        rows = evaluate_rows(args)          # (no table below: the rows are the report)
+    own_rows = args.sampled or args.evaluate
+    for n in (() if own_rows else (int(x) for x in args.envs.split(","))):
         base = make_env(n)
         rolls = {m: make_env(n, m) for m in PERIODS}
         for mix, coast_hi in MIXES.items():
@@ -196,15 +301,15 @@ def main():
                     h.close()
         for e in (base, *rolls.values()):
             e.close()
-    if not args.sampled:
+    if not own_rows:
         print("\n| envs | mix | loop | mean / max Euler steps per cycle | " + " | ".join(["step loop"] + [f"M = {m}" for m in PERIODS]) + " | largest spread |")
         print("|---|---|---|---|" + "---|" * (len(PERIODS) + 2))
-    for r in ([] if args.sampled else rows):
+    for r in ([] if own_rows else rows):
         f = r["forms"]
         cells = [f"{f[k][0]:.2f}" for k in ["step loop"] + [f"M={m}" for m in PERIODS]]
         print(f"| {r['envs']} | {r['mix']} | {r['loop']} | {r['mean_cycle_steps']:.0f} / {r['max_cycle_steps']} | " + " | ".join(cells) +
               f" | {100 * max(v[1] for v in f.values()):.1f} % |")
-    if not args.sampled:
+    if not own_rows:
         print("(ms per call of H = %d env steps; median of %d alternated rounds)" % (H, args.rounds))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -26,7 +26,7 @@ def __getattr__(name):  # lazy: the pieces below need torch / the HIP library
         from . import records
         return getattr(records, name)
     if name in ("MLPPolicy", "GaussianPolicy", "pursuit_policy", "summarize_rollout", "evaluation_views", "navigation_views",
-                "navigation_record"):
+                "navigation_record", "summarize_robot_rollout", "robot_evaluation_views"):
         from . import policy
         return getattr(policy, name)
     if name in ("SalpLib", "load_library", "SalpError", "PolicyHandle"):

@@ -58,9 +58,9 @@ class CRobotConfig(ctypes.Structure):
 
 
 def _prototypes():
-    """name -> (restype, argtypes) of every function of include/salp_robot_rollout.h, of include/salp_robot_sampled.h, and of
-    every function of include/salp_vec.h and include/salp_robot.h, in header order (tests/test_capi_prototypes.py compares
-    the third table with its two headers).  vp: a handle, a buffer (host or device) or a stream."""
+    """name -> (restype, argtypes) of every function of include/salp_robot_rollout.h, of include/salp_robot_sampled.h, of
+    include/salp_robot_evaluate.h, and of every function of include/salp_vec.h and include/salp_robot.h, in header order
+    (tests/test_capi_prototypes.py compares the last table with its two headers).  vp: a handle, a buffer (host or device) or a stream."""
     vp, i64, u64, i32, u32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int32, ctypes.c_uint32
     rc, dbl, ptr = ctypes.c_int, ctypes.c_double, ctypes.POINTER
     create = lambda cfg: (rc, [ptr(cfg), i64, rc, u64, i64, ptr(vp)])
@@ -81,7 +81,11 @@ def _prototypes():
         "salp_robot_policy_noise_step": (rc, [vp, ptr(u64)]),
         "salp_robot_vec_rollout_policy_sampled": (rc, [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]),
     }
-    return rollout, sampled, {
+    evaluate = {      # include/salp_robot_evaluate.h, in header order (tests/test_capi_robot_evaluate.py compares it with that header)
+        "salp_robot_vec_evaluate_policy": (rc, [vp, vp, i32, vp, u32, vp]),
+        "salp_robot_vec_evaluate_policy_sampled": (rc, [vp, vp, i32, vp, u32, vp]),
+    }
+    return rollout, sampled, evaluate, {
         "salp_last_error": (ctypes.c_char_p, []),
         "salp_abi_version": (rc, []),
         "salp_device_count": (rc, []),
@@ -138,7 +142,7 @@ def _prototypes():
     }
 
 
-ROBOT_ROLLOUT_PROTOTYPES, ROBOT_SAMPLED_PROTOTYPES, PROTOTYPES = _prototypes()
+ROBOT_ROLLOUT_PROTOTYPES, ROBOT_SAMPLED_PROTOTYPES, ROBOT_EVALUATE_PROTOTYPES, PROTOTYPES = _prototypes()
 ROBOT_EXPORTS = tuple(n for n in PROTOTYPES if n.startswith("salp_robot_"))
 EXPORTS = tuple(n for n in PROTOTYPES if n not in ROBOT_EXPORTS)
 
@@ -164,7 +168,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
             f"HIP library not found at {p}; build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(there is no CPU fallback)")
     L = ctypes.CDLL(p)
-    for name, (restype, argtypes) in {**PROTOTYPES, **ROBOT_ROLLOUT_PROTOTYPES, **ROBOT_SAMPLED_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **ROBOT_ROLLOUT_PROTOTYPES, **ROBOT_SAMPLED_PROTOTYPES, **ROBOT_EVALUATE_PROTOTYPES}.items():
         # the default library has every symbol (a missing one raises here); an explicit path may be an older A/B
         # variant (profiles/ab_bench.py) that lacks the newer ones
         if path is None or hasattr(L, name):

@@ -1,4 +1,5 @@
-// salp_robot.hip — the C ABI of include/salp_robot.h, include/salp_robot_rollout.h and include/salp_robot_sampled.h, the batched HEAD simulator for gfx950: the
+// salp_robot.hip — the C ABI of include/salp_robot.h, include/salp_robot_rollout.h, include/salp_robot_sampled.h and
+// include/salp_robot_evaluate.h, the batched HEAD simulator for gfx950: the
 // reference's `Robot.step_through_cycle` (src/salp/environments/robot.py) under `SalpRobotEnv.step/reset`
 // (src/salp/environments/salp_robot_env.py), one robot per lane.  Host code only: the handle and the entry points.
 //   salp_robot_kernels.h   every kernel this file launches (and the notes on how the simulator is laid out on the GPU)
@@ -19,6 +20,7 @@
 #include "../../include/salp_robot.h"
 #include "../../include/salp_robot_rollout.h"
 #include "../../include/salp_robot_sampled.h"
+#include "../../include/salp_robot_evaluate.h"
 #include "salp_robot_params.h"
 #include "salp_robot_kernels.h"
 #include "salp_host.h"
@@ -73,6 +75,17 @@ static int launch_robot_step(salp_robot_vec* h, const float* act, float* obs, fl
                    inner_steps, order);
 }
 
+// The rollout kernel of the handle's service period, for the action source ACT and the output signature SIG.
+template <int ACT, int SIG>
+static int launch_robot_rollout(const salp_robot_vec* h, hipStream_t st, const RobotRollout& J) {
+  switch (h->period) {
+    case 0: return launch_1d(salp_robot_rollout_kernel<ACT, 0, SIG>, h->n, kRBlock, st, h->P, h->S, J);
+    case 32: return launch_1d(salp_robot_rollout_kernel<ACT, 32, SIG>, h->n, kRBlock, st, h->P, h->S, J);
+    case 128: return launch_1d(salp_robot_rollout_kernel<ACT, 128, SIG>, h->n, kRBlock, st, h->P, h->S, J);
+    default: return launch_1d(salp_robot_rollout_kernel<ACT, 512, SIG>, h->n, kRBlock, st, h->P, h->S, J);
+  }
+}
+
 // salp_robot_vec_rollout (ACT = kActRead, source = the actions), salp_robot_vec_rollout_policy (kActPolicy, source = the
 // policy's device block, which is on the device whatever `flags` says) and salp_robot_vec_rollout_policy_sampled
 // (kActPolicySampled, the same source; behind the rollout kernel the block's noise step goes on by the horizon, in the
@@ -87,29 +100,49 @@ static int robot_rollout_impl(salp_robot_vec_t* h, const float* source, int32_t 
     return fail(bad, why);
   CallFrame f;
   if (const int rc = f.enter(h, stream)) return rc;
-  RobotRollout J;
+  RobotRollout J = {};
   J.horizon = horizon; J.max_iters = rollout_max_iters(horizon, h->max_steps, h->period);
   const size_t n = (size_t)h->n, HN = (size_t)horizon * n;
   HostStream s[] = {stream_in(ACT == kActRead ? source : nullptr, HN * 3), stream_out(obs, HN * 6), stream_out(reward, HN),
                     stream_out(terminated, HN), stream_out(truncated, HN), stream_out(final_obs, HN * 6, true),
                     stream_out(inner_steps, HN), stream_out(act_out, HN * 3), stream_out(logp_out, HN)};
-  const auto launch = [&] {
-    switch (h->period) {
-      case 0: return launch_1d(salp_robot_rollout_kernel<ACT, 0>, h->n, kRBlock, f.st, h->P, h->S, J);
-      case 32: return launch_1d(salp_robot_rollout_kernel<ACT, 32>, h->n, kRBlock, f.st, h->P, h->S, J);
-      case 128: return launch_1d(salp_robot_rollout_kernel<ACT, 128>, h->n, kRBlock, f.st, h->P, h->S, J);
-      default: return launch_1d(salp_robot_rollout_kernel<ACT, 512>, h->n, kRBlock, f.st, h->P, h->S, J);
-    }
-  };
   return staged(h->stage, f.st, flags & 1u, s, [&] {
     J.act = ACT == kActRead ? s[0].as<const float>() : source;
     J.obs = s[1].as<float>(); J.reward = s[2].as<float>(); J.terminated = s[3].as<uint8_t>(); J.truncated = s[4].as<uint8_t>();
     J.final_obs = s[5].as<float>(); J.inner_steps = s[6].as<int32_t>(); J.act_out = s[7].as<float>();
     J.logp_out = s[8].as<float>();
-    const int rc = launch();
+    const int rc = launch_robot_rollout<ACT, kSigSteps>(h, f.st, J);
     if (ACT != kActPolicySampled || rc != SALP_OK) return rc;
     return policy_noise_advance(const_cast<float*>(source), horizon, f.st);
   });
+}
+
+// salp_robot_vec_evaluate_policy (ACT = kActPolicy) and salp_robot_vec_evaluate_policy_sampled (kActPolicySampled): the
+// closed loop of robot_rollout_impl with the summary signature, one record per robot in `rec`, which goes in as well as out
+// in the host-pointer form; everything is checked before anything is launched.
+template <int ACT>
+static int robot_evaluate_impl(salp_robot_vec_t* h, const salp_robot_policy_t* pol, int32_t horizon, void* rec, uint32_t flags,
+                               void* stream) {
+  if (!h || !pol) return fail(SALP_ERR_INVALID, "handle / policy is NULL");
+  char why[160];
+  if (const int bad = check_evaluate_args(h->max_steps, horizon, flags, rec, pol->h == h, ACT == kActPolicySampled, pol->gaussian,
+                                          why, sizeof(why)))
+    return fail(bad, why);
+  CallFrame f;
+  if (const int rc = f.enter(h, stream)) return rc;
+  RobotRollout J = {};
+  J.horizon = horizon; J.max_iters = rollout_max_iters(horizon, h->max_steps, h->period);
+  J.eval_flags = flags & ((uint32_t)SALP_ROBOT_EVAL_ACCUMULATE | (uint32_t)SALP_ROBOT_EVAL_FIRST_EPISODE);
+  J.act = pol->block;
+  HostStream s[] = {stream_out(static_cast<int32_t*>(rec), (size_t)h->n * SALP_REVAL_WORDS, true)};
+  const int rc = staged(h->stage, f.st, flags & 1u, s, [&] {
+    J.rec = s[0].as<int32_t>();
+    const int launched = launch_robot_rollout<ACT, kSigSummary>(h, f.st, J);
+    if (ACT != kActPolicySampled || launched != SALP_OK) return launched;
+    return policy_noise_advance(pol->block, horizon, f.st);
+  });
+  if (rc == SALP_OK) pol->last_stream = (hipStream_t)stream;
+  return rc;
 }
 
 extern "C" {
@@ -342,6 +375,17 @@ int salp_robot_vec_rollout_policy_sampled(salp_robot_vec_t* h, const salp_robot_
                                                        inner_steps, act_out, flags, stream, logp_out);
   if (rc == SALP_OK) pol->last_stream = (hipStream_t)stream;
   return rc;
+}
+
+int salp_robot_vec_evaluate_policy(salp_robot_vec_t* h, const salp_robot_policy_t* pol, int32_t horizon, void* rec, uint32_t flags,
+                                   void* stream) {
+  return robot_evaluate_impl<kActPolicy>(h, pol, horizon, rec, flags, stream);
+}
+
+// (the policy arrives const and its noise word is advanced all the same, as in salp_robot_vec_rollout_policy_sampled)
+int salp_robot_vec_evaluate_policy_sampled(salp_robot_vec_t* h, const salp_robot_policy_t* pol, int32_t horizon, void* rec,
+                                           uint32_t flags, void* stream) {
+  return robot_evaluate_impl<kActPolicySampled>(h, pol, horizon, rec, flags, stream);
 }
 
 int salp_robot_vec_get_state(salp_robot_vec_t* h, double* state, uint32_t flags, void* stream) {

@@ -332,7 +332,7 @@ void salp_robot_trajectory_kernel(RobotParams P0, RobotTrajectory J) {
   }
 }
 
-// ---- multi-cycle rollout (salp_robot_vec_rollout, salp_robot_vec_rollout_policy, _policy_sampled) ------
+// ---- multi-cycle rollout (salp_robot_vec_rollout, salp_robot_vec_rollout_policy, _policy_sampled, _evaluate_policy) ------
 // H env steps — H breathing cycles per robot — in one launch, env i on lane i, the robot in registers throughout; the
 // actions are read (kActRead) or computed by the in-kernel MLP policy from the row the step before wrote (kActPolicy; or
 // sampled from its Gaussian form, kActPolicySampled; salp_policy.h).  ONE loop over Euler iterations serves the whole launch.  Every lane carries its own step index
@@ -359,7 +359,9 @@ struct RobotRollout {
   float* act_out;          // [H][n][3], kActPolicy / kActPolicySampled only           (every output nullable)
   int64_t max_iters;
   int32_t horizon;
+  uint32_t eval_flags;     // kSigSummary only: SALP_ROBOT_EVAL_ACCUMULATE / _FIRST_EPISODE of the call's flags
   float* logp_out;         // [H][n], kActPolicySampled only
+  int32_t* rec;            // kSigSummary only: [n][SALP_REVAL_WORDS], 16-byte aligned
 };
 // kActPolicySampled (salp_robot_vec_rollout_policy_sampled, include/salp_robot_sampled.h): the closed loop with the
 // stochastic form of a Gaussian policy.  The policy's noise step n0 is read once at entry (wave-uniform); a lane served
@@ -368,6 +370,46 @@ struct RobotRollout {
 enum { kActRead = 0, kActPolicy = 1, kActPolicySampled = 2 };
 enum { kRobotNoiseStream = 3 };     // fourth counter word of component 0 / 1's block; component 2's is one above
 enum { ROBOT_POLICY_OBS = 6, ROBOT_POLICY_ACT = 3 };     // the policy's shape: salp_policy.h with 6 inputs and 3 components
+// The output signature, SIG.  kSigSteps: the per-step blocks above.  kSigSummary (salp_robot_vec_evaluate_policy, _sampled;
+// include/salp_robot_evaluate.h): no per-step output, one record of SALP_REVAL_WORDS words per robot in J.rec.  The loop,
+// the service points, the cycle pieces and the policy evaluation are the same text, so a summary launch computes the
+// bits of the per-step launch it stands for.  At a service point a due lane folds (float)rew, term, trunc and steps of
+// its step into its record, which lives in J.rec between service points and not in registers (the Euler loop needs them
+// all; a service point comes once per hundreds of Euler iterations, so 48 bytes read and written there cost nothing):
+// the record is initialised at entry — zeroed, or with SALP_ROBOT_EVAL_ACCUMULATE left as the caller passed it.  With
+// SALP_ROBOT_EVAL_FIRST_EPISODE a lane whose record has FIRST_END != 0, at entry or after its fold, is finished (t = H):
+// it neither steps nor waits, like every finished lane.  Records of padding lanes and of rows >= n are never touched.
+enum { kSigSteps = 0, kSigSummary = 1 };
+typedef int32_t i4 __attribute__((ext_vector_type(4)));
+static_assert(SALP_REVAL_WORDS == 12 && SALP_REVAL_RETURN == 0 && SALP_REVAL_FIRST_RETURN == 2 && SALP_REVAL_EULER_STEPS == 4 &&
+              SALP_REVAL_FIRST_LENGTH == 6 && SALP_REVAL_FIRST_END == 7 && SALP_REVAL_EPISODES == 8 && SALP_REVAL_REACHED == 9 &&
+              SALP_REVAL_FIRST_EULER_STEPS == 10, "the record is three 16-byte pieces: words 0-3, 4-7, 8-11");
+
+__device__ __forceinline__ double words_as_double(int32_t lo, int32_t hi) {
+  return __longlong_as_double((long long)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo));
+}
+
+// One env step folded into the record at q (include/salp_robot_evaluate.h): three 16-byte loads, three 16-byte stores.
+// Returns FIRST_END after the fold.
+__device__ __forceinline__ int32_t fold_robot_record(i4* q, float rew, bool term, bool trunc, int steps) {
+  i4 a = q[0], b = q[1], c = q[2];
+  const double r = (double)rew;
+  const uint64_t ret = (uint64_t)__double_as_longlong(words_as_double(a.x, a.y) + r);
+  a.x = (int32_t)(uint32_t)ret; a.y = (int32_t)(uint32_t)(ret >> 32);
+  const uint64_t euler = (((uint64_t)(uint32_t)b.y << 32) | (uint32_t)b.x) + (uint64_t)(int64_t)steps;
+  b.x = (int32_t)(uint32_t)euler; b.y = (int32_t)(uint32_t)(euler >> 32);
+  if (b.w == 0) {     // the first episode is still open: FIRST_RETURN, FIRST_LENGTH, FIRST_EULER_STEPS, FIRST_END
+    const uint64_t first = (uint64_t)__double_as_longlong(words_as_double(a.z, a.w) + r);
+    a.z = (int32_t)(uint32_t)first; a.w = (int32_t)(uint32_t)(first >> 32);
+    b.z += 1;
+    c.z += steps;
+    b.w = term ? 1 : (trunc ? 2 : 0);     // terminated wins
+  }
+  c.x += (term || trunc) ? 1 : 0;
+  c.y += term ? 1 : 0;
+  q[0] = a; q[1] = b; q[2] = c;
+  return b.w;
+}
 
 // what the opening of a cycle leaves for the Euler steps of that cycle (the names of the cycle pieces)
 struct RobotCycle {
@@ -385,10 +427,11 @@ __device__ __forceinline__ double wave_uniform(double x) {
   return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
 
-template <int ACT, int M>
+template <int ACT, int M, int SIG = kSigSteps>
 __global__ __launch_bounds__(kRBlock) __attribute__((amdgpu_waves_per_eu(SALP_ROBOT_WAVES, SALP_ROBOT_WAVES)))
 void salp_robot_rollout_kernel(RobotParams P, RobotState S, RobotRollout J) {
   static_assert(M >= 0 && (M & (M - 1)) == 0, "M is 0 (never) or a power of two");
+  static_assert(SIG == kSigSteps || (SIG == kSigSummary && ACT != kActRead), "a summary is of a closed loop");
   constexpr bool kRecord = false;
   const RobotHistory H = {};
   const int64_t i0 = (int64_t)blockIdx.x * kRBlock + threadIdx.x;
@@ -439,6 +482,17 @@ void salp_robot_rollout_kernel(RobotParams P, RobotState S, RobotRollout J) {
 
   int32_t t = active ? 0 : horizon;     // padding lanes are finished from the start
   bool running = false;                 // a cycle has been opened for env step t and that step is not finished yet
+  if constexpr (SIG == kSigSummary) {
+    if (active) {
+      i4* const q = reinterpret_cast<i4*>(J.rec + i * SALP_REVAL_WORDS);
+      if (!(J.eval_flags & (uint32_t)SALP_ROBOT_EVAL_ACCUMULATE)) {
+        const i4 zero = {0, 0, 0, 0};
+        q[0] = zero; q[1] = zero; q[2] = zero;
+      } else if ((J.eval_flags & (uint32_t)SALP_ROBOT_EVAL_FIRST_EPISODE) && J.rec[i * SALP_REVAL_WORDS + SALP_REVAL_FIRST_END] != 0) {
+        t = horizon;                    // its first episode ended in an earlier call: nothing to run
+      }
+    }
+  }
   // One round per service point: the service code, then Euler iterations up to the next service point.  The Euler
   // iterations form an inner loop of their own so that the register allocator ranks what they read above what only the
   // service code reads (as one flat loop it reloaded two of the Euler step's operands from scratch on every iteration).
@@ -451,15 +505,20 @@ void salp_robot_rollout_kernel(RobotParams P, RobotState S, RobotRollout J) {
       if (due) {
         if (running) {     // env step t is over: due lanes are active lanes
           const int64_t row = (int64_t)t * n;
-          float* const obs = J.obs ? J.obs + row * 6 : nullptr;
-          float* const reward = J.reward ? J.reward + row : nullptr;
-          uint8_t* const terminated = J.terminated ? J.terminated + row : nullptr;
-          uint8_t* const truncated = J.truncated ? J.truncated + row : nullptr;
-          float* const final_obs = J.final_obs ? J.final_obs + row * 6 : nullptr;
-          int32_t* const inner_steps = J.inner_steps ? J.inner_steps + row : nullptr;
+          float* const final_obs = (SIG == kSigSteps && J.final_obs) ? J.final_obs + row * 6 : nullptr;
 #include "salp_robot_step_finish.h"
-#include "salp_robot_step_outputs.h"
           ++t;
+          if constexpr (SIG == kSigSummary) {
+            const int32_t first_end = fold_robot_record(reinterpret_cast<i4*>(J.rec + i * SALP_REVAL_WORDS), (float)rew, term, trunc, steps);
+            if ((J.eval_flags & (uint32_t)SALP_ROBOT_EVAL_FIRST_EPISODE) && first_end != 0) t = horizon;
+          } else {
+            float* const obs = J.obs ? J.obs + row * 6 : nullptr;
+            float* const reward = J.reward ? J.reward + row : nullptr;
+            uint8_t* const terminated = J.terminated ? J.terminated + row : nullptr;
+            uint8_t* const truncated = J.truncated ? J.truncated + row : nullptr;
+            int32_t* const inner_steps = J.inner_steps ? J.inner_steps + row : nullptr;
+#include "salp_robot_step_outputs.h"
+          }
           running = false;
         }
         if (t < horizon) {
@@ -480,12 +539,12 @@ void salp_robot_rollout_kernel(RobotParams P, RobotState S, RobotRollout J) {
             } else {
               policy_eval<ROBOT_POLICY_OBS, ROBOT_POLICY_ACT>(J.act, pol_off, x, a);
             }
-            if (J.act_out) {
+            if (SIG == kSigSteps && J.act_out) {
               float* ao = J.act_out + ((int64_t)t * n + i) * 3;
               ao[0] = a[0]; ao[1] = a[1]; ao[2] = a[2];
             }
             if constexpr (ACT == kActPolicySampled) {
-              if (J.logp_out) J.logp_out[(int64_t)t * n + i] = lp;
+              if (SIG == kSigSteps && J.logp_out) J.logp_out[(int64_t)t * n + i] = lp;
             }
           } else {
             const float* ai = J.act + ((int64_t)t * n + i) * 3;

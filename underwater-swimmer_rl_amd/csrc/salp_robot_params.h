@@ -2,7 +2,8 @@
 // of the cycle (action scales, contract / release rates, the cycle-length cut, the schedule's bins), the list of the
 // physical parameters a trajectory robot may have of its own (SALP_ROBOT_PHYS), and the host functions that derive a
 // RobotParams from a salp_robot_config_t and decide what salp_robot_vec_create, salp_robot_vec_step_history,
-// salp_robot_vec_trajectory and the two rollout calls refuse (and the rollout kernel's service period and iteration bound).
+// salp_robot_vec_trajectory, the rollout calls and the evaluation calls refuse (and the rollout kernel's service period and
+// iteration bound).
 //
 // The header compiles in two ways, like salp_params.h and salp_fp64_math.h:
 //   * with hipcc: what salp_robot.hip includes, before salp_robot_kernels.h;
@@ -22,6 +23,7 @@
 
 #include "../../include/salp_robot.h"
 #include "../../include/salp_robot_rollout.h"   // SALP_ROBOT_MAX_ROLLOUT_CYCLES
+#include "../../include/salp_robot_evaluate.h"  // the evaluation calls' flags and SALP_REVAL_*
 #include "../../include/salp_vec.h"   // SALP_OK, SALP_ERR_INVALID
 
 // An unnamed namespace, as in salp_host.h: the kernels of salp_robot_kernels.h live in one, and RobotParams is part of their names.
@@ -190,6 +192,27 @@ inline int check_rollout_args(int64_t max_steps, int32_t horizon, uint32_t flags
   if (flags & ~1u) return refuse_robot_call(msg, msg_size, "unknown flag bits");
   if (!has_main_output) return refuse_robot_call(msg, msg_size, "one of obs, reward, terminated, truncated is required");
   // the same refusal as the history and trajectory calls: the loop's iteration bound is counted in Euler steps
+  if (max_steps < 0) return refuse_robot_call(msg, msg_size, "dt is too small (more than 2^24 Euler steps per cycle)");
+  return (int)SALP_OK;
+}
+
+// What salp_robot_vec_evaluate_policy and salp_robot_vec_evaluate_policy_sampled refuse once they have a handle (max_steps)
+// and a policy.  own_policy: the policy was created on this handle; sampled: the call is the sampled one; gaussian: the
+// policy has a log-std head; device_ptrs is bit 0 of flags.
+inline int check_evaluate_args(int64_t max_steps, int32_t horizon, uint32_t flags, const void* rec, bool own_policy, bool sampled,
+                               bool gaussian, char* msg, size_t msg_size) {
+  if (!rec) return refuse_robot_call(msg, msg_size, "rec is NULL");
+  if (horizon < 1 || horizon > SALP_ROBOT_MAX_ROLLOUT_CYCLES) {
+    snprintf(msg, msg_size, "horizon must be in [1, %d]", (int)SALP_ROBOT_MAX_ROLLOUT_CYCLES);
+    return (int)SALP_ERR_INVALID;
+  }
+  if (flags & ~(1u | (uint32_t)SALP_ROBOT_EVAL_ACCUMULATE | (uint32_t)SALP_ROBOT_EVAL_FIRST_EPISODE))
+    return refuse_robot_call(msg, msg_size, "unknown flag bits");
+  if ((flags & 1u) && ((uintptr_t)rec % 16u) != 0) return refuse_robot_call(msg, msg_size, "device rec must be 16-byte aligned");
+  if (!own_policy) return refuse_robot_call(msg, msg_size, "the policy belongs to another handle");
+  if (sampled && !gaussian)
+    return refuse_robot_call(msg, msg_size, "sampling needs a Gaussian policy (salp_robot_policy_create_gaussian)");
+  // the same refusal as the history, trajectory and rollout calls: the loop's iteration bound is counted in Euler steps
   if (max_steps < 0) return refuse_robot_call(msg, msg_size, "dt is too small (more than 2^24 Euler steps per cycle)");
   return (int)SALP_OK;
 }

@@ -512,6 +512,67 @@ def summarize_rollout(reward, terminated, truncated, captured=None, record=None)
     return rec
 
 
+# ---------------------------------------------------------------------- robot evaluation records (salp_robot_vec_evaluate_policy)
+REVAL_ACCUMULATE, REVAL_FIRST_EPISODE = 4, 8      # call flags next to SALP_DEVICE_PTRS (include/salp_robot_evaluate.h)
+(REVAL_RETURN, REVAL_FIRST_RETURN, REVAL_EULER_STEPS, REVAL_FIRST_LENGTH, REVAL_FIRST_END, REVAL_EPISODES, REVAL_REACHED,
+ REVAL_FIRST_EULER_STEPS, REVAL_WORDS) = 0, 2, 4, 6, 7, 8, 9, 10, 12
+
+
+def robot_evaluation_views(record) -> dict:
+    """Typed views (no copy) of a block of robot summary records, int32 [N, 12] (numpy array or torch tensor, contiguous):
+    `record` itself, `return_sum` and `first_return` float64 [N], `euler_steps` int64 [N], `first_length`, `first_end`,
+    `episodes`, `reached`, `first_euler_steps` int32 [N] (include/salp_robot_evaluate.h SALP_REVAL_*)."""
+    if isinstance(record, np.ndarray):
+        if record.dtype != np.int32 or record.ndim != 2 or record.shape[1] != REVAL_WORDS or not record.flags.c_contiguous:
+            raise ValueError("record must be a contiguous int32 [N, 12] block")
+        f64, i64 = record.view(np.float64), record.view(np.int64)             # [N, 6]
+    else:
+        import torch
+        if record.dtype != torch.int32 or record.dim() != 2 or record.shape[1] != REVAL_WORDS or not record.is_contiguous():
+            raise ValueError("record must be a contiguous int32 [N, 12] block")
+        f64, i64 = record.view(torch.float64), record.view(torch.int64)
+    return dict(record=record, return_sum=f64[:, REVAL_RETURN // 2], first_return=f64[:, REVAL_FIRST_RETURN // 2],
+                euler_steps=i64[:, REVAL_EULER_STEPS // 2], first_length=record[:, REVAL_FIRST_LENGTH],
+                first_end=record[:, REVAL_FIRST_END], episodes=record[:, REVAL_EPISODES], reached=record[:, REVAL_REACHED],
+                first_euler_steps=record[:, REVAL_FIRST_EULER_STEPS])
+
+
+def summarize_robot_rollout(reward, terminated, truncated, inner_steps, record=None, first_episode=False) -> np.ndarray:
+    """The summary records of a robot rollout's per-step outputs — the numpy statement of what
+    salp_robot_vec_evaluate_policy leaves: reward float32 [H, N], terminated / truncated [H, N] (0 / 1), inner_steps
+    integer [H, N].  Returns int32 [N, 12].  The float64 sums are sequential additions of the float32 rewards in step order.
+    `record`: records to continue (SALP_ROBOT_EVAL_ACCUMULATE; not modified) — an all-zero record is a fresh one.
+    `first_episode` (SALP_ROBOT_EVAL_FIRST_EPISODE): a robot's steps after the first ending of its record are ignored."""
+    reward = np.asarray(reward)
+    if reward.dtype != np.float32:
+        raise ValueError("reward must be float32: the sums are over the float32 values a rollout stores")
+    H, N = reward.shape
+    term = np.asarray(terminated).astype(bool).reshape(H, N)
+    trunc = np.asarray(truncated).astype(bool).reshape(H, N)
+    inner = np.asarray(inner_steps).astype(np.int64).reshape(H, N)
+    rec = np.zeros((N, REVAL_WORDS), np.int32) if record is None else np.array(record, dtype=np.int32, order="C").reshape(N, REVAL_WORDS)
+    v = robot_evaluation_views(rec)
+    ret, first_ret, euler = v["return_sum"].copy(), v["first_return"].copy(), v["euler_steps"].copy()
+    first_len, first_end, first_euler = v["first_length"].copy(), v["first_end"].copy(), v["first_euler_steps"].copy()
+    episodes, reached = v["episodes"].copy(), v["reached"].copy()
+    for t in range(H):
+        r = reward[t].astype(np.float64)
+        open_ = first_end == 0
+        run = open_ if first_episode else np.ones(N, bool)
+        ret = np.where(run, ret + r, ret)
+        euler = np.where(run, euler + inner[t], euler)
+        first_ret = np.where(open_, first_ret + r, first_ret)
+        first_len = first_len + open_.astype(np.int32)
+        first_euler = np.where(open_, first_euler + inner[t], first_euler).astype(np.int32)
+        first_end = np.where(open_, np.where(term[t], 1, np.where(trunc[t], 2, 0)), first_end).astype(np.int32)    # terminated wins
+        episodes = episodes + (run & (term[t] | trunc[t])).astype(np.int32)
+        reached = reached + (run & term[t]).astype(np.int32)
+    v["return_sum"][:], v["first_return"][:], v["euler_steps"][:] = ret, first_ret, euler
+    v["first_length"][:], v["first_end"][:], v["first_euler_steps"][:] = first_len, first_end, first_euler
+    v["episodes"][:], v["reached"][:] = episodes, reached
+    return rec
+
+
 # ---------------------------------------------------------------------- navigation records (salp_vec_evaluate_navigation)
 (NAV_STEPS, NAV_STATUS, NAV_PATH, NAV_LATERAL, NAV_XMIN, NAV_XMAX, NAV_YMIN, NAV_YMAX, NAV_X, NAV_Y,
  NAV_WORDS) = 0, 1, 2, 4, 6, 8, 10, 12, 14, 16, 20

@@ -12,6 +12,8 @@ robot.py:335-358, 422-445): `info["inner_steps"]` is the number of Euler steps e
 `env.rollout(actions_HN3)` runs H cycles of every robot in one launch, and `env.rollout_policy(policy, H)` does so with
 every action computed in the kernel by a small MLP policy (`policy.MLPPolicy`, 6 observations -> 3 action components);
 with a `policy.GaussianPolicy` and `sample=True` the kernel samples the tanh-Gaussian action and returns its log-probability.
+`env.evaluate_policy(policy, H)` is that closed loop with no per-step output: one summary record per robot, continuable
+across calls (`accumulate=True`) and, with `first_episode=True`, stopped at the end of each robot's first episode.
 Same conventions as SalpVectorEnv: device tensors, same-step autoreset with `final_observation`,
 no CPU fallback."""
 from __future__ import annotations
@@ -246,6 +248,43 @@ class SalpRobotVectorEnv(ArrayBackend, PolicyCache):
             return self._rollout_result(*out, actions=aout, logp=logp)
         self._call("salp_robot_vec_rollout_policy", handle._p, H, *out, aout, what="rollout_policy")
         return self._rollout_result(*out, actions=aout)
+
+    def evaluate_policy(self, policy, horizon: int, out=None, accumulate: bool = False, sample: bool = False,
+                        first_episode: bool = False) -> dict:
+        """`horizon` closed-loop env steps of `rollout_policy` in one kernel launch with NO per-step output
+        (salp_robot_vec_evaluate_policy, include/salp_robot_evaluate.h): one summary record per robot (48 B) instead of
+        seven [H, N] blocks.  Returns typed views of one int32 [N, 12] block (`policy.robot_evaluation_views`): `record`,
+        `return_sum` and `first_return` (float64 [N]: the float32 step rewards added in step order in fp64 — over the call,
+        and up to the robot's first episode end), `euler_steps` (int64 [N]: Euler steps simulated; seconds = dt x this),
+        `first_length`, `first_end` (0 not finished, 1 target reached, 2 truncated), `episodes`, `reached`,
+        `first_euler_steps` (int32 [N]).  The record is, bit for bit, `policy.summarize_robot_rollout` of what
+        `rollout_policy(policy, horizon)` returns from the same state.
+        `out`: a block (or a dict returned earlier) to write into; without it the env uses a block of its own, which the
+        next call overwrites.  `accumulate=True` continues the records in the block, so a run cut into several calls (or
+        replayed from a captured graph) adds up; an all-zero record is a fresh one, and the env's own block starts zeroed.
+        `first_episode=True`: a robot is no longer stepped once its first episode has ended (it sits at the start of its
+        next episode), which is how a policy is scored over whole episodes: `evaluate_policy(p, 500, first_episode=True)`.
+        With `accumulate`, robots whose record already has `first_end != 0` run nothing.
+        `sample=True` (a `GaussianPolicy` or its handle): the run takes the policy's sampled actions, as
+        `rollout_policy(..., sample=True)` would; the noise step advances by `horizon` behind the launch."""
+        from .policy import REVAL_ACCUMULATE, REVAL_FIRST_EPISODE, REVAL_WORDS, robot_evaluation_views
+        handle = self._policy_handle(policy)
+        shape = (self.num_envs, REVAL_WORDS)
+        if out is None:
+            fresh = "record" not in self._bufs
+            rec = self._buf("record", shape, np.int32)
+            if fresh:
+                rec[...] = 0
+        else:
+            rec = self._out_block(out["record"] if isinstance(out, dict) else out, shape, np.int32)
+        views = robot_evaluation_views(rec)       # checks dtype and contiguity
+        if sample and not handle.gaussian:
+            raise ValueError("sample=True needs a GaussianPolicy (or the handle of one)")
+        flags = self._flags | (REVAL_ACCUMULATE if accumulate else 0) | (REVAL_FIRST_EPISODE if first_episode else 0)
+        name = "salp_robot_vec_evaluate_policy_sampled" if sample else "salp_robot_vec_evaluate_policy"
+        _capi.call(self.L, name, self._h, handle._p, int(horizon), rec, flags, self._stream,
+                   what="evaluate_policy (sampled)" if sample else "evaluate_policy")
+        return views
 
     def get_state(self) -> np.ndarray:
         """fp64 [27, N] snapshot, rows R_* (include/salp_robot.h)."""
