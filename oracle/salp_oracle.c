@@ -635,13 +635,12 @@ int salp_oracle_set_base_num_food(salp_oracle_t* h, int k) {
    (every partial sum, u, the activation, the product, the action) were non-zero subnormals. */
 static int is_subnormal(float v) { return v != 0.0f && fabsf(v) < 1.17549435e-38f; }
 
-int salp_oracle_policy_forward(const salp_policy_desc_t* desc, int32_t obs_dim, int32_t act_dim, const float* weights,
-                               const float* obs, int64_t M, float* u, float* a, int64_t* subnormals) {
-  if (!desc || !weights || !obs || !a || M < 0) return -1;
-  if (desc->struct_size != sizeof(salp_policy_desc_t) || desc->n_hidden < 0 || desc->n_hidden > 2) return -1;
-  if (obs_dim < 1 || obs_dim > 64 || act_dim < 1 || act_dim > 2) return -1;
+/* width[0 .. L]: layer l maps width[l] inputs to width[l + 1] outputs, the last one the head(s).  Returns L, or -1. */
+static int policy_widths(const salp_policy_desc_t* desc, int32_t obs_dim, int32_t act_dim, int width[4]) {
+  if (!desc || desc->struct_size != sizeof(salp_policy_desc_t) || desc->n_hidden < 0 || desc->n_hidden > 2) return -1;
+  if (obs_dim < 1 || obs_dim > 64 || act_dim < 1 || act_dim > 3) return -1;
   if (desc->out_activation != SALP_POLICY_OUT_TANH && desc->out_activation != SALP_POLICY_OUT_CLIP) return -1;
-  int width[4], L = 0;                     /* layer l maps width[l] inputs to width[l + 1] outputs */
+  int L = 0;
   width[L++] = obs_dim;
   for (int l = 0; l < desc->n_hidden; ++l) {
     const int w = desc->hidden[l];
@@ -649,6 +648,29 @@ int salp_oracle_policy_forward(const salp_policy_desc_t* desc, int32_t obs_dim, 
     width[L++] = w;
   }
   width[L] = act_dim;
+  return L;
+}
+
+/* y[j] = b[j] + sum_i W[j][i] x[i]: bias first, one fmaf per input in ascending index order; fmaxf(., 0) with `relu`. */
+static int64_t policy_layer(const float* W, const float* b, int in, int out, const float* x, float* y, int relu) {
+  int64_t sub = 0;
+  for (int j = 0; j < out; ++j) {
+    float acc = b[j];
+    for (int i = 0; i < in; ++i) {
+      acc = fmaf(W[(size_t)j * in + i], x[i], acc);
+      sub += is_subnormal(acc);
+    }
+    y[j] = relu ? fmaxf(acc, 0.0f) : acc;
+  }
+  return sub;
+}
+
+int salp_oracle_policy_forward(const salp_policy_desc_t* desc, int32_t obs_dim, int32_t act_dim, const float* weights,
+                               const float* obs, int64_t M, float* u, float* a, int64_t* subnormals) {
+  if (!desc || !weights || !obs || !a || M < 0) return -1;
+  int width[4];
+  const int L = policy_widths(desc, obs_dim, act_dim, width);
+  if (L < 0) return -1;
   size_t words = 0;
   for (int l = 0; l < L; ++l) words += (size_t)width[l + 1] * width[l] + width[l + 1];
   const float* scale = weights + words;
@@ -661,18 +683,9 @@ int salp_oracle_policy_forward(const salp_policy_desc_t* desc, int32_t obs_dim, 
     const float* p = weights;
     for (int l = 0; l < L; ++l) {
       const int in = width[l], out = width[l + 1];
-      const float* W = p;
-      const float* b = p + (size_t)out * in;
-      for (int j = 0; j < out; ++j) {
-        float acc = b[j];
-        for (int i = 0; i < in; ++i) {
-          acc = fmaf(W[(size_t)j * in + i], x[i], acc);
-          sub += is_subnormal(acc);
-        }
-        y[j] = (l + 1 < L) ? fmaxf(acc, 0.0f) : acc;
-      }
+      sub += policy_layer(p, p + (size_t)out * in, in, out, x, y, l + 1 < L);
       for (int j = 0; j < out; ++j) x[j] = y[j];
-      p = b + out;
+      p += (size_t)out * in + out;
     }
     for (int k = 0; k < act_dim; ++k) {
       const float uk = x[k];
@@ -683,6 +696,42 @@ int salp_oracle_policy_forward(const salp_policy_desc_t* desc, int32_t obs_dim, 
       if (u) u[m * act_dim + k] = uk;
       a[m * act_dim + k] = ak;
     }
+  }
+  if (subnormals) *subnormals = sub;
+  return 0;
+}
+
+/* The two heads of a Gaussian policy (include/salp_vec.h "Sampled actions") from the PUBLIC Gaussian layout of ONE policy:
+   the hidden layers, then W_mu[act_dim][in], b_mu, W_ls[act_dim][in], b_ls, scale, shift.  The same arithmetic as above on
+   the shared body; both heads start from their bias and add the last hidden layer's outputs in ascending order with one
+   fmaf each.  m [M][act_dim]: the mean head before anything is added to it; r [M][act_dim]: the log-std head's raw sum,
+   BEFORE the clamp to [-20, 2].  Everything here is IEEE arithmetic: a kernel that keeps the promised order gives these
+   bits.  *subnormals (nullable): non-zero subnormal partial sums formed on the way. */
+int salp_oracle_policy_forward_gaussian(const salp_policy_desc_t* desc, int32_t obs_dim, int32_t act_dim, const float* weights,
+                                        const float* obs, int64_t M, float* m_out, float* r_out, int64_t* subnormals) {
+  if (!desc || !weights || !obs || !m_out || !r_out || M < 0) return -1;
+  int width[4];
+  const int L = policy_widths(desc, obs_dim, act_dim, width);
+  if (L < 0 || desc->out_activation != SALP_POLICY_OUT_TANH) return -1;
+  int64_t sub = 0;
+#pragma omp parallel for num_threads(g_threads) schedule(static) reduction(+ : sub)
+  for (int64_t m = 0; m < M; ++m) {
+    float x[64], y[64];
+    for (int i = 0; i < obs_dim; ++i) x[i] = obs[m * obs_dim + i];
+    const float* p = weights;
+    for (int l = 0; l + 1 < L; ++l) {
+      const int in = width[l], out = width[l + 1];
+      sub += policy_layer(p, p + (size_t)out * in, in, out, x, y, 1);
+      for (int j = 0; j < out; ++j) x[j] = y[j];
+      p += (size_t)out * in + out;
+    }
+    const int in = width[L - 1];
+    const float* W_mu = p;
+    const float* b_mu = W_mu + (size_t)act_dim * in;
+    const float* W_ls = b_mu + act_dim;
+    const float* b_ls = W_ls + (size_t)act_dim * in;
+    sub += policy_layer(W_mu, b_mu, in, act_dim, x, m_out + m * act_dim, 0);
+    sub += policy_layer(W_ls, b_ls, in, act_dim, x, r_out + m * act_dim, 0);
   }
   if (subnormals) *subnormals = sub;
   return 0;

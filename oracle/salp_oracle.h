@@ -42,6 +42,10 @@ int salp_oracle_set_base_num_food(salp_oracle_t* h, int k);   /* snake:36 base_n
  * subnormals (nullable): the number of non-zero subnormal values formed on the way.  See salp_oracle.c. */
 int salp_oracle_policy_forward(const salp_policy_desc_t* desc, int32_t obs_dim, int32_t act_dim, const float* weights,
                                const float* obs, int64_t M, float* u, float* a, int64_t* subnormals);
+/* The two heads of a Gaussian policy from the public Gaussian layout of ONE policy (hidden layers, W_mu, b_mu, W_ls, b_ls,
+ * scale, shift): m [M][act_dim] the mean head, r [M][act_dim] the log-std head's raw sum before its clamp. */
+int salp_oracle_policy_forward_gaussian(const salp_policy_desc_t* desc, int32_t obs_dim, int32_t act_dim, const float* weights,
+                                        const float* obs, int64_t M, float* m, float* r, int64_t* subnormals);
 #ifdef __cplusplus
 }
 #endif

@@ -333,7 +333,7 @@ static double env_step(const struct salp_robot_oracle* h, robot_t* r, const floa
   *term = 0; *trunc = 0;
   if (dist < 0.01) { *term = 1; reward += 10.0; }
   else if (dist > 5.0) { *trunc = 1; reward -= 5.0; }
-  if (r->cycle >= 500) *trunc = 1;
+  if (r->cycle >= c->max_cycles) *trunc = 1;   /* salp_robot_env.py: 500, the config's default */
   return reward;
 }
 

@@ -23,8 +23,9 @@ def device_state(dev, cfg):
     return f64, i32
 
 
-def started(cfg, n, f64, i32, seed=pc.ENV_SEED):
-    dev = SalpLib(cfg, n, device_id=0, seed=seed)
+def started(cfg, n, f64, i32, seed=pc.ENV_SEED, base=0):
+    """A handle whose envs have the global indices base .. base + n - 1, put into the start state (f64, i32)."""
+    dev = SalpLib(cfg, n, device_id=0, seed=seed, env_index_base=base)
     dev.set_state(f64, i32, 0)
     return dev
 

@@ -38,6 +38,7 @@ PROTOTYPES = {
     "salp_oracle_global_step": (i64, [vp]),
     "salp_oracle_set_base_num_food": (cint, [vp, cint]),
     "salp_oracle_policy_forward": (cint, [vp, i32, i32, vp, vp, i64, vp, vp, vp]),
+    "salp_oracle_policy_forward_gaussian": (cint, [vp, i32, i32, vp, vp, i64, vp, vp, vp]),
 }
 
 
@@ -77,6 +78,20 @@ def policy_forward(policy, obs, weights=None):
     `policy.pack()`; obs [..., N, obs_dim], env i of the N belonging to policy i // (N / P).
     Returns u (before the output activation) and a, float32 [..., N, act_dim], and the number of non-zero subnormal values
     formed on the way."""
+    return _forward("salp_oracle_policy_forward", policy, obs, weights)
+
+
+def policy_forward_gaussian(policy, obs, weights=None):
+    """The two heads of a `GaussianPolicy` restated in C in the same arithmetic (salp_oracle_policy_forward_gaussian), from
+    the public Gaussian layout: `weights` float32 [P, words], default `policy.pack()`; obs as for `policy_forward`.
+    Returns m (the mean head) and r (the log-std head's raw sum, before its clamp), float32 [..., N, act_dim], and the number
+    of non-zero subnormal values formed on the way."""
+    if not getattr(policy, "gaussian", False):
+        raise ValueError("policy_forward_gaussian takes a GaussianPolicy")
+    return _forward("salp_oracle_policy_forward_gaussian", policy, obs, weights)
+
+
+def _forward(name, policy, obs, weights):
     x = np.ascontiguousarray(obs, dtype=np.float32)
     P, OD, AD = policy.n_policies, policy.obs_dim, policy.act_dim
     if x.shape[-1] != OD:
@@ -90,10 +105,9 @@ def policy_forward(policy, obs, weights=None):
     d, total = policy.desc(), 0
     for k in range(P):
         sub = ctypes.c_int64(0)
-        rc = lib().salp_oracle_policy_forward(ctypes.byref(d), OD, AD, _p(w[k]), _p(g[k]), g[k].size // OD, _p(u[k]), _p(a[k]),
-                                              ctypes.byref(sub))
+        rc = getattr(lib(), name)(ctypes.byref(d), OD, AD, _p(w[k]), _p(g[k]), g[k].size // OD, _p(u[k]), _p(a[k]), ctypes.byref(sub))
         if rc != 0:
-            raise RuntimeError(f"salp_oracle_policy_forward failed: {rc}")
+            raise RuntimeError(f"{name} failed: {rc}")
         total += sub.value
     back = lambda v: np.ascontiguousarray(np.moveaxis(v, 0, 1)).reshape(lead + (N, AD))
     return back(u), back(a), total

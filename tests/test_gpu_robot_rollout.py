@@ -11,8 +11,8 @@ fallbacks, by < 1e-12 relative per cycle — and which lanes step together is wh
 loop; times at most 8 cycles and rounded up that is 1e-11, and a float32 cast of such a value moves by at most one unit in
 the last place.  Each comparison also reports (prints) whether the outputs were in fact bit-identical.
 
-The oracle hard-codes the truncation after 500 cycles, so episode endings at small horizons are compared device against
-device (max_cycles = 2 or 3); the oracle comparison uses the default configuration."""
+Episode endings at small horizons are compared device against device here (max_cycles = 2 or 3); the oracle comparison
+uses the default configuration (truncation after 500 cycles)."""
 import ctypes
 import time
 

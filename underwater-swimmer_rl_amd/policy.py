@@ -11,7 +11,8 @@ evaluation in the library's fixed order may be from it.
 
 `GaussianPolicy` adds the log-std head of `sac.Actor` (salp_policy_create_gaussian): the kernel then SAMPLES the action,
 `tanh(mu + exp(log_std) z) * scale + shift`, from the policy's own Philox stream (`noise`) and returns its log-probability
-(include/salp_vec.h "Sampled actions"); `reference(obs, z)` / `error_bound(obs, z)` state and bound that computation.
+(include/salp_vec.h "Sampled actions"); `reference(obs, z)` / `error_bound(obs, z)` state and bound that computation, and
+`sampling_stage(mu, ls_raw, z)` the part of it behind the two heads alone.
 """
 from __future__ import annotations
 
@@ -355,6 +356,11 @@ class GaussianPolicy(MLPPolicy):
             x = np.maximum(x, 0.0)
         mu, e_mu = _affine(*self.layers[-1], x, e, with_bound)
         lsr, e_ls = _affine(*self.log_std, x, e, with_bound)
+        return self._sampling(mu, e_mu, lsr, e_ls, z, with_bound)
+
+    def _sampling(self, mu, e_mu, lsr, e_ls, z, with_bound: bool):
+        """Everything of `_sampled` behind the two heads: mu, lsr (the log-std head before its clamp) and z float64
+        [P, M, A]; e_mu, e_ls: how far a computed head may be from them (used with_bound only)."""
         ls = np.clip(lsr, LOG_STD_MIN, LOG_STD_MAX)
         if with_bound:      # a head that is beyond a clamp by more than its own bound leaves the clamp's constant, exactly
             e_ls = np.where((lsr + e_ls < LOG_STD_MIN) | (lsr - e_ls > LOG_STD_MAX), 0.0, e_ls)
@@ -446,6 +452,26 @@ class GaussianPolicy(MLPPolicy):
         g, gz, back, back1 = self._grouped_z(obs, z)
         _, _, ea, el = self._sampled(g, gz, True)
         return back(ea), back1(el)
+
+    def sampling_stage(self, mu, ls_raw, z):
+        """The sampling arithmetic alone, from GIVEN head values: mu and ls_raw (the log-std head before its clamp)
+        [..., N, act_dim] — float32 values, taken as exact — and z float64 of the same shape.  Returns (action, logp,
+        e_action, e_logp): the float64 action [..., N, act_dim] and log-probability [..., N] of the definition from those
+        heads, and how far a correct fp32 evaluation FROM THE SAME HEADS may be from them.  Nothing is carried in
+        (e_mu = e_ls = 0, the clamp is exact); what remains are the terms of `_sampled` behind the heads: expf, the noise's
+        logf / sqrtf / cospif, the fma, tanhf, log1pf and the roundings of the logp chain, through the named ULP_* alone."""
+        m, r, zz = (np.asarray(v, dtype=np.float64) for v in (mu, ls_raw, z))
+        if m.shape[-1] != self.act_dim or r.shape != m.shape or zz.shape != m.shape:
+            raise ValueError(f"mu, ls_raw and z must share one shape [..., N, {self.act_dim}]; got {m.shape}, {r.shape}, {zz.shape}")
+        lead, N, P, A = m.shape[:-2], m.shape[-2], self.n_policies, self.act_dim
+        self.check_envs(N)
+        group = lambda v: np.moveaxis(v.reshape(-1, P, N // P, A), 1, 0).reshape(P, -1, A)
+        gm = group(m)
+        zero = np.zeros_like(gm)
+        a, lp, ea, el = self._sampling(gm, zero, group(r), zero, group(zz), True)
+        back = lambda v: np.moveaxis(v.reshape(P, -1, N // P, A), 0, 1).reshape(lead + (N, A))
+        back1 = lambda v: np.moveaxis(v.reshape(P, -1, N // P), 0, 1).reshape(lead + (N,))
+        return back(a), back1(lp), back(ea), back1(el)
 
 
 def _affine(W, b, x, e, with_bound: bool):
