@@ -3,7 +3,8 @@
 (tests/golden/ref_harness.py) in the build container.  Run:  python tests/golden/gen_golden.py
 
 Each fixture `ref_<case>.npz` holds inputs and expected outputs only (no reference source):
-  cfg_json      the 13 reference kwargs + seed / env_index_base / case notes
+  cfg_json      the 13 reference kwargs + seed / env_index_base / case notes, and every parent constant that is off its
+                default (tank_margin, base_radius, ...: golden_util.CONSTANTS), written into the reference env as attributes
   actions       f32 [H, N, act_dim]
   inject_f64 / inject_i32 (optional)  state snapshot rows written before the first step
                 (public layout of include/salp_vec.h; what eval/collect_navigation_data.py:76-89 pokes)
@@ -15,6 +16,7 @@ Each fixture `ref_<case>.npz` holds inputs and expected outputs only (no referen
   info          i32 [H, N, 3]         food_collected, steps_since_food, collision (pre-autoreset)
   end_f64 / end_i32   state snapshot after the last step
   food_schedule (optional) i32 [M, 2]  rows (t, k): `env.base_num_food_items = k` written before step t
+  wall_clamp_without_collision (rt_* only) u8 [H, N]  steps the reference clamped at a wall and reported no collision
 Autoreset is emulated the way a VectorEnv would drive the reference: when step() reports
 terminated or truncated, reset() is called and its observation replaces the returned one.
 """
@@ -30,8 +32,10 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
+import golden_util as gu  # noqa: E402
 import ref_harness as rh  # noqa: E402
 import underwater_swimmer_rl_amd as pkg  # noqa: E402
 
@@ -89,16 +93,22 @@ class _Any:
 ONLY = [None]
 
 
-def run_case(name, params, actions, seed, base=0, inject=None, notes="", food_schedule=None):
+def run_case(name, params, actions, seed, base=0, inject=None, notes="", food_schedule=None, check=None, hold=None):
+    """`params`: a preset with overrides, or the fields of a full SalpSnakeConfig.  Parent constants off their defaults are
+    written into the reference env as attributes (ref_harness.ReferenceEnv) and into cfg_json next to the 13 kwargs.
+    `check(cfg, out)` runs on the arrays before anything is written and raises if the vector misses what it is for."""
     if ONLY[0] and name not in ONLY[0]:
         import collections
         return collections.defaultdict(_Any)
     ESCAPES[0] = 0
+    params = dict(params)
     cfg = pkg.load_env_config(params.pop("preset"), **params) if "preset" in params else pkg.SalpSnakeConfig(**params)
+    assert cfg.angular_drag == 0.95, "angular_drag is a literal in the reference (salp_robot.py:320)"
+    constants = gu.non_default_constants(cfg)
     H, n, ad = actions.shape
     assert ad == cfg.act_dim
     F, od = cfg.num_food_items, cfg.obs_dim
-    envs = [rh.ReferenceEnv(seed, base + i, **cfg.env_kwargs()) for i in range(n)]
+    envs = [rh.ReferenceEnv(seed, base + i, constants=constants, **cfg.env_kwargs()) for i in range(n)]
     for r in envs:
         r.episode_length = 0
         r.shape_hold = 7
@@ -118,6 +128,7 @@ def run_case(name, params, actions, seed, base=0, inject=None, notes="", food_sc
     trunc = np.zeros((H, n), np.uint8)
     info = np.zeros((H, n, 3), np.int32)
     sched = dict(food_schedule or [])
+    escaped = np.zeros((H, n), np.uint8)
     for t in range(H):
         if t in sched:      # the curriculum's attribute poke (continuous_trainer.py:409-411), before step t
             for r in envs:
@@ -134,6 +145,7 @@ def run_case(name, params, actions, seed, base=0, inject=None, notes="", food_sc
             clamped = (r.env.robot_pos[0] in (m, r.env.width - m)) or (r.env.robot_pos[1] in (m, r.env.height - m))
             if clamped and not inf["collision"]:
                 ESCAPES[0] += 1
+                escaped[t, i] = 1
             rew[t, i], term[t, i], trunc[t, i] = rw, te, tr
             info[t, i] = (inf["food_collected"], inf["steps_since_food"], int(inf["collision"]))
             if (te or tr) and not cfg.no_autoreset:      # no_autoreset: a hand loop that ignores `done`
@@ -146,17 +158,28 @@ def run_case(name, params, actions, seed, base=0, inject=None, notes="", food_sc
     meta = dict(cfg.env_kwargs(), seed=seed, env_index_base=base, case=name, notes=notes)
     if cfg.no_autoreset:
         meta["no_autoreset"] = True
+    meta.update(constants)
     out = dict(cfg_json=np.array(json.dumps(meta)), actions=actions, reset_obs=reset_obs, obs=obs, final_obs=fin,
                reward=rew, terminated=term, truncated=trunc, info=info, end_f64=end_f64, end_i32=end_i32)
     if inj_f64 is not None:
         out["inject_f64"], out["inject_i32"] = inj_f64, inj_i32
     if food_schedule:
         out["food_schedule"] = np.asarray(sorted(food_schedule), np.int32)     # rows (step, base_num_food_items)
+    if name.startswith("rt_"):      # the reference's own clamps at a wall that it did not report as a collision, per step
+        out["wall_clamp_without_collision"] = escaped
+    if check is not None:
+        check(cfg, out)
     path = os.path.join(HERE, f"ref_{name}.npz")
-    np.savez_compressed(path, **out)
     ev = dict(terminated=int(term.sum()), truncated=int(trunc.sum()), food=int(info[..., 0].max()),
               collisions=int(info[..., 2].sum()), wall_clamps_without_collision=ESCAPES[0])
-    print(f"{name:28s} H={H:5d} N={n:2d} {ev}  -> {os.path.getsize(path) / 1024:.0f} KiB")
+
+    def write():
+        np.savez_compressed(path, **out)
+        print(f"{name:28s} H={H:5d} N={n:2d} {ev}  -> {os.path.getsize(path) / 1024:.0f} KiB")
+    if hold is None:
+        write()
+    else:       # the caller writes the set once its conditions over all of it hold
+        hold.append((name, cfg, out, write))
     return ev
 
 
@@ -341,6 +364,100 @@ def main(only=None):
     # --- env_index_base: the same global envs from a shard
     run_case("shard_base_1000", dict(preset="single_food_long_horizon"), uniform_actions(128, 4, 1, 23), seed=1001,
              base=1000, notes="global env indices 1000..1003")
+
+    rt_cases()
+
+
+RT_ENVS, RT_STEPS = 16, 250
+
+
+def wall_start(cfg, seed, calm=(), foods_at_hand=False):
+    """Start state of the rt_* vectors: env i heads for wall i % 4 (left, right, top, bottom), its body edge at its widest
+    (1.3 base_radius, the rest shape) 3 to 60 px from that wall, moving towards it at 0.3 to 3 px/step.  `calm` envs take the
+    far, slow end of both ranges (55 px, 0.4 px/step); with `foods_at_hand` their first three foods lie 3, 6 and 9 px from
+    them, one capture per step."""
+    def inj(f64, i32):
+        n = f64.shape[1]
+        F = (f64.shape[0] - F_FOOD0) // 2
+        rng = np.random.default_rng(seed)
+        gap, speed = rng.uniform(3.0, 60.0, n), rng.uniform(0.3, 3.0, n)
+        along, drift = rng.uniform(0.3, 0.7, n), rng.uniform(-0.5, 0.5, n)
+        f64[F_THETA] = rng.uniform(-math.pi, math.pi, n)
+        ang = rng.uniform(-math.pi, math.pi, (3, n))
+        r = 1.3 * cfg.base_radius
+        size = (cfg.width, cfg.height)
+        for i in range(n):
+            g, v = (55.0, 0.4) if i in calm else (gap[i], speed[i])
+            axis, far = divmod(i % 4, 2)            # 0 left, 1 right, 2 top, 3 bottom
+            pos = np.array([along[i] * cfg.width, along[i] * cfg.height])
+            vel = np.array([drift[i], drift[i]])
+            pos[axis] = size[axis] - cfg.tank_margin - g - r if far else cfg.tank_margin + g + r
+            vel[axis] = v if far else -v
+            f64[F_X, i], f64[F_Y, i], f64[F_VX, i], f64[F_VY, i] = pos[0], pos[1], vel[0], vel[1]
+            if foods_at_hand and i in calm:
+                for k, d in enumerate((3.0, 6.0, 9.0)):
+                    f64[F_FOOD0 + k, i] = pos[0] + d * math.cos(ang[k, i])
+                    f64[F_FOOD0 + F + k, i] = pos[1] + d * math.sin(ang[k, i])
+    return inj
+
+
+def rt_cases():
+    """Vectors off the reference's default constants: every class of kernel that reads its constants from
+    the launch parameters, each of the thirteen run-time values off its default in at least one vector, start states at the
+    walls.  The conditions (golden_util.RT_*) are counted on the reference's own run; a set that misses one is not written."""
+    n, H = RT_ENVS, RT_STEPS
+    held = []
+
+    def case(name, params, actions, seed, start_seed, notes, **start):
+        cfg = pkg.load_env_config(params["preset"], **{k: v for k, v in params.items() if k != "preset"})
+
+        def check(cfg, out):
+            ev = gu.rt_events(cfg, out)
+            print(f"{name:28s} {ev} clamps without collision {int(out['wall_clamp_without_collision'].sum())}")
+            gu.check_rt_case(name, ev)
+        run_case(name, params, actions, seed=seed, inject=wall_start(cfg, start_seed, **start), notes=notes, check=check,
+                 hold=held)
+
+    case("rt_tank_f1", dict(preset="single_food", width=900, height=700, tank_margin=40.0, max_steps_without_food=70),
+         uniform_actions(H, n, 1, 201), seed=301, start_seed=401, notes="<1, 3, !STD>: 900x700 tank, margin 40")
+    case("rt_f3_norespawn", dict(preset="sac_gail", num_food_items=3, respawn_food=False, width=900, tank_margin=40.0,
+                                 food_radius=22.0, max_steps_without_food=70),
+         uniform_actions(H, n, 1, 202), seed=302, start_seed=402, calm=(12, 13, 14, 15), foods_at_hand=True,
+         notes="<4, 3, !STD>: completion without respawn, wider tank, larger food")
+    # free breathing: holds of 2-3 steps release back to rest (water <= 0.05 of a 61-step inhale), 5-18 steps release into
+    # the short exhale int(97 * 0.3), longer ones into a scaled or a full exhale
+    a = np.zeros((H, n, 2), np.float32)
+    a[..., 1] = uniform_actions(H, n, 1, 203)[..., 0]
+    pat = [(3, 6), (10, 40), (70, 100), (2, 5), (16, 35), (30, 60), (6, 31), (62, 90)]        # (hold, release) steps
+    for i in range(n):
+        t, j = 0, i
+        while t < H:
+            hold, rel = pat[j % len(pat)]
+            a[t:t + hold, i, 0] = 0.9
+            a[t + hold:t + hold + rel, i, 0] = 0.2
+            t += hold + rel
+            j += 1
+    case("rt_free_f5", dict(preset="sac_gail", num_food_items=5, forced_breathing=False, width=1000, base_radius=33.7,
+                            tank_margin=37.5, food_radius=11.0, min_food_distance=60.0, inhale_duration=61, exhale_duration=97,
+                            rest_duration=45, max_steps_without_food=80),
+         a, seed=303, start_seed=403, notes="<8, 3, !STD>: two actions, early releases, odd radius and margin")
+    case("rt_physics_f12", dict(preset="sac_gail", drag_coefficient=0.97, max_thrust_force=120.0, base_radius=26.0,
+                                inhale_duration=100, exhale_duration=130, rest_duration=30, nozzle_response_rate=0.08,
+                                max_nozzle_angle=0.9, tank_margin=50.1, max_steps_without_food=124),
+         uniform_actions(H, n, 1, 204), seed=304, start_seed=404, notes="<12, 3, !STD>: other physics, default tank size")
+    case("rt_crowded_f16", dict(preset="sac_gail", num_food_items=16, width=700, height=520, food_radius=19.9,
+                                min_food_distance=123.4, proximity_reward_weight=2.0, max_steps_without_food=60),
+         uniform_actions(H, n, 1, 205), seed=305, start_seed=405,
+         notes="<16, 3, !STD>: 16 foods that cannot keep their distance, the reset's fallback draw")
+    case("rt_generic_f9_k5", dict(preset="sac_gail", num_food_items=9, max_observed_food=5, width=1234, height=777,
+                                  base_radius=21.3, tank_margin=41.3, max_thrust_force=157.0, drag_coefficient=0.953,
+                                  inhale_duration=77, exhale_duration=201, max_steps_without_food=120),
+         uniform_actions(H, n, 1, 206), seed=306, start_seed=406, notes="<12, 8>: the generic kernel, five observed foods")
+    if len(held) == 6:      # a partial run (`gen_golden.py rt_tank_f1`) cannot judge the set
+        gu.check_rt_set({name: gu.rt_events(cfg, out) for name, cfg, out, _ in held},
+                        {name: int(out["wall_clamp_without_collision"].sum()) for name, cfg, out, _ in held})
+    for *_, write in held:
+        write()
 
 
 if __name__ == "__main__":

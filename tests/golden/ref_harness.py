@@ -223,13 +223,22 @@ class ReferenceEnv:
     The constructor burns its draws on a throw-away stream (the reference's __init__
     generates food twice, salp_snake_env.py:62->151 and :90); the env's real stream
     starts at counter 0 with the first explicit reset().
+
+    `constants`: parent constants (salp_robot.py:32-53, salp_snake_env.py:53-54) written as instance attributes after
+    construction and before the first reset(), the way the reference's evaluation scripts poke attributes.  That is
+    enough: reset() re-derives the body shape from `base_radius` (salp_robot.py:111-113) and nothing else is cached
+    (`base_surface_area` is never read).
     """
 
-    def __init__(self, seed: int, env_index: int, **params):
+    def __init__(self, seed: int, env_index: int, constants=None, **params):
         cls, self._rproxy, self._nproxy = load_reference()
         self.stream = EnvStream(seed, env_index)
         self._bind(EnvStream(0xDEAD, 0xBEEF))
         self.env = cls(render_mode=None, **params)
+        for name, value in (constants or {}).items():
+            if not hasattr(self.env, name):
+                raise AttributeError(f"the reference env has no attribute {name}")
+            setattr(self.env, name, value)
         self._bind(self.stream)
 
     def _bind(self, stream):

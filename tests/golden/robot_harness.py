@@ -77,9 +77,11 @@ def load():
 
 
 class ReferenceRobotEnv:
-    """make_env() of train_robot.py:10-22 with the target stream of (seed, env_index)."""
+    """make_env() of train_robot.py:10-22 with the target stream of (seed, env_index).  `width` / `height` / `tank_margin`
+    (None = the reference's 900 / 700 / 50) are written as attributes after construction, before the first counted reset():
+    every reset reads them afresh for the target's range (salp_robot_env.py:320-323), nothing else keeps them."""
 
-    def __init__(self, seed, env_index):
+    def __init__(self, seed, env_index, width=None, height=None, tank_margin=None):
         robot_mod, env_mod, self._proxy = load()
         nozzle = robot_mod.Nozzle(length1=0.05, length2=0.05, length3=0.05, area=0.00016, mass=1.0)
         robot = robot_mod.Robot(dry_mass=1.0, init_length=0.3, init_width=0.15, max_contraction=0.06, nozzle=nozzle)
@@ -88,6 +90,10 @@ class ReferenceRobotEnv:
         self.stream = TargetStream(seed, env_index)
         self._proxy.stream = TargetStream(0xBAD, 0xBAD)      # the constructor's own reset() burns a throw-away stream
         self.env = env_mod.SalpRobotEnv(render_mode=None, robot=robot)
+        for name, value in (("width", width), ("height", height), ("tank_margin", tank_margin)):
+            if value is not None:
+                assert hasattr(self.env, name)
+                setattr(self.env, name, value)
 
     def reset(self):
         self._proxy.stream = self.stream

@@ -1,4 +1,5 @@
 """Shared helpers for the golden-vector tests (tests/golden/ref_*.npz, made by gen_golden.py)."""
+import dataclasses
 import glob
 import json
 import os
@@ -12,17 +13,44 @@ GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 KW = ("width", "height", "num_food_items", "food_reward", "collision_penalty", "time_penalty", "efficiency_bonus",
       "forced_breathing", "max_observed_food", "random_food_count", "respawn_food", "proximity_reward_weight",
       "max_steps_without_food")
+# the parent constants a fixture may store next to the 13 kwargs, when they are off their defaults (salp_robot.py:32-53,
+# salp_snake_env.py:53-54).  `angular_drag` is not among them: it is a literal in the reference (salp_robot.py:320).
+CONSTANTS = ("tank_margin", "base_radius", "max_thrust_force", "drag_coefficient", "max_nozzle_angle",
+             "nozzle_response_rate", "inhale_duration", "exhale_duration", "rest_duration", "food_radius", "min_food_distance")
+# the thirteen values that reach the kernels which read their constants from the launch parameters
+RUNTIME_VALUES = ("width", "height") + CONSTANTS
+DEFAULTS = {f.name: f.default for f in dataclasses.fields(pkg.SalpSnakeConfig)}
+
+# obs columns (salp_robot.py:377-388) and info columns used by the event counts
+OBS_X, OBS_Y, OBS_SIZE, OBS_PHASE, OBS_WATER = 0, 1, 6, 7, 8
+INFO_FOOD_COLLECTED, INFO_STEPS_SINCE_FOOD, INFO_COLLISION = 0, 1, 2
+WALLS = ("left", "right", "top", "bottom")
 
 
 def fixture_names():
     return sorted(os.path.basename(p)[4:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, "ref_*.npz")))
 
 
+def rt_fixture_names():
+    """The vectors generated off the reference's default constants (gen_golden.py `rt_*`)."""
+    return [n for n in fixture_names() if n.startswith("rt_")]
+
+
+def non_default_constants(cfg):
+    return {k: getattr(cfg, k) for k in CONSTANTS if getattr(cfg, k) != DEFAULTS[k]}
+
+
+def cfg_from_meta(meta, **overrides):
+    """A fixture without stored constants loads exactly as before they existed: the 13 kwargs, defaults elsewhere."""
+    kw = {k: meta[k] for k in KW + tuple(c for c in CONSTANTS if c in meta)}
+    kw.update(overrides)
+    return pkg.SalpSnakeConfig(**kw, no_autoreset=bool(meta.get("no_autoreset", False)))
+
+
 def load_fixture(name):
     z = np.load(os.path.join(GOLDEN_DIR, f"ref_{name}.npz"), allow_pickle=False)
     meta = json.loads(str(z["cfg_json"]))
-    cfg = pkg.SalpSnakeConfig(**{k: meta[k] for k in KW}, no_autoreset=bool(meta.get("no_autoreset", False)))
-    return z, meta, cfg
+    return z, meta, cfg_from_meta(meta)
 
 
 def obs_diff(cfg, a, b):
@@ -32,3 +60,80 @@ def obs_diff(cfg, a, b):
     for c in angle_cols(cfg):
         d[..., c] = np.minimum(d[..., c], 2.0 - d[..., c])
     return np.nan_to_num(d, nan=0.0)
+
+
+# (food slots, observed capacity, literal constants) of the kernel each rt_* vector must run, as salp_vec_last_launch
+# reports it: one vector per class of kernel that reads its constants from the launch parameters
+RT_KERNEL = {
+    "rt_tank_f1": (1, 3, 0), "rt_f3_norespawn": (4, 3, 0), "rt_free_f5": (8, 3, 0), "rt_physics_f12": (12, 3, 0),
+    "rt_crowded_f16": (16, 3, 0), "rt_generic_f9_k5": (12, 8, 0),
+}
+
+# What each rt_* vector must show (at least), and what the set must show together.  gen_golden.py refuses to write a
+# vector that misses its row; tests/test_rt_fixture_recipe.py asserts the same from the stored arrays.
+RT_EVERY_CASE = dict(truncated=1, twice=1)
+RT_CASE_FLOORS = {
+    "rt_crowded_f16": dict(fallback_foods=1, captures=5),
+    "rt_free_f5": dict(short_exhale=1, back_to_rest=1),
+    "rt_f3_norespawn": dict(completed=1),
+}
+RT_SET_EPISODES_PER_WALL = 3
+RT_SET_CLAMPS_WITHOUT_COLLISION = 3
+
+
+def check_rt_case(name, ev):
+    for k, v in dict(RT_EVERY_CASE, **RT_CASE_FLOORS.get(name, {})).items():
+        assert ev[k] >= v, f"{name}: {k} = {ev[k]}, the vector needs at least {v} ({ev})"
+
+
+def check_rt_set(events, clamps):
+    """`events`: rt_events of every vector of the set by name; `clamps`: their wall_clamp_without_collision totals."""
+    for w in WALLS:
+        total = sum(ev["walls"][w] for ev in events.values())
+        assert total >= RT_SET_EPISODES_PER_WALL, f"the {w} wall ends {total} episodes over the set"
+    assert sum(clamps.values()) >= RT_SET_CLAMPS_WITHOUT_COLLISION, f"clamps without a collision over the set: {clamps}"
+
+
+def rt_events(cfg, z):
+    """Event counts of one vector, from the arrays a fixture stores (`z`: the npz or the dict about to be written).
+      walls           episodes ended by each wall (left, right, top, bottom; a corner hit counts for both), told from the
+                      terminal observation: body edge (obs 6 * base_radius) at or beyond the wall, to 0.01 px — the
+                      observation is float32, which moves x by at most 1e-4 px
+      captures        steps that collected a food (steps_since_food is 0 after a step only then)
+      completed       terminations without a collision (respawn_food=False: the last food collected)
+      truncated, twice (envs that finish at least two episodes)
+      short_exhale    early releases with 0.05 < water < 0.3: the step that turns `inhaling` into `exhaling` shows the inhaled
+                      water unchanged; below 0.3 the exhale lasts int(exhale_duration * 0.3) steps (salp_robot.py:223)
+      back_to_rest    early releases with water <= 0.05: `inhaling` straight to `rest` on a step that ends no episode
+      fallback_foods  foods of the reset's layout closer than min_food_distance to an earlier food or to the tank centre:
+                      rejection sampling (salp_snake_env.py:97-123) never accepts those, so each one is the unconditional
+                      draw after 100 failed attempts (:126-131).  Counted only where the injection left the foods alone."""
+    term, trunc, info = z["terminated"].astype(bool), z["truncated"].astype(bool), z["info"]
+    done = term | trunc
+    hit = term & (info[..., INFO_COLLISION] != 0)
+    fin = z["final_obs"].astype(np.float64)
+    x, y, r = fin[..., OBS_X] * cfg.width, fin[..., OBS_Y] * cfg.height, fin[..., OBS_SIZE] * cfg.base_radius
+    m, eps = cfg.tank_margin, 0.01
+    with np.errstate(invalid="ignore"):
+        at = (x - r <= m + eps, x + r >= cfg.width - m - eps, y - r <= m + eps, y + r >= cfg.height - m - eps)
+    walls = {w: int((hit & a).sum()) for w, a in zip(WALLS, at)}
+    assert not (hit & ~(at[0] | at[1] | at[2] | at[3])).any(), "a collision at no wall"
+    phase = np.concatenate([z["reset_obs"][None, :, OBS_PHASE], z["obs"][:, :, OBS_PHASE]])
+    water = z["obs"][:, :, OBS_WATER]
+    released = (phase[:-1] == 0.5) & ~done          # the row is the step's own observation, not a post-reset one
+    short = released & (phase[1:] == 1.0) & (water > 0.05) & (water < 0.3)
+    rest = released & (phase[1:] == 0.0)
+    fallback = -1
+    if "inject_f64" in getattr(z, "files", z):
+        F = cfg.num_food_items
+        f = z["inject_f64"]
+        fx, fy = f[10:10 + F], f[10 + F:10 + 2 * F]
+        fallback = 0
+        for e in range(fx.shape[1]):
+            for k in range(F):
+                d = [np.hypot(fx[k, e] - cfg.width / 2, fy[k, e] - cfg.height / 2)]
+                d += [np.hypot(fx[k, e] - fx[j, e], fy[k, e] - fy[j, e]) for j in range(k)]
+                fallback += int(min(d) < cfg.min_food_distance)
+    return dict(walls=walls, collisions=int(hit.sum()), captures=int((info[..., INFO_STEPS_SINCE_FOOD] == 0).sum()),
+                completed=int((term & ~hit).sum()), truncated=int(trunc.sum()), twice=int((done.sum(axis=0) >= 2).sum()),
+                short_exhale=int(short.sum()), back_to_rest=int(rest.sum()), fallback_foods=fallback)

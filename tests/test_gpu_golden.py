@@ -4,7 +4,7 @@ implementation (tests/golden/ref_*.npz): flags and info integers identical, obse
 import numpy as np
 import pytest
 
-from golden_util import fixture_names, load_fixture, obs_diff
+from golden_util import RT_KERNEL, fixture_names, load_fixture, obs_diff, rt_fixture_names
 from underwater_swimmer_rl_amd import _capi
 from underwater_swimmer_rl_amd._capi import SalpLib
 
@@ -36,6 +36,9 @@ def test_hip_matches_reference_vectors(name):
             assert dev.base_num_food == sched[t]
         dev.step(act[t], obs[t], rew[t], term[t], trunc[t], fin[t], info, 0)
         assert np.array_equal(info, z["info"][t]), f"info at step {t}"
+    if name in RT_KERNEL:       # a vector off the default constants that ran a literal-constant kernel pins nothing new
+        ll = dev.last_launch()
+        assert (ll["food_slots"], ll["observed_capacity"], ll["literal_constants"]) == RT_KERNEL[name], (name, ll)
     assert np.array_equal(term, z["terminated"]) and np.array_equal(trunc, z["truncated"])
     nan_ref = np.isnan(z["obs"])
     assert np.array_equal(np.isnan(obs), nan_ref)
@@ -50,6 +53,45 @@ def test_hip_matches_reference_vectors(name):
     r = z["reward"]
     ok = np.isfinite(r)
     assert (np.abs(rew[ok] - r[ok]) / np.maximum(1.0, np.abs(r[ok]))).max() <= 1e-5
+    f64 = np.empty((_capi.F_FOOD0 + 2 * cfg.num_food_items, n), np.float64)
+    i32 = np.empty((_capi.I_COUNT, n), np.int32)
+    dev.get_state(f64, i32, 0)
+    assert np.array_equal(i32, z["end_i32"]), np.nonzero(i32 != z["end_i32"])
+    e = z["end_f64"]
+    assert np.array_equal(np.isnan(f64), np.isnan(e))
+    assert np.nanmax(np.abs(f64 - e)) <= 1e-9
+    dev.close()
+
+
+@pytest.mark.parametrize("name", rt_fixture_names())
+def test_fused_rollout_matches_reference_vectors_off_the_defaults(name):
+    """The rt_* vectors (tests/golden/gen_golden.py `rt_cases`: run-time constants off the reference's defaults, swimmers
+    started at the four walls) through ONE fused salp_vec_rollout launch from the injected state, with final_obs: the
+    rollout kernel's own terminal branch against the reference's wall endings, clamps without a collision, time-outs and
+    completions.  Same tolerances as the stepwise test; the launch must be the run-time-constant kernel of the vector's class."""
+    z, meta, cfg = load_fixture(name)
+    act = np.ascontiguousarray(z["actions"])
+    H, n, _ = act.shape
+    dev = SalpLib(cfg, n, device_id=0, seed=meta["seed"], env_index_base=meta["env_index_base"])
+    dev.set_state(np.ascontiguousarray(z["inject_f64"]), np.ascontiguousarray(z["inject_i32"]), 0)
+    obs = np.empty((H, n, cfg.obs_dim), np.float32)
+    fin = np.full((H, n, cfg.obs_dim), np.nan, np.float32)
+    rew = np.empty((H, n), np.float32)
+    term = np.empty((H, n), np.uint8)
+    trunc = np.empty((H, n), np.uint8)
+    dev.rollout(act, H, obs, rew, term, trunc, fin, None, 0)
+    ll = dev.last_launch()
+    assert (ll["food_slots"], ll["observed_capacity"], ll["literal_constants"]) == RT_KERNEL[name], (name, ll)
+    assert ll["actions_in_kernel"] == 0 and ll["envs_unpredicated"] + ll["envs_predicated"] == n
+    assert np.array_equal(term, z["terminated"]) and np.array_equal(trunc, z["truncated"])
+    assert not np.isnan(obs).any()
+    assert obs_diff(cfg, obs, z["obs"]).max() <= 1e-5
+    done = (z["terminated"] | z["truncated"]).astype(bool)
+    assert done.any() and np.array_equal(~np.isnan(fin[..., 0]), done)      # terminal rows are written for finished envs only
+    assert not np.isnan(fin[done]).any()
+    assert obs_diff(cfg, fin[done], z["final_obs"][done]).max() <= 1e-5
+    r = z["reward"]
+    assert np.isfinite(r).all() and (np.abs(rew - r) / np.maximum(1.0, np.abs(r))).max() <= 1e-5
     f64 = np.empty((_capi.F_FOOD0 + 2 * cfg.num_food_items, n), np.float64)
     i32 = np.empty((_capi.I_COUNT, n), np.int32)
     dev.get_state(f64, i32, 0)

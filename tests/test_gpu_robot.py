@@ -24,7 +24,9 @@ def test_hip_robot_matches_reference_vectors(path):
     meta = json.loads(str(z["meta"]))
     act = z["actions"]
     T, n, _ = act.shape
-    env = SalpRobotVectorEnv(n, device=0, seed=meta["seed"], env_index_base=meta["env_index_base"], output="numpy")
+    tank = {k: meta[k] for k in ("width", "height", "tank_margin") if k in meta}      # the three vectors off the 900x700 tank
+    env = SalpRobotVectorEnv(n, device=0, seed=meta["seed"], env_index_base=meta["env_index_base"], output="numpy", **tank)
+    assert (env.cfg.width, env.cfg.height, env.cfg.tank_margin) == (meta.get("width", 900), meta.get("height", 700), meta.get("tank_margin", 50))
     assert rel(env.observe(), z["reset_obs"]) <= TOL
     for t in range(T):
         obs, rew, term, trunc, info = env.step(act[t])

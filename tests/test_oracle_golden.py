@@ -11,7 +11,8 @@ NAMES = fixture_names()
 
 
 def test_fixtures_present():
-    assert len(NAMES) >= 14, NAMES
+    assert len(NAMES) >= 20, NAMES
+    assert sum(n.startswith("rt_") for n in NAMES) == 6, NAMES      # the vectors off the reference's default constants
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -15,10 +15,20 @@ from support import rel
 
 GOLD = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "robot_*.npz")))
 TOL = 1e-6
+TANK_KEYS = ("width", "height", "tank_margin")
 
 
 def test_fixtures_present():
-    assert len(GOLD) == 3
+    assert len(GOLD) == 6
+
+
+def robot_config(meta):
+    """The oracle's configuration for a vector: the reference's own, with the tank the vector's `meta` names (if any)."""
+    cfg = rol.default_robot_config()
+    for k in TANK_KEYS:
+        if k in meta:
+            setattr(cfg, k, meta[k])
+    return cfg
 
 
 @pytest.mark.parametrize("path", GOLD, ids=[os.path.basename(p)[:-4] for p in GOLD])
@@ -27,7 +37,7 @@ def test_robot_oracle_matches_reference_vectors(path):
     meta = json.loads(str(z["meta"]))
     act = z["actions"]
     T, n, _ = act.shape
-    orc = rol.RobotOracleVec(n, seed=meta["seed"], env_index_base=meta["env_index_base"])
+    orc = rol.RobotOracleVec(n, seed=meta["seed"], env_index_base=meta["env_index_base"], cfg=robot_config(meta))
     assert rel(orc.reset(np.zeros(n, np.uint8)), z["reset_obs"]) <= TOL
     for t in range(T):
         out = orc.step(act[t])
@@ -40,6 +50,31 @@ def test_robot_oracle_matches_reference_vectors(path):
             assert rel(out["final_obs"][done], z["final_obs"][t][done]) <= TOL
     assert rel(orc.get_state(), z["end_state"]) <= TOL
     orc.close()
+
+
+def test_other_tank_vectors_hold_their_events():
+    """What the three vectors off the reference's 900x700 tank were made for, from the stored arrays."""
+    z = {os.path.basename(p)[6:-4]: np.load(p, allow_pickle=False) for p in GOLD}
+    metas = {k: json.loads(str(v["meta"])) for k, v in z.items()}
+    assert [metas[k].get(t) for k in ("target_reached", "small_tank", "wide_tank") for t in TANK_KEYS] == \
+        [100, 100, 50, 300, 260, 35, 2400, 1800, 20]
+    assert not any(t in metas[k] for k in ("cycles", "max_cycles", "out_of_bounds") for t in TANK_KEYS)
+    r = z["target_reached"]
+    term, inner = r["terminated"].astype(bool), r["inner_steps"]
+    assert r["actions"].shape[:2] == (12, 4) and term.sum() >= 20
+    assert (r["end_state"][rol.R_TARGET:rol.R_TARGET + 2] == 0.0).all()                # every target is the origin
+    assert (term[:, 0::2].any(axis=1) & (~term[:, 1::2] & (inner[:, 1::2] > 100)).any(axis=1)).any()
+    assert (r["reward"][term] > 9.0).all()                                             # the +10 of reaching the target
+    for name, reach in (("small_tank", (0.575, 0.475)), ("wide_tank", (5.9, 4.4))):
+        s = z[name]
+        assert s["actions"].shape[:2] == (40, 4)
+        tx, ty = np.abs(s["end_state"][rol.R_TARGET]), np.abs(s["end_state"][rol.R_TARGET + 1])
+        assert (tx <= reach[0] + 1e-6).all() and (ty <= reach[1] + 1e-6).all(), name
+    w = z["wide_tank"]
+    assert w["truncated"].sum() >= 1 and w["actions"].shape[0] < 500                   # 40 cycles, not 500: distance > 5 m
+    gone = w["final_obs"][w["truncated"].astype(bool)]
+    assert (np.hypot(gone[:, 0], gone[:, 1]) > 5.0).all()                              # obs 0-1: position minus target
+    assert np.hypot(*w["end_state"][rol.R_TARGET:rol.R_TARGET + 2]).max() > 2.9        # a target the default tank cannot place
 
 
 def test_cycle_structure():
