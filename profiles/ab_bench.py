@@ -12,6 +12,9 @@ the actions it takes into the shared action block, so with --launches 1 and the 
 variant behind it replays exactly those actions from the same state (the price of the policy block alone).
 "+evaluate": salp_vec_evaluate_policy with the same policy as "+policy" (one 32-byte summary record per env, no per-step
 output); pair it against "+policy" of the PARENT commit's library: `par+policy=parent.so new+evaluate=libsalp_hip.so`.
+"+policypacked" / "+policypackedfinal": salp_vec_rollout_policy_packed with the same policy (records of obs_dim + 4 /
+2 obs_dim + 4 words, the actions into the shared block like "+policy"); pair it against "+policy" of the same library, and
+for scale "+packed" against a plain variant: the closed-loop ratio should lie near the open-loop one.
 --policy linear | mlp32 | mlp64 picks the policy of both: the 25-parameter linear clip rule (the pursuit rule), or the
 24 -> 32 -> 32 -> A / 24 -> 64 -> 64 -> A actor.
 "+actorgraph": the same actor in torch around salp_vec_step, `SalpVectorEnv.capture_policy_steps(n_steps = chunk)` replayed
@@ -94,6 +97,10 @@ def main():
             return
         if "+evaluate" in name:
             _capi.check(lib, lib.salp_vec_evaluate_policy(h, policies[name], H, vp(eval_rec.data_ptr()), _capi.SALP_DEVICE_PTRS, st), "evaluate_policy")
+            return
+        if "+policypacked" in name:
+            flags = _capi.SALP_DEVICE_PTRS | (_capi.REC_FINAL_OBS if name.endswith("+policypackedfinal") else 0)
+            _capi.check(lib, lib.salp_vec_rollout_policy_packed(h, policies[name], H, vp(rec.data_ptr()), vp(act.data_ptr()), flags, st), "rollout_policy_packed")
             return
         if "+policy" in name:
             _capi.check(lib, lib.salp_vec_rollout_policy(h, policies[name], H, vp(obs.data_ptr()), vp(rew.data_ptr()), vp(term.data_ptr()),

@@ -58,14 +58,18 @@ class CRobotConfig(ctypes.Structure):
 
 
 def _prototypes():
-    """name -> (restype, argtypes) of every function of include/salp_robot_rollout.h, of include/salp_robot_sampled.h, of
-    include/salp_robot_evaluate.h, and of every function of include/salp_vec.h and include/salp_robot.h, in header order
+    """name -> (restype, argtypes) of every function of include/salp_vec_policy_packed.h, of include/salp_robot_rollout.h, of
+    include/salp_robot_sampled.h, of include/salp_robot_evaluate.h, and of every function of include/salp_vec.h and include/salp_robot.h, in header order
     (tests/test_capi_prototypes.py compares the last table with its two headers).  vp: a handle, a buffer (host or device) or a stream."""
     vp, i64, u64, i32, u32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int32, ctypes.c_uint32
     rc, dbl, ptr = ctypes.c_int, ctypes.c_double, ctypes.POINTER
     create = lambda cfg: (rc, [ptr(cfg), i64, rc, u64, i64, ptr(vp)])
     step = (rc, [vp] * 8 + [u32, vp])                  # h, act, obs, reward, terminated, truncated, final_obs, info / inner_steps
     policy_create = (rc, [vp, ptr(CPolicyDesc), vp, u32, vp, ptr(vp)])
+    policy_packed = {     # include/salp_vec_policy_packed.h, in header order (tests/test_capi_policy_packed.py compares it with that header)
+        "salp_vec_rollout_policy_packed": (rc, [vp, vp, i32, vp, vp, u32, vp]),
+        "salp_vec_rollout_policy_packed_sampled": (rc, [vp, vp, i32, vp, vp, vp, u32, vp]),
+    }
     rollout = {       # include/salp_robot_rollout.h, in header order (tests/test_capi_robot_rollout.py compares it with that header)
         "salp_robot_vec_rollout": (rc, [vp, vp, i32, vp, vp, vp, vp, vp, vp, u32, vp]),
         "salp_robot_policy_words": (rc, [vp, ptr(CPolicyDesc)]),
@@ -85,7 +89,7 @@ def _prototypes():
         "salp_robot_vec_evaluate_policy": (rc, [vp, vp, i32, vp, u32, vp]),
         "salp_robot_vec_evaluate_policy_sampled": (rc, [vp, vp, i32, vp, u32, vp]),
     }
-    return rollout, sampled, evaluate, {
+    return policy_packed, rollout, sampled, evaluate, {
         "salp_last_error": (ctypes.c_char_p, []),
         "salp_abi_version": (rc, []),
         "salp_device_count": (rc, []),
@@ -142,7 +146,7 @@ def _prototypes():
     }
 
 
-ROBOT_ROLLOUT_PROTOTYPES, ROBOT_SAMPLED_PROTOTYPES, ROBOT_EVALUATE_PROTOTYPES, PROTOTYPES = _prototypes()
+POLICY_PACKED_PROTOTYPES, ROBOT_ROLLOUT_PROTOTYPES, ROBOT_SAMPLED_PROTOTYPES, ROBOT_EVALUATE_PROTOTYPES, PROTOTYPES = _prototypes()
 ROBOT_EXPORTS = tuple(n for n in PROTOTYPES if n.startswith("salp_robot_"))
 EXPORTS = tuple(n for n in PROTOTYPES if n not in ROBOT_EXPORTS)
 
@@ -168,7 +172,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
             f"HIP library not found at {p}; build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(there is no CPU fallback)")
     L = ctypes.CDLL(p)
-    for name, (restype, argtypes) in {**PROTOTYPES, **ROBOT_ROLLOUT_PROTOTYPES, **ROBOT_SAMPLED_PROTOTYPES, **ROBOT_EVALUATE_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **POLICY_PACKED_PROTOTYPES, **ROBOT_ROLLOUT_PROTOTYPES, **ROBOT_SAMPLED_PROTOTYPES,
+                                      **ROBOT_EVALUATE_PROTOTYPES}.items():
         # the default library has every symbol (a missing one raises here); an explicit path may be an older A/B
         # variant (profiles/ab_bench.py) that lacks the newer ones
         if path is None or hasattr(L, name):
@@ -300,6 +305,17 @@ class SalpLib:
         self._call("salp_vec_rollout_policy_sampled", handle._p, int(horizon), obs, reward, term, trunc, act_out, logp_out,
                    flags, stream)
 
+    def rollout_policy_packed(self, handle: "PolicyHandle", horizon, rec, act_out, flags, stream=0):
+        """salp_vec_rollout_policy_packed (include/salp_vec_policy_packed.h): the closed loop of rollout_policy writing the
+        records of rollout_packed; rec float32 [horizon, n, width], act_out may be None; flags: SALP_DEVICE_PTRS and / or
+        REC_FINAL_OBS."""
+        self._call("salp_vec_rollout_policy_packed", handle._p, int(horizon), rec, act_out, flags, stream)
+
+    def rollout_policy_packed_sampled(self, handle: "PolicyHandle", horizon, rec, act_out, logp_out, flags, stream=0):
+        """salp_vec_rollout_policy_packed_sampled: the same with a Gaussian policy's sampled actions; act_out and logp_out
+        may be None."""
+        self._call("salp_vec_rollout_policy_packed_sampled", handle._p, int(horizon), rec, act_out, logp_out, flags, stream)
+
     def evaluate_policy_sampled(self, handle: "PolicyHandle", horizon, rec, flags, stream=0):
         """salp_vec_evaluate_policy_sampled: evaluate_policy under a Gaussian policy's sampled actions."""
         self._call("salp_vec_evaluate_policy_sampled", handle._p, int(horizon), rec, flags, stream)
@@ -325,7 +341,7 @@ class SalpLib:
     def last_launch(self) -> dict:
         """The kernel instantiation of the most recent step / rollout call (salp_vec_last_launch).  `full_signature`: 1 = the four
         main outputs only, 2 = the four plus final_obs / info, 3 = the packed record (step_packed / rollout_packed, every
-        instantiation), 4 = the per-env summary record and no per-step output (evaluate_policy),
+        instantiation; rollout_policy_packed with `actions_in_kernel` 2 or 3), 4 = the per-env summary record and no per-step output (evaluate_policy),
         5 = the navigation record (evaluate_navigation), 0 = every store tested (some main output absent, the generic instantiation, or a predicated launch
         asked for final_obs / info) — of the kernel that ran: the unpredicated launch's
         when there was one, else the predicated launch's.  `signature_unpredicated` / `signature_predicated`: each half's own,

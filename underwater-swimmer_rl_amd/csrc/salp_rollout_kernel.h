@@ -23,7 +23,7 @@
 // them their register counts; profiles/r10/refactor_notes.md lists what was tried.  Its sections are marked `// ----`.
 //
 // The template is instantiated implicitly, by the small salp_rollout_*.hip units next to this file: one per food-slot count
-// and literal / run-time constants for K = 3, one for the generic-K kernels, so that the 360 instantiations compile in
+// and literal / run-time constants for K = 3, one for the generic-K kernels, so that the 440 instantiations compile in
 // parallel.  Each unit defines the rollout_unit_fn of its handle class (the generic unit: of its two); salp_vec.hip (the
 // service kernels and the C ABI of include/salp_vec.h) reaches the kernels only through those.  No instantiation may be
 // named in two units.
@@ -836,6 +836,7 @@ RolloutPick pick_sig(int sig) {
       else return RolloutPick{nullptr, -1};
     }
     if (sig == kSigSummary) return picked<FMAX, KMAX, FORCED, STD, kSigSummary, RAGGED, ACT>();
+    if (sig == kSigPacked) return picked<FMAX, KMAX, FORCED, STD, kSigPacked, RAGGED, ACT>();
     return picked<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, ACT>();
   } else if constexpr (ACT != ACT_READ) return picked<FMAX, KMAX, FORCED, STD, kSigMain, RAGGED, ACT>();
   else {
@@ -849,9 +850,9 @@ RolloutPick pick_sig(int sig) {
 // `act`: where the actions come from (ACT_READ / ACT_GEN / ACT_POLICY / ACT_POLICY_SAMPLED)
 template <int FMAX, int KMAX, bool STD, bool RAGGED>
 RolloutPick pick_rollout(bool forced, int sig, int act) {
-  if ((sig == kSigMain || sig == kSigSummary) && act == ACT_POLICY_SAMPLED)   // the same two signatures, sampling
+  if ((sig == kSigMain || sig == kSigSummary || sig == kSigPacked) && act == ACT_POLICY_SAMPLED)   // the same signatures but the navigation, sampling
     return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, ACT_POLICY_SAMPLED>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, ACT_POLICY_SAMPLED>(sig);
-  if ((sig == kSigMain || sig == kSigSummary || sig == kSigNav) && act == ACT_POLICY)   // the in-kernel policy exists for the main-only output signature and for the summary
+  if ((sig == kSigMain || sig == kSigSummary || sig == kSigNav || sig == kSigPacked) && act == ACT_POLICY)   // the in-kernel policy exists for the main-only output signature, the packed record, the summary and the navigation record
     return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, ACT_POLICY>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, ACT_POLICY>(sig);
   if (sig == kSigMain && act == ACT_GEN)
     return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, ACT_GEN>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, ACT_GEN>(sig);

@@ -39,7 +39,8 @@ enum { ACT_READ = 0, ACT_GEN = 1, ACT_POLICY = 2, ACT_POLICY_SAMPLED = 3 };
 // store is tested, the step ends in a full drain (a 12-food rollout with final_obs ran 22 % slower in that form,
 // profiles/r03/ab_notes.md session 15).  The one-wavefront predicated launches exist as kSigMain and kSigPartial only.
 // kSigPacked = ONE stream of transition records (salp_vec_step_packed / salp_vec_rollout_packed): no per-lane reward / flag /
-// info stores at all; unpredicated and predicated, K = 3 and generic K; no in-kernel action generation.
+// info stores at all; unpredicated and predicated, K = 3 and generic K; no in-kernel action generation.  K = 3 also with the
+// in-kernel policy, deterministic and sampling (salp_vec_rollout_policy_packed, include/salp_vec_policy_packed.h).
 // kSigSummary = NO per-step output: one record of SALP_EVAL_WORDS words per env at the end of the launch
 // (salp_vec_evaluate_policy); exists for the in-kernel policy and K = 3 only, unpredicated and predicated.
 // kSigNav = the summary kernel's loop with a per-env stop at a goal and one navigation record of SALP_NAV_WORDS words per env
@@ -59,7 +60,7 @@ struct IOPtrs {
   float* final_obs;       // [H][n][obs_dim] rows of finished envs only
   union {
     int32_t* info;        // [H][n][3]
-    float* logp_out;      // ACT_POLICY_SAMPLED (whose signatures have no info): [H][n] or null
+    float* logp_out;      // ACT_POLICY_SAMPLED (whose signatures have no info stream — the packed record carries the counters): [H][n] or null
   };
   union {
     float* act_out;       // [H][n][act_dim]
@@ -125,7 +126,7 @@ struct RolloutTraits {
   // stepped: nothing of its state, statistics or record moves; a wavefront with no running lane leaves the step loop.
   static constexpr bool NAV = SIG == kSigNav;
   static constexpr bool SUMMARY = SIG == kSigSummary || NAV;     // everything the two share: no per-step output, no tile write
-  static_assert(!POLICY || ((SIG == 1 || SIG == 4 || SIG == 5) && KMAX == 3), "policy kernels: the main-only, the summary and the navigation signature, K = 3");
+  static_assert(!POLICY || ((SIG == 1 || SIG == 3 || SIG == 4 || SIG == 5) && KMAX == 3), "policy kernels: the main-only, the packed, the summary and the navigation signature, K = 3");
   static_assert(!SUMMARY || POLICY, "the summary signature exists for the in-kernel policy only");
   static_assert(!NAV || (FMAX == 1 && FORCED && ACT == ACT_POLICY), "the navigation signature: one food, forced breathing, the deterministic policy");
   // (the summary kernels the other way round — by value with 4 / 8 slots, the device copy with 16: with no store in the step loop
@@ -143,7 +144,10 @@ struct RolloutTraits {
   // TAILREG: the unpredicated 8-slot packed kernel stores that last float4 straight from registers (one 16-B store per
   // lane where the other signatures issue their reward / flag / info stores) and keeps the tile of the unpacked
   // signatures: 40960 B of LDS per workgroup is exactly four workgroups per CU, a seven-column tile (45056 B) is three.
-  static constexpr bool TAILREG = PACKED && !RAGGED && KMAX == 3 && FMAX == 8;
+  // Not with the in-kernel policy: its 8-slot kernels run one wavefront per SIMD (waves_per_simd below), one workgroup per CU,
+  // so LDS limits nothing there; they take the seven-column tile and the stash like every other slot count, and every store
+  // of the record stays a whole-line store.
+  static constexpr bool TAILREG = PACKED && !RAGGED && KMAX == 3 && FMAX == 8 && !POLICY;
   static constexpr int OBS = 12 + 4 * KMAX;        // floats of the widest observation row
   static constexpr int AD = FORCED ? 1 : 2;        // action components
   static constexpr int QMAX = 3 + KMAX;          // float4 per observation row
@@ -207,7 +211,13 @@ struct RolloutTraits {
     // that at 2 held 2-16 scratch instructions (12-36 B per lane) where the twin holds fewer or none — the 4-slot rollout kernels,
     // the free-breathing 4-slot summary kernel with literal constants, the free-breathing one-food summary kernel with run-time
     // constants: 1.  From the code-object metadata of all 80: profiles/r07/sampled_kernel_resources.txt.
-    if (SAMPLED && !RAGGED && FMAX == 4 && (SIG == 1 || !FORCED)) return 1;
+    // The packed policy kernels (sig 3, salp_vec_rollout_policy_packed) take the bounds of their main-only twins (sig 1), sampling
+    // or not: the record's last float4 waits in LDS, not in registers (profiles/r16/policy_packed_kernel_resources.txt).
+    if (SAMPLED && !RAGGED && FMAX == 4 && (SIG == 1 || SIG == 3 || !FORCED)) return 1;
+    // Two more packed kernels go to 1, by the same rule (scratch at 2 where the twin holds less): the unpredicated one-food
+    // sampling kernel with run-time constants (12 B, its twin none) and the unpredicated free-breathing 4-slot kernel (20 B, its twin 12).
+    if (SIG == 3 && SAMPLED && !RAGGED && FMAX == 1 && !STD) return 1;
+    if (SIG == 3 && POLICY && !SAMPLED && !RAGGED && FMAX == 4 && !FORCED) return 1;
     if (SAMPLED && !RAGGED && FMAX == 1 && SIG == 4 && !STD && !FORCED) return 1;
     // The summary kernels (sig 4) take their twins' bounds, but for the unpredicated 4-slot kernel with run-time constants: 1 (at 2
     // it sat at 255-256 VGPRs with 12-132 B of scratch, its twin holds 0-12 B; at 1 258-272 registers, 2-16 of them AGPRs, none).

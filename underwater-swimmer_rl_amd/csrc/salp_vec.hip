@@ -12,6 +12,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "../../include/salp_vec_policy_packed.h"
 #include "salp_host.h"
 #include "salp_policy_object.h"
 #include "salp_rollout_kernel.h"
@@ -127,8 +128,8 @@ int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, Rollout
   const bool extras = !policy && (io.final_obs || io.info);
   const int sig = kind.out == kOutNav ? kSigNav : kind.out == kOutSummary ? kSigSummary : kind.out == kOutPacked ? kSigPacked
                 : (!main_outputs ? kSigPartial : (extras ? kSigExtras : kSigMain));
-  if (policy && sig != kSigMain && sig != kSigSummary && sig != kSigNav)
-    return fail(SALP_ERR_INVALID, "policy kernels exist for the main-only, the summary and the navigation signature");
+  if (policy && sig != kSigMain && sig != kSigPacked && sig != kSigSummary && sig != kSigNav)
+    return fail(SALP_ERR_INVALID, "policy kernels exist for the main-only, the packed, the summary and the navigation signature");
   const int gen = policy ? kind.act : (io.act == nullptr ? ACT_GEN : ACT_READ);
   // envs in full wavefronts: unpredicated kernel
   int64_t n_full = h->n / kWave * kWave;
@@ -574,6 +575,44 @@ int salp_vec_rollout_policy_sampled(salp_vec_t* h, const salp_policy_t* pol, int
                                     uint8_t* terminated, uint8_t* truncated, float* act_out, float* logp_out,
                                     uint32_t flags, void* stream) {
   return rollout_policy_impl(h, pol, H, obs, reward, terminated, truncated, act_out, logp_out, flags, stream, true);
+}
+
+// salp_vec_rollout_policy_packed (and _sampled; include/salp_vec_policy_packed.h): the kSigPacked kernels with the in-kernel
+// policy — the checks of the policy calls, then those of the packed calls; everything before anything is launched.
+static int rollout_policy_packed_impl(salp_vec_t* h, const salp_policy_t* pol, int32_t H, float* rec, float* act_out, float* logp_out,
+                                      uint32_t flags, void* stream, bool sampled) {
+  int rc = check_policy_call(h, pol, sampled);
+  if (rc != SALP_OK) return rc;
+  if (!rec) return fail(SALP_ERR_INVALID, "rec is NULL");
+  if (H <= 0) return fail(SALP_ERR_INVALID, "horizon must be >= 1");
+  rc = check_record_args(flags, SALP_DEVICE_PTRS | SALP_REC_FINAL_OBS,
+                         "unknown flag bits (SALP_DEVICE_PTRS and SALP_REC_FINAL_OBS are defined)", rec,
+                         "rec must be 16-byte aligned (the records are written as float4)");
+  if (rc != SALP_OK) return rc;
+  CallFrame f;
+  if ((rc = f.enter(h, stream)) != SALP_OK) return rc;
+  const bool with_final = (flags & SALP_REC_FINAL_OBS) != 0;
+  IOPtrs io = io_for(h);
+  set_policy_block(io, pol->block);
+  const size_t HN = (size_t)H * (size_t)h->n;
+  HostStream s[] = {stream_out(rec, HN * (size_t)salp_vec_record_width(h, flags), with_final),   // in: the tails of unfinished rows stay as they are
+                    stream_out(act_out, HN * h->act_dim), stream_out(sampled ? logp_out : nullptr, HN)};
+  return staged(h->stage, f.st, flags & SALP_DEVICE_PTRS, s, [&] {
+    set_record_block(io, s[0].as<float>(), with_final);
+    io.act_out = s[1].as<float>();
+    if (sampled) io.logp_out = s[2].as<float>();     // (the info slot: the record carries the counters)
+    return run_rollout(h, io, H, f.st, {kOutPacked, sampled ? ACT_POLICY_SAMPLED : ACT_POLICY}, pol);
+  });
+}
+
+int salp_vec_rollout_policy_packed(salp_vec_t* h, const salp_policy_t* pol, int32_t horizon, float* rec, float* act_out,
+                                   uint32_t flags, void* stream) {
+  return rollout_policy_packed_impl(h, pol, horizon, rec, act_out, nullptr, flags, stream, false);
+}
+
+int salp_vec_rollout_policy_packed_sampled(salp_vec_t* h, const salp_policy_t* pol, int32_t horizon, float* rec, float* act_out,
+                                           float* logp_out, uint32_t flags, void* stream) {
+  return rollout_policy_packed_impl(h, pol, horizon, rec, act_out, logp_out, flags, stream, true);
 }
 
 // salp_vec_evaluate_policy (and _sampled): the kSigSummary kernels.  Everything is checked before anything is launched.

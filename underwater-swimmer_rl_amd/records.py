@@ -57,6 +57,41 @@ def unpack_record(rec, obs_dim: int) -> dict:
     }
 
 
+def transitions(first_obs, record, actions, obs_dim: int):
+    """The replay tuples of a closed-loop block (`SalpVectorEnv.rollout_policy_packed`, records with the terminal tail):
+    `(obs, actions, reward, next_obs, terminated)` over all H x N rows, flattened to [H * N, ...] in step order.
+      obs       the row each action saw: `first_obs` [N, obs_dim] (the observation before the call), then the record's obs
+                of step t - 1 — one new [H, N, obs_dim] block;
+      next_obs  the terminal tail where the row is finished (terminated | truncated), else the record's obs (after the
+                same-step autoreset the record's obs of a finished row is the next episode's first row).  The tails of
+                unfinished rows — never written by the kernels — are selected around, not multiplied: nothing of them,
+                a NaN included, reaches the result;
+      actions, reward, terminated   views of `actions` and of the block (no copy).
+    numpy arrays and torch tensors (CPU or GPU) alike, like `unpack_record`."""
+    D = int(obs_dim)
+    f = unpack_record(record, D)
+    if f["final_observation"] is None:
+        raise ValueError("transitions needs records with the terminal observation (want_final_observation=True)")
+    if record.ndim != 3:
+        raise ValueError(f"a record block is [H, N, width]; got {tuple(record.shape)}")
+    H, N = int(record.shape[0]), int(record.shape[1])
+    if tuple(first_obs.shape) != (N, D) or tuple(actions.shape[:2]) != (H, N):
+        raise ValueError(f"first_obs {tuple(first_obs.shape)} / actions {tuple(actions.shape)} do not fit a block of {H} x {N} rows of obs_dim {D}")
+    if isinstance(record, np.ndarray):
+        seen = np.empty((H, N, D), np.float32)
+        done = np.logical_or(f["terminated"], f["truncated"])
+        next_obs = np.where(done[..., None], f["final_observation"], f["obs"])
+    else:
+        import torch
+        seen = torch.empty((H, N, D), dtype=torch.float32, device=record.device)
+        done = torch.logical_or(f["terminated"], f["truncated"])
+        next_obs = torch.where(done[..., None], f["final_observation"], f["obs"])
+    seen[0] = first_obs
+    seen[1:] = f["obs"][:-1]
+    flat = lambda t: t.reshape((H * N,) + tuple(t.shape[2:]))
+    return flat(seen), flat(actions), f["reward"].reshape(H * N), flat(next_obs), f["terminated"].reshape(H * N)
+
+
 def pack_record(obs, reward, terminated, truncated, info, final_obs=None) -> np.ndarray:
     """The layout in numpy: obs [..., D], reward / terminated / truncated [...], info [..., 3] int (food_collected,
     steps_since_food, collision: the SALP_INFO_* columns), final_obs [..., D] or None -> float32 [..., width].  The whole

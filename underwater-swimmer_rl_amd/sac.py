@@ -421,7 +421,7 @@ IN_KERNEL_HIDDEN_MAX = 64      # widest hidden layer of an actor that runs insid
 
 
 @torch.no_grad()
-def collect_in_kernel(env, agent: SAC, buffer: DeviceReplayBuffer, horizon: int, handle=None):
+def collect_in_kernel(env, agent: SAC, buffer: DeviceReplayBuffer, horizon: int, handle=None, keep_truncated: bool = False):
     """`horizon` vector steps of experience in ONE launch: the agent's actor is packed as a `policy.GaussianPolicy`, the
     rollout kernel samples its tanh-Gaussian actions itself (`env.rollout_policy(..., sample=True)`), and the H x N
     transitions go to `buffer` in step order: `obs` = the row each action saw (the current observation, then obs[t - 1]),
@@ -429,8 +429,10 @@ def collect_in_kernel(env, agent: SAC, buffer: DeviceReplayBuffer, horizon: int,
     observation, and after the same-step autoreset obs[t] is the next episode's first row; terminated ones are kept (the
     target ignores their next_obs).  A robot env (`SalpRobotVectorEnv`) returns `final_observation` from its rollout: there
     `next_obs` is the terminal row wherever an episode ended (terminated or truncated) and obs[t] elsewhere, and all H x N
-    transitions are stored, as `train_sac` stores them.  Returns the policy handle: pass it back as `handle` and the next
-    call only uploads the actor's new weights (`handle.update`)."""
+    transitions are stored, as `train_sac` stores them.  `keep_truncated=True` does the same on a snake env: the launch is
+    `env.rollout_policy_packed(..., sample=True, want_final_observation=True)`, whose records carry the terminal rows, and all
+    H x N transitions are stored through `records.transitions` (on a robot env the flag changes nothing).  Returns the
+    policy handle: pass it back as `handle` and the next call only uploads the actor's new weights (`handle.update`)."""
     from .policy import GaussianPolicy
     wide = [h for h in agent.cfg.hidden_sizes if h > IN_KERNEL_HIDDEN_MAX]
     if wide or len(agent.cfg.hidden_sizes) > 2:
@@ -443,6 +445,11 @@ def collect_in_kernel(env, agent: SAC, buffer: DeviceReplayBuffer, horizon: int,
         handle.update(pol.pack(), 0, env._stream)
     H, n = int(horizon), env.num_envs
     first = env.observe().clone()
+    if keep_truncated and hasattr(env, "rollout_policy_packed"):
+        from .records import transitions
+        out = env.rollout_policy_packed(handle, H, want_final_observation=True, sample=True)
+        buffer.add(*transitions(first, out["record"], out["actions"], env.obs_dim))
+        return handle
     out = env.rollout_policy(handle, H, sample=True)
     seen = torch.cat([first[None], out["obs"][:-1]])
     if "final_observation" in out:     # the robot rollout keeps terminal rows: nothing is left out

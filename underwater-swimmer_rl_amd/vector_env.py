@@ -283,6 +283,33 @@ class SalpVectorEnv(ArrayBackend, PolicyCache):
         self._lib.rollout_policy(policy, H, obs, rew, term, trunc, aout, self._flags, self._stream)
         return dict(obs=obs, reward=rew, terminated=term, truncated=trunc, final_obs=None, actions=aout)
 
+    def rollout_policy_packed(self, policy, horizon: int, want_final_observation: bool = True, want_actions: bool = True,
+                              sample: bool = False, out=None) -> dict:
+        """The closed loop of `rollout_policy` with the packed records of `rollout_packed` as its output
+        (salp_vec_rollout_policy_packed): dict(record=[H, N, width], actions=[H, N, act_dim] or None) and, with
+        `sample=True` (a `GaussianPolicy`), `logp` [H, N].  The record keeps what `rollout_policy` cannot return: the info
+        counters, the collision byte and — with `want_final_observation` — the terminal observation of every finished row
+        (`records.unpack_record` gives the views, `records.transitions` the replay tuples over all H x N rows).  `out`: a
+        float32 [H, N, width] block to write into (its width must match `want_final_observation`); default an env-owned
+        buffer."""
+        policy = self._policy_handle(policy)
+        H, n = int(horizon), self.num_envs
+        if H < 1:
+            raise ValueError("horizon must be >= 1")
+        with_final = bool(want_final_observation)
+        shape = (H, n, self._lib.record_width(with_final))
+        rec = out if out is not None else self._buf("r_rec_final" if with_final else "r_rec", shape, np.float32)
+        if tuple(rec.shape) != shape:
+            raise ValueError(f"out has shape {tuple(rec.shape)}; expected {shape}")
+        aout = self._buf("r_actions", (H, n, self.act_dim), np.float32) if want_actions else None
+        flags = self._flags | (_capi.REC_FINAL_OBS if with_final else 0)
+        if sample:
+            logp = self._buf("r_logp", (H, n), np.float32)
+            self._lib.rollout_policy_packed_sampled(policy, H, rec, aout, logp, flags, self._stream)
+            return dict(record=rec, actions=aout, logp=logp)
+        self._lib.rollout_policy_packed(policy, H, rec, aout, flags, self._stream)
+        return dict(record=rec, actions=aout)
+
     def evaluate_policy(self, policy, horizon: int, out=None, accumulate: bool = False, sample: bool = False) -> dict:
         """`horizon` closed-loop steps of `rollout_policy` in one kernel launch with NO per-step output: one summary record
         per env (32 B) instead of [H, N] observations, rewards and flags.  Returns typed views of one int32 [N, 8] block
