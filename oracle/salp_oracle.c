@@ -72,6 +72,8 @@ typedef struct {
   int shape_hold;
   int episode_length;
   double episode_return;
+  /* food placement counters (salp_oracle.h SALP_ORACLE_PC_*): bookkeeping only, no output depends on them */
+  int64_t placed[SALP_ORACLE_PC_COUNT];
 } env_t;
 
 struct salp_oracle {
@@ -81,6 +83,7 @@ struct salp_oracle {
   int64_t base;
   int64_t global_step;
   int base_num_food;                 /* snake:36 base_num_food_items: foods of the NEXT episodes (<= cfg.num_food_items slots) */
+  int reset_limit, respawn_limit;    /* snake:99 `attempts < 100`, snake:239 `attempts < 50`; salp_oracle_set_placement_limits */
   env_t* env;
 };
 
@@ -112,6 +115,13 @@ static void draw_xy(const struct salp_oracle* h, int64_t i, env_t* e, double* x,
   *y = ylo + (yhi - ylo) * u53(w[2], w[3]);
 }
 
+/* a food was placed after `rejections` rejected draws: by a valid draw, or (forced) by the unconditional one */
+static void count_placement(env_t* e, int respawn, int forced, int rejections) {
+  e->placed[respawn ? SALP_ORACLE_PC_RESPAWN_PLACED : SALP_ORACLE_PC_RESET_PLACED] += 1;
+  if (forced) e->placed[respawn ? SALP_ORACLE_PC_RESPAWN_FORCED : SALP_ORACLE_PC_RESET_FORCED] += 1;
+  else if (rejections > e->placed[SALP_ORACLE_PC_MAX_VALID_REJECTIONS]) e->placed[SALP_ORACLE_PC_MAX_VALID_REJECTIONS] = rejections;
+}
+
 /* snake:92-131 _generate_food_positions */
 static void generate_food(const struct salp_oracle* h, int64_t i, env_t* e) {
   const salp_config_t* c = &h->cfg;
@@ -119,7 +129,7 @@ static void generate_food(const struct salp_oracle* h, int64_t i, env_t* e) {
   for (int k = 0; k < SALP_MAX_FOOD; ++k) e->food[k][0] = e->food[k][1] = NAN;
   for (int f = 0; f < e->num_food; ++f) {
     int attempts = 0;
-    while (attempts < 100) {
+    while (attempts < h->reset_limit) {
       double x, y;
       draw_xy(h, i, e, &x, &y);
       int valid = 1;
@@ -129,13 +139,14 @@ static void generate_food(const struct salp_oracle* h, int64_t i, env_t* e) {
       }
       double rd = sqrt(pow(x - (double)c->width / 2, 2.0) + pow(y - (double)c->height / 2, 2.0));
       if (rd < c->min_food_distance) valid = 0;
-      if (valid) { e->food[count][0] = x; e->food[count][1] = y; ++count; break; }
+      if (valid) { e->food[count][0] = x; e->food[count][1] = y; ++count; count_placement(e, 0, 0, attempts); break; }
       ++attempts;
     }
-    if (attempts >= 100) {
+    if (attempts >= h->reset_limit) {
       double x, y;
       draw_xy(h, i, e, &x, &y);
       e->food[count][0] = x; e->food[count][1] = y; ++count;
+      count_placement(e, 0, 1, attempts);
     }
   }
 }
@@ -256,7 +267,7 @@ static void apply_jet_thrust(const struct salp_oracle* h, int64_t i, env_t* e) {
 static void respawn_food(const struct salp_oracle* h, int64_t i, env_t* e) {
   const salp_config_t* c = &h->cfg;
   int attempts = 0;
-  while (attempts < 50) {
+  while (attempts < h->respawn_limit) {
     double x, y;
     draw_xy(h, i, e, &x, &y);
     double rd = sqrt(pow(x - e->x, 2.0) + pow(y - e->y, 2.0));
@@ -269,14 +280,14 @@ static void respawn_food(const struct salp_oracle* h, int64_t i, env_t* e) {
     }
     if (valid) {
       for (int k = 0; k < e->num_food; ++k)
-        if (is_none(e->food[k])) { e->food[k][0] = x; e->food[k][1] = y; return; }
+        if (is_none(e->food[k])) { e->food[k][0] = x; e->food[k][1] = y; count_placement(e, 1, 0, attempts); return; }
     }
     ++attempts;
   }
   double x, y;
   draw_xy(h, i, e, &x, &y);
   for (int k = 0; k < e->num_food; ++k)
-    if (is_none(e->food[k])) { e->food[k][0] = x; e->food[k][1] = y; return; }
+    if (is_none(e->food[k])) { e->food[k][0] = x; e->food[k][1] = y; count_placement(e, 1, 1, attempts); return; }
 }
 
 /* snake:157-202 step over legacy:119-156 step. Returns reward; sets flags. */
@@ -447,6 +458,7 @@ int salp_oracle_create(const salp_config_t* cfg, int64_t n, uint64_t seed, int64
   if (!h) return -4;
   h->cfg = *cfg; h->n = n; h->seed = seed; h->base = base; h->global_step = 0;
   h->base_num_food = cfg->num_food_items;
+  h->reset_limit = 100; h->respawn_limit = 50;
   h->env = (env_t*)calloc((size_t)n, sizeof(env_t));
   if (!h->env) { free(h); return -4; }
   for (int64_t i = 0; i < n; ++i) { h->env[i].rng_counter = 0; reset_env(h, i, &h->env[i]); }
@@ -622,6 +634,30 @@ int64_t salp_oracle_global_step(const salp_oracle_t* h) { return h->global_step;
 int salp_oracle_set_base_num_food(salp_oracle_t* h, int k) {
   if (!h || k < 0 || k > h->cfg.num_food_items) return -1;
   h->base_num_food = k;
+  return 0;
+}
+
+/* Food placement counters [SALP_ORACLE_PC_COUNT][n], kept per env since creation or the last clear: the foods placed at
+   reset (create, salp_oracle_reset with or without a mask, autoreset) and at respawn, how many of each by the unconditional
+   draw behind `limit` rejections (snake:120-131, :270-276), and the longest run of rejections a VALID draw ended. */
+int salp_oracle_get_placement_counters(const salp_oracle_t* h, int64_t* out) {
+  if (!h || !out) return -1;
+  for (int64_t i = 0; i < h->n; ++i)
+    for (int k = 0; k < SALP_ORACLE_PC_COUNT; ++k) out[(int64_t)k * h->n + i] = h->env[i].placed[k];
+  return 0;
+}
+
+int salp_oracle_clear_placement_counters(salp_oracle_t* h) {
+  if (!h) return -1;
+  for (int64_t i = 0; i < h->n; ++i) memset(h->env[i].placed, 0, sizeof(h->env[i].placed));
+  return 0;
+}
+
+/* The rejection limits of later resets and respawns; the reference's are 100 and 50 (the defaults).  For the guard of
+   the placement tests alone, which shows that a limit one off changes foods and draw counters. */
+int salp_oracle_set_placement_limits(salp_oracle_t* h, int reset_limit, int respawn_limit) {
+  if (!h || reset_limit < 0 || respawn_limit < 0) return -1;
+  h->reset_limit = reset_limit; h->respawn_limit = respawn_limit;
   return 0;
 }
 

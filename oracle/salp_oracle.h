@@ -37,6 +37,19 @@ int salp_oracle_get_state(salp_oracle_t* h, double* f64, int32_t* i32);
 int salp_oracle_set_state(salp_oracle_t* h, const double* f64, const int32_t* i32);
 int64_t salp_oracle_global_step(const salp_oracle_t* h);
 int salp_oracle_set_base_num_food(salp_oracle_t* h, int k);   /* snake:36 base_num_food_items, 0..num_food_items */
+/* Food placement counters, per env since creation or the last clear; they change no output.  out: int64 [SALP_ORACLE_PC_COUNT][n]. */
+enum {
+  SALP_ORACLE_PC_RESET_PLACED = 0,         /* foods placed at reset (create, reset with or without a mask, autoreset) */
+  SALP_ORACLE_PC_RESET_FORCED = 1,         /* ... of them by the unconditional draw behind `reset_limit` rejections */
+  SALP_ORACLE_PC_RESPAWN_PLACED = 2,       /* foods placed at respawn */
+  SALP_ORACLE_PC_RESPAWN_FORCED = 3,       /* ... of them by the unconditional draw behind `respawn_limit` rejections */
+  SALP_ORACLE_PC_MAX_VALID_REJECTIONS = 4, /* the most rejections that preceded a VALID acceptance */
+  SALP_ORACLE_PC_COUNT = 5
+};
+int salp_oracle_get_placement_counters(const salp_oracle_t* h, int64_t* out);
+int salp_oracle_clear_placement_counters(salp_oracle_t* h);
+/* The rejection limits (snake:99 and :239; defaults 100 and 50) of LATER resets and respawns: test guard only. */
+int salp_oracle_set_placement_limits(salp_oracle_t* h, int reset_limit, int respawn_limit);
 /* The in-kernel policy (include/salp_vec.h "Policy") in the header's own arithmetic, from the public weight layout of
  * ONE policy: obs [M][obs_dim] -> u [M][act_dim] (nullable; before the output activation) and a [M][act_dim].
  * subnormals (nullable): the number of non-zero subnormal values formed on the way.  See salp_oracle.c. */

@@ -16,6 +16,9 @@ from underwater_swimmer_rl_amd._capi import (  # noqa: F401  (the snapshot rows 
     I_PHASE, I_TIMER, I_EXHALE_DUR, I_SHAPE_HOLD, I_STEPS_SINCE_FOOD, I_FOOD_COLLECTED, I_RNG_COUNTER, I_EPISODE_LENGTH, I_COUNT,
     INFO_COLS)
 
+# rows of OracleVec.placement_counters() (oracle/salp_oracle.h SALP_ORACLE_PC_*)
+PC_RESET_PLACED, PC_RESET_FORCED, PC_RESPAWN_PLACED, PC_RESPAWN_FORCED, PC_MAX_VALID_REJECTIONS, PC_COUNT = range(6)
+
 _SO = os.path.join(native_lib.ORACLE_DIR, "libsalp_oracle.so")
 
 
@@ -37,6 +40,9 @@ PROTOTYPES = {
     "salp_oracle_set_state": (cint, [vp, vp, vp]),
     "salp_oracle_global_step": (i64, [vp]),
     "salp_oracle_set_base_num_food": (cint, [vp, cint]),
+    "salp_oracle_get_placement_counters": (cint, [vp, vp]),
+    "salp_oracle_clear_placement_counters": (cint, [vp]),
+    "salp_oracle_set_placement_limits": (cint, [vp, cint, cint]),
     "salp_oracle_policy_forward": (cint, [vp, i32, i32, vp, vp, i64, vp, vp, vp]),
     "salp_oracle_policy_forward_gaussian": (cint, [vp, i32, i32, vp, vp, i64, vp, vp, vp]),
 }
@@ -133,6 +139,22 @@ class OracleVec:
     def set_base_num_food(self, k):
         if lib().salp_oracle_set_base_num_food(self._h, int(k)) != 0:
             raise ValueError(f"base_num_food_items {k} out of range")
+
+    def placement_counters(self):
+        """int64 [PC_COUNT, n] (oracle/salp_oracle.h SALP_ORACLE_PC_*): foods placed at reset and at respawn, how many of
+        each by the forced draw, the most rejections before a valid acceptance; per env since creation or the last clear."""
+        out = np.empty((PC_COUNT, self.n), np.int64)
+        if lib().salp_oracle_get_placement_counters(self._h, _p(out)) != 0:
+            raise RuntimeError("salp_oracle_get_placement_counters failed")
+        return out
+
+    def clear_placement_counters(self):
+        lib().salp_oracle_clear_placement_counters(self._h)
+
+    def set_placement_limits(self, reset_limit=100, respawn_limit=50):
+        """The rejection limits of later resets and respawns (the reference's: 100 and 50).  Guard tests only."""
+        if lib().salp_oracle_set_placement_limits(self._h, int(reset_limit), int(respawn_limit)) != 0:
+            raise ValueError(f"placement limits ({reset_limit}, {respawn_limit}) out of range")
 
     def close(self):
         if self._h:
