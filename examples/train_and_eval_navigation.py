@@ -16,7 +16,10 @@ The scripted pursuit baseline: 99 of 100, 1817 +/- 216, 1.175, 0.860.  The refer
 this update-to-data ratio; that is the only reason for the flags above.)
 Those figures were taken with `run_navigation_trials` (one kernel launch per env-step).  The evaluations now run the whole
 trial loop in one launch (`run_navigation_trials_in_kernel`, salp_vec_evaluate_navigation) whenever the actor fits
-`MLPPolicy.from_actor` (up to two hidden layers of 16-64 units), and fall back to the stepwise runner otherwise."""
+`MLPPolicy.from_actor` (up to two hidden layers of 16-64 units), and fall back to the stepwise runner otherwise.
+`--wide-eval` scores a wider actor — the default 256 x 256 among them — in one launch as well, through the wide in-kernel
+policy (`MLPPolicy.from_actor(actor, wide=True)`, include/salp_vec_policy_wide.h), and scores the kept checkpoint with the
+stepwise runner too, so that the two success counts stand next to each other."""
 import argparse
 import json
 import os
@@ -42,6 +45,8 @@ def main():
     ap.add_argument("--auto-alpha", action="store_true", help="learn the entropy coefficient (SB3's default) instead of the YAML's fixed alpha")
     ap.add_argument("--lr", type=float, default=None)
     ap.add_argument("--reward-scale", type=float, default=1.0, help="the learner sees reward * scale (the env's reward is unchanged)")
+    ap.add_argument("--wide-eval", action="store_true",
+                    help="score actors wider than 64 units (multiples of 32 up to 256) in one launch with the wide in-kernel policy")
     args = ap.parse_args()
     dev = "cuda:0"
     env = salp.SalpVectorEnv(args.preset, num_envs=args.envs, device=dev, seed=0)
@@ -57,10 +62,12 @@ def main():
 
     def in_kernel_policy():
         """The actor's deterministic action as an in-kernel policy, or None when its shape does not fit one."""
-        try:
-            return salp.MLPPolicy.from_actor(agent.actor)
-        except (ValueError, AttributeError):
-            return None
+        for wide in ((False, True) if args.wide_eval else (False,)):
+            try:
+                return salp.MLPPolicy.from_actor(agent.actor, wide=wide)
+            except (ValueError, AttributeError):
+                pass
+        return None
 
     def evaluate(tag, heading_seed=0):
         # the whole trial loop in one kernel launch when the actor fits the in-kernel policy, else one launch per step
@@ -97,7 +104,11 @@ def main():
             best_sd = {k: (v.clone() if torch.is_tensor(v) else {kk: vv.clone() for kk, vv in v.items()}) for k, v in agent.state_dict().items()}
     if best_sd is not None:               # score the kept checkpoint on 100 trials with OTHER initial headings
         agent.load_state_dict(best_sd)
-        evaluate("best checkpoint, fresh headings", heading_seed=7)
+        m = evaluate("best checkpoint, fresh headings", heading_seed=7)
+        if args.wide_eval:                # the same checkpoint and headings under the stepped protocol
+            stepped = summarize(run_navigation_trials(lambda o: agent.act(o, deterministic=True), num_trials=100, device=dev, seed=123, heading_seed=7))
+            print(json.dumps({"eval": "best checkpoint, fresh headings, one launch per step", "success_rate": round(float(stepped["success_rate"]), 4),
+                              "same_success_count_as_one_launch": bool(round(100 * stepped["success_rate"]) == round(100 * m["success_rate"]))}), flush=True)
     env.close()
 
 

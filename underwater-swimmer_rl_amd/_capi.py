@@ -70,6 +70,12 @@ def _prototypes():
         "salp_vec_rollout_policy_packed": (rc, [vp, vp, i32, vp, vp, u32, vp]),
         "salp_vec_rollout_policy_packed_sampled": (rc, [vp, vp, i32, vp, vp, vp, u32, vp]),
     }
+    policy_wide = {       # include/salp_vec_policy_wide.h, in header order (tests/test_wide_policy_host.py compares it with that header)
+        "salp_policy_words_wide": (rc, [vp, ptr(CPolicyDesc), rc]),
+        "salp_policy_create_wide": policy_create,
+        "salp_policy_create_gaussian_wide": policy_create,
+        "salp_vec_last_launch_policy_wide": (rc, [vp]),
+    }
     rollout = {       # include/salp_robot_rollout.h, in header order (tests/test_capi_robot_rollout.py compares it with that header)
         "salp_robot_vec_rollout": (rc, [vp, vp, i32, vp, vp, vp, vp, vp, vp, u32, vp]),
         "salp_robot_policy_words": (rc, [vp, ptr(CPolicyDesc)]),
@@ -89,7 +95,7 @@ def _prototypes():
         "salp_robot_vec_evaluate_policy": (rc, [vp, vp, i32, vp, u32, vp]),
         "salp_robot_vec_evaluate_policy_sampled": (rc, [vp, vp, i32, vp, u32, vp]),
     }
-    return policy_packed, rollout, sampled, evaluate, {
+    return policy_packed, policy_wide, rollout, sampled, evaluate, {
         "salp_last_error": (ctypes.c_char_p, []),
         "salp_abi_version": (rc, []),
         "salp_device_count": (rc, []),
@@ -146,7 +152,7 @@ def _prototypes():
     }
 
 
-POLICY_PACKED_PROTOTYPES, ROBOT_ROLLOUT_PROTOTYPES, ROBOT_SAMPLED_PROTOTYPES, ROBOT_EVALUATE_PROTOTYPES, PROTOTYPES = _prototypes()
+POLICY_PACKED_PROTOTYPES, POLICY_WIDE_PROTOTYPES, ROBOT_ROLLOUT_PROTOTYPES, ROBOT_SAMPLED_PROTOTYPES, ROBOT_EVALUATE_PROTOTYPES, PROTOTYPES = _prototypes()
 ROBOT_EXPORTS = tuple(n for n in PROTOTYPES if n.startswith("salp_robot_"))
 EXPORTS = tuple(n for n in PROTOTYPES if n not in ROBOT_EXPORTS)
 
@@ -172,7 +178,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
             f"HIP library not found at {p}; build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(there is no CPU fallback)")
     L = ctypes.CDLL(p)
-    for name, (restype, argtypes) in {**PROTOTYPES, **POLICY_PACKED_PROTOTYPES, **ROBOT_ROLLOUT_PROTOTYPES, **ROBOT_SAMPLED_PROTOTYPES,
+    for name, (restype, argtypes) in {**PROTOTYPES, **POLICY_PACKED_PROTOTYPES, **POLICY_WIDE_PROTOTYPES, **ROBOT_ROLLOUT_PROTOTYPES, **ROBOT_SAMPLED_PROTOTYPES,
                                       **ROBOT_EVALUATE_PROTOTYPES}.items():
         # the default library has every symbol (a missing one raises here); an explicit path may be an older A/B
         # variant (profiles/ab_bench.py) that lacks the newer ones
@@ -264,8 +270,13 @@ class SalpLib:
 
     def policy_words(self, policy) -> int:
         """salp_policy_words: float32 words of one policy of this shape on this handle (raises for a shape out of range)."""
-        name = "salp_policy_words_gaussian" if getattr(policy, "gaussian", False) else "salp_policy_words"
-        rc = getattr(self.lib, name)(self._h, ctypes.byref(policy.desc()))
+        gauss = bool(getattr(policy, "gaussian", False))
+        if getattr(policy, "wide", False):
+            name = "salp_policy_words_wide"
+            rc = self.lib.salp_policy_words_wide(self._h, ctypes.byref(policy.desc()), int(gauss))
+        else:
+            name = "salp_policy_words_gaussian" if gauss else "salp_policy_words"
+            rc = getattr(self.lib, name)(self._h, ctypes.byref(policy.desc()))
         if rc < 0:
             check(self.lib, rc, name)
         return int(rc)
@@ -273,10 +284,11 @@ class SalpLib:
     def policy_create(self, policy, weights=None, flags=0, stream=0) -> "PolicyHandle":
         """salp_policy_create for an `MLPPolicy` (shape and, unless `weights` is given, its packed float32 weights; `weights`
         with SALP_DEVICE_PTRS: a device block in the public layout [P, words]); salp_policy_create_gaussian for a
-        `GaussianPolicy`."""
+        `GaussianPolicy`; the _wide entry points (include/salp_vec_policy_wide.h) for a policy made with `wide=True`."""
         h = ctypes.c_void_p()
         gauss = bool(getattr(policy, "gaussian", False))
-        self._call("salp_policy_create_gaussian" if gauss else "salp_policy_create", ctypes.byref(policy.desc()),
+        name = ("salp_policy_create_gaussian" if gauss else "salp_policy_create") + ("_wide" if getattr(policy, "wide", False) else "")
+        self._call(name, ctypes.byref(policy.desc()),
                    policy.pack() if weights is None else weights, flags, stream, ctypes.byref(h))
         ph = PolicyHandle(self, h, policy.n_policies, int(policy.words), gauss)
         self._policies.append(ph)
@@ -352,6 +364,10 @@ class SalpLib:
         keys = ("food_slots", "observed_capacity", "literal_constants", "forced", "full_signature", "actions_in_kernel",
                 "envs_unpredicated", "envs_predicated", "signature_unpredicated", "signature_predicated")
         return dict(zip(keys, (int(v) for v in (*a, *b))))
+
+    def last_launch_policy_wide(self) -> int:
+        """salp_vec_last_launch_policy_wide: 1 when the most recent launch ran the wide policy kernels, else 0."""
+        return int(self.lib.salp_vec_last_launch_policy_wide(self._h))
 
     def last_kernel_resources(self) -> dict:
         """Registers, LDS, scratch and resident workgroups per CU of the most recent call's kernel (salp_vec_last_kernel_resources)."""

@@ -15,6 +15,7 @@
 
 #include "salp_host.h"
 #include "salp_policy.h"
+#include "salp_policy_wide.h"
 #include "salp_policy_upload.h"
 
 namespace {
@@ -24,6 +25,7 @@ struct PolicyDims {
   int obs_dim, act_dim, kmax;
   int64_t n;                 // the handle's env count (fixes env -> policy)
   int device;
+  int food_slots;            // the snake handle's kernel class (1: the one-food kernels); the wide scheme asks for it
 };
 
 // The fields of both policy structs; each adds the back-pointer to its handle (`h`).
@@ -37,21 +39,23 @@ struct PolicyObject {
   float* pub;                // device: staging of the public layout [P][words] (host-pointer create / update)
   int32_t* map;              // device: word k of a policy in the block <- public word map[k] (-1: zero)
   int gaussian;              // *_policy_create_gaussian: a log-std head behind the mean head, a noise step in the header
+  int wide;                  // salp_policy_create_wide: the block has the layout of salp_policy_wide.h and runs its kernels
   mutable hipStream_t last_stream;   // the stream of the most recent create / update / noise-step write, and of whatever else the ABI file records
 };
 
 // The descriptor's ranges for a handle of these dimensions (salp_policy.h).  On success *words (nullable) = public words
 // of one policy.  A NULL handle (n == 0) and a NULL descriptor get one refusal, one text.
-int check_policy_dims(const PolicyDims& dims, const salp_policy_desc_t* d, bool gaussian, int* words) {
+int check_policy_dims(const PolicyDims& dims, const salp_policy_desc_t* d, bool gaussian, int* words, bool wide = false) {
   const char* why = "";
-  const int rc = salp::check_policy_desc(dims.obs_dim, dims.act_dim, dims.kmax, dims.n, dims.n ? d : nullptr, gaussian, words, &why);
+  const int rc = wide ? salp::check_policy_desc_wide(dims.obs_dim, dims.act_dim, dims.kmax, dims.food_slots, dims.n, dims.n ? d : nullptr, gaussian, words, &why)
+                      : salp::check_policy_desc(dims.obs_dim, dims.act_dim, dims.kmax, dims.n, dims.n ? d : nullptr, gaussian, words, &why);
   return rc == SALP_OK ? rc : fail(rc, why);
 }
 
 // *_policy_words and *_policy_words_gaussian
-int policy_words(const PolicyDims& dims, const salp_policy_desc_t* d, bool gaussian) {
+int policy_words(const PolicyDims& dims, const salp_policy_desc_t* d, bool gaussian, bool wide = false) {
   int words = 0;
-  const int rc = check_policy_dims(dims, d, gaussian, &words);
+  const int rc = check_policy_dims(dims, d, gaussian, &words, wide);
   return rc != SALP_OK ? rc : words;
 }
 
@@ -81,14 +85,15 @@ int policy_update(const PolicyObject& pol, const float* weights, bool device_ptr
 
 // *_policy_create and *_policy_create_gaussian: checks in the order out, descriptor, weights, flags (`known_flags`: a bit
 // outside is refused; bit 0 says device pointers), then the block map, the three allocations, map and header, the first
-// upload.  On success **out is zero but for the shared fields: the caller sets its back-pointer.
+// upload.  On success **out is zero but for the shared fields: the caller sets its back-pointer.  `wide`: the ranges, the
+// block map and the header of salp_policy_wide.h instead.
 template <class Policy>
 int policy_create(const PolicyDims& dims, const salp_policy_desc_t* desc, const float* weights, uint32_t flags, uint32_t known_flags,
-                  void* stream, bool gaussian, Policy** out) {
+                  void* stream, bool gaussian, Policy** out, bool wide = false) {
   if (!out) return fail(SALP_ERR_INVALID, "out is NULL");
   *out = nullptr;
   int words = 0;
-  int rc = check_policy_dims(dims, desc, gaussian, &words);
+  int rc = check_policy_dims(dims, desc, gaussian, &words, wide);
   if (rc != SALP_OK) return rc;
   if (!weights) return fail(SALP_ERR_INVALID, "weights is NULL");
   if (flags & ~known_flags) return fail(SALP_ERR_INVALID, "unknown flag bits");
@@ -97,9 +102,10 @@ int policy_create(const PolicyDims& dims, const salp_policy_desc_t* desc, const 
   Policy* pol = new (std::nothrow) Policy();     // value-initialised: every field zero
   if (!pol) return fail(SALP_ERR_OOM, "host allocation failed");
   pol->d = *desc; pol->device = dims.device; pol->obs_dim = dims.obs_dim; pol->act_dim = dims.act_dim; pol->n = dims.n;
-  pol->words = words; pol->gaussian = gaussian ? 1 : 0;
+  pol->words = words; pol->gaussian = gaussian ? 1 : 0; pol->wide = wide ? 1 : 0;
   std::vector<int32_t> map;     // word k of a policy in the device block <- public word map[k]: salp_policy.h
-  pol->stride = salp::policy_block_map(dims.obs_dim, dims.act_dim, *desc, gaussian, map);
+  pol->stride = wide ? salp::policy_block_map_wide(dims.act_dim, *desc, gaussian, map)
+                     : salp::policy_block_map(dims.obs_dim, dims.act_dim, *desc, gaussian, map);
   const salp::PolicyBytes bytes = salp::policy_bytes(*desc, words, pol->stride);
   hipError_t e = hipMalloc((void**)&pol->block, bytes.block);
   if (e == hipSuccess) e = hipMalloc((void**)&pol->pub, bytes.pub);
@@ -107,7 +113,8 @@ int policy_create(const PolicyDims& dims, const salp_policy_desc_t* desc, const 
   if (e == hipSuccess) e = hipMemcpy(pol->map, map.data(), bytes.map, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     int32_t hd[salp::PH_WORDS];
-    salp::policy_header(*desc, pol->stride, dims.n, gaussian, hd);
+    if (wide) salp::policy_header_wide(*desc, pol->stride, dims.n, gaussian, hd);
+    else salp::policy_header(*desc, pol->stride, dims.n, gaussian, hd);
     e = hipMemcpy(pol->block, hd, sizeof(hd), hipMemcpyHostToDevice);
   }
   if (e != hipSuccess)

@@ -13,7 +13,8 @@
 //     workgroup; the event statistics (episodes, terminations, food, ...) are counted in LDS on the rare steps that change
 //     them and leave as one atomic instruction per wavefront and event step; both go to one of 64 line-sized replicas
 //     (order-independent).
-// No MFMA: there is no dense contraction on this path; the bound is HBM write bandwidth.
+// MFMA in one place: the wide in-kernel policy (ACT_POLICY_WIDE*, salp_policy_wide.h), the path's one dense contraction,
+// in the one-food kernels; everything else has none and its bound is HBM write bandwidth.
 //
 // Two headers: salp_rollout_traits.h — the launch arguments (IOPtrs, ColdBlock, the named meanings of IOPtrs' overloaded
 // slots) and RolloutTraits, every compile-time switch and size of an instantiation with the reason for each and its LDS bytes
@@ -23,8 +24,8 @@
 // them their register counts; profiles/r10/refactor_notes.md lists what was tried.  Its sections are marked `// ----`.
 //
 // The template is instantiated implicitly, by the small salp_rollout_*.hip units next to this file: one per food-slot count
-// and literal / run-time constants for K = 3, one for the generic-K kernels, so that the 440 instantiations compile in
-// parallel.  Each unit defines the rollout_unit_fn of its handle class (the generic unit: of its two); salp_vec.hip (the
+// and literal / run-time constants for K = 3, one for the generic-K kernels, so that the 492 instantiations (52 of them the wide
+// policy's, in the two one-food units) compile in parallel.  Each unit defines the rollout_unit_fn of its handle class (the generic unit: of its two); salp_vec.hip (the
 // service kernels and the C ABI of include/salp_vec.h) reaches the kernels only through those.  No instantiation may be
 // named in two units.
 #pragma once
@@ -39,6 +40,7 @@
 #include "salp_rollout_traits.h"
 #include "salp_food_lds.h"
 #include "salp_policy.h"
+#include "salp_policy_wide.h"
 
 // What a choice of kernel returns: the kernel (its host-side address, a rollout_fn) and the output signature it was
 // compiled for — which is not always the one asked for (pick_sig): salp_vec_last_launch / _signatures report this value.
@@ -361,7 +363,13 @@ __global__ __launch_bounds__(kBlock, (RolloutTraits<FMAX, KMAX, FORCED, STD, SIG
         float zv[AD];
         zv[0] = policy_normal(nw.x, nw.y);
         if constexpr (!FORCED) zv[1] = policy_normal(nw.z, nw.w);
+        if constexpr (T::WIDE) policy_eval_wide<AD, true>(io.act, pol_off, ob0, zv, av, lp);
+        else
         policy_eval_sampled<T::OBS, AD>(io.act, pol_off, ob0, zv, av, lp);
+      } else if constexpr (T::WIDE) {
+        const float zv[AD] = {};
+        float unused = 0.f;
+        policy_eval_wide<AD, false>(io.act, pol_off, ob0, zv, av, unused);
       } else
       policy_eval<T::OBS, AD>(io.act, pol_off, ob0, av);
       take_actions(av, a0, a1);
@@ -725,7 +733,13 @@ __global__ __launch_bounds__(kBlock, (RolloutTraits<FMAX, KMAX, FORCED, STD, SIG
             float zv[AD];
             zv[0] = policy_normal(nw.x, nw.y);
             if constexpr (!FORCED) zv[1] = policy_normal(nw.z, nw.w);
+            if constexpr (T::WIDE) policy_eval_wide<AD, true>(io.act, pol_off, ob, zv, av, lp);
+            else
             policy_eval_sampled<T::OBS, AD>(io.act, pol_off, ob, zv, av, lp);
+          } else if constexpr (T::WIDE) {
+            const float zv[AD] = {};
+            float unused = 0.f;
+            policy_eval_wide<AD, false>(io.act, pol_off, ob, zv, av, unused);
           } else
           policy_eval<T::OBS, AD>(io.act, pol_off, ob, av);
           take_actions(av, a0, a1);
@@ -830,9 +844,9 @@ RolloutPick picked() {
 }
 template <int FMAX, int KMAX, bool FORCED, bool STD, bool RAGGED, int ACT>
 RolloutPick pick_sig(int sig) {
-  if constexpr (ACT == ACT_POLICY || ACT == ACT_POLICY_SAMPLED) {
+  if constexpr (ACT == ACT_POLICY || ACT == ACT_POLICY_SAMPLED || ACT == ACT_POLICY_WIDE || ACT == ACT_POLICY_WIDE_SAMPLED) {
     if (sig == kSigNav) {
-      if constexpr (ACT == ACT_POLICY && FMAX == 1 && KMAX == 3 && FORCED) return picked<FMAX, KMAX, FORCED, STD, kSigNav, RAGGED, ACT>();
+      if constexpr ((ACT == ACT_POLICY || ACT == ACT_POLICY_WIDE) && FMAX == 1 && KMAX == 3 && FORCED) return picked<FMAX, KMAX, FORCED, STD, kSigNav, RAGGED, ACT>();
       else return RolloutPick{nullptr, -1};
     }
     if (sig == kSigSummary) return picked<FMAX, KMAX, FORCED, STD, kSigSummary, RAGGED, ACT>();
@@ -850,6 +864,15 @@ RolloutPick pick_sig(int sig) {
 // `act`: where the actions come from (ACT_READ / ACT_GEN / ACT_POLICY / ACT_POLICY_SAMPLED)
 template <int FMAX, int KMAX, bool STD, bool RAGGED>
 RolloutPick pick_rollout(bool forced, int sig, int act) {
+  if (act == ACT_POLICY_WIDE || act == ACT_POLICY_WIDE_SAMPLED) {     // the wide evaluation (salp_policy_wide.h): one food, K = 3, the same signatures
+    if constexpr (FMAX == 1 && KMAX == 3) {
+      if ((sig == kSigMain || sig == kSigSummary || sig == kSigPacked) && act == ACT_POLICY_WIDE_SAMPLED)
+        return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, ACT_POLICY_WIDE_SAMPLED>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, ACT_POLICY_WIDE_SAMPLED>(sig);
+      if ((sig == kSigMain || sig == kSigSummary || sig == kSigNav || sig == kSigPacked) && act == ACT_POLICY_WIDE)
+        return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, ACT_POLICY_WIDE>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, ACT_POLICY_WIDE>(sig);
+    }
+    return RolloutPick{nullptr, -1};
+  }
   if ((sig == kSigMain || sig == kSigSummary || sig == kSigPacked) && act == ACT_POLICY_SAMPLED)   // the same signatures but the navigation, sampling
     return forced ? pick_sig<FMAX, KMAX, true, STD, RAGGED, ACT_POLICY_SAMPLED>(sig) : pick_sig<FMAX, KMAX, false, STD, RAGGED, ACT_POLICY_SAMPLED>(sig);
   if ((sig == kSigMain || sig == kSigSummary || sig == kSigNav || sig == kSigPacked) && act == ACT_POLICY)   // the in-kernel policy exists for the main-only output signature, the packed record, the summary and the navigation record

@@ -29,7 +29,9 @@ constexpr int kWave = 64;
 // ACT = ACT_POLICY_SAMPLED: the same closed loop with the stochastic form of a Gaussian policy (salp_vec_rollout_policy_sampled,
 // salp_vec_evaluate_policy_sampled): the action of step t is sampled with the policy's noise block n0 + t of the env, n0 =
 // the policy's noise step read from its device block at entry; its log-probability goes to logp_out with the action.
-enum { ACT_READ = 0, ACT_GEN = 1, ACT_POLICY = 2, ACT_POLICY_SAMPLED = 3 };
+// ACT = ACT_POLICY_WIDE / ACT_POLICY_WIDE_SAMPLED: the same two closed loops with the policy evaluated on the matrix cores
+// (salp_policy_wide.h: hidden widths up to 256); one-food kernels only, one wavefront per SIMD.
+enum { ACT_READ = 0, ACT_GEN = 1, ACT_POLICY = 2, ACT_POLICY_SAMPLED = 3, ACT_POLICY_WIDE = 4, ACT_POLICY_WIDE_SAMPLED = 5 };
 
 // Output signatures (template parameter SIG): kSigMain = obs, reward, terminated, truncated and nothing else — every
 // store of the step loop is unconditional, so the compiler can count the stores issued after the action prefetch and wait
@@ -113,8 +115,10 @@ struct RolloutTraits {
   static constexpr int FMAX = FMAX_, KMAX = KMAX_, SIG = SIG_, ACT = ACT_;
   static constexpr bool FORCED = FORCED_, STD = STD_, RAGGED = RAGGED_;
   static constexpr bool GEN = ACT == ACT_GEN;
-  static constexpr bool SAMPLED = ACT == ACT_POLICY_SAMPLED;
-  static constexpr bool POLICY = ACT == ACT_POLICY || SAMPLED;
+  static constexpr bool WIDE = ACT == ACT_POLICY_WIDE || ACT == ACT_POLICY_WIDE_SAMPLED;     // the evaluation of salp_policy_wide.h
+  static constexpr bool SAMPLED = ACT == ACT_POLICY_SAMPLED || ACT == ACT_POLICY_WIDE_SAMPLED;
+  static constexpr bool POLICY = ACT == ACT_POLICY || SAMPLED || WIDE;
+  static_assert(!WIDE || (FMAX_ == 1 && KMAX_ == 3), "the wide policy evaluation exists in the one-food kernels only");
   // SIG 4 (kSigSummary): NO per-step output at all — salp_vec_evaluate_policy.  record_block(io) is the block of per-env summary
   // records ([n][SALP_EVAL_WORDS] words, include/salp_vec.h), accumulate(io) says that the records are read first and continued
   // (SALP_EVAL_ACCUMULATE).  The observation is formed in registers for the policy alone: no tile write, no flush, no
@@ -128,7 +132,7 @@ struct RolloutTraits {
   static constexpr bool SUMMARY = SIG == kSigSummary || NAV;     // everything the two share: no per-step output, no tile write
   static_assert(!POLICY || ((SIG == 1 || SIG == 3 || SIG == 4 || SIG == 5) && KMAX == 3), "policy kernels: the main-only, the packed, the summary and the navigation signature, K = 3");
   static_assert(!SUMMARY || POLICY, "the summary signature exists for the in-kernel policy only");
-  static_assert(!NAV || (FMAX == 1 && FORCED && ACT == ACT_POLICY), "the navigation signature: one food, forced breathing, the deterministic policy");
+  static_assert(!NAV || (FMAX == 1 && FORCED && (ACT == ACT_POLICY || ACT == ACT_POLICY_WIDE)), "the navigation signature: one food, forced breathing, the deterministic policy");
   // (the summary kernels the other way round — by value with 4 / 8 slots, the device copy with 16: with no store in the step loop
   // the twins' choice left 300-560 scalar registers spilled and 68-196 B of scratch reserved in four of them; so chosen, none
   // of the 40 holds scratch where its twin holds none, profiles/r06/eval_kernel_resources.txt)
@@ -213,6 +217,9 @@ struct RolloutTraits {
     // constants: 1.  From the code-object metadata of all 80: profiles/r07/sampled_kernel_resources.txt.
     // The packed policy kernels (sig 3, salp_vec_rollout_policy_packed) take the bounds of their main-only twins (sig 1), sampling
     // or not: the record's last float4 waits in LDS, not in registers (profiles/r16/policy_packed_kernel_resources.txt).
+    // The wide policy kernels: 1 — the stored hidden layer of one env half is up to 128 registers on top of the step's own, the
+    // accumulators of two tiles 32 more; the wavefront owns the SIMD's 512 registers (profiles/r05/policy_wide_kernel_resources.txt).
+    if (WIDE) return 1;
     if (SAMPLED && !RAGGED && FMAX == 4 && (SIG == 1 || SIG == 3 || !FORCED)) return 1;
     // Two more packed kernels go to 1, by the same rule (scratch at 2 where the twin holds less): the unpredicated one-food
     // sampling kernel with run-time constants (12 B, its twin none) and the unpredicated free-breathing 4-slot kernel (20 B, its twin 12).

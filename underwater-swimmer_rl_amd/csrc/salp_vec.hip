@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/salp_vec_policy_packed.h"
+#include "../../include/salp_vec_policy_wide.h"
 #include "salp_host.h"
 #include "salp_policy_object.h"
 #include "salp_rollout_kernel.h"
@@ -43,6 +44,7 @@ struct salp_vec {
   int64_t last_launch[8];    // salp_vec_last_launch
   int64_t last_sigs[2];      // salp_vec_last_launch_signatures
   const void* last_kernel;   // the main (else the predicated) kernel of the most recent launch: salp_vec_last_kernel_resources
+  int last_wide;             // salp_vec_last_launch_policy_wide: the most recent launch ran the kernels of salp_policy_wide.h
 };
 
 struct salp_policy : PolicyObject {     // salp_policy_object.h; last_stream: create / update / noise-step writes, sampled calls included
@@ -59,7 +61,7 @@ int validate(const salp_config_t* c) {
 }
 
 // What a policy of this handle is checked against and made for (salp_policy_object.h); a NULL handle: zeros.
-PolicyDims policy_dims(const salp_vec* h) { return h ? PolicyDims{h->obs_dim, h->act_dim, h->kmax, h->n, h->device} : PolicyDims{}; }
+PolicyDims policy_dims(const salp_vec* h) { return h ? PolicyDims{h->obs_dim, h->act_dim, h->kmax, h->n, h->device, h->fmax} : PolicyDims{}; }
 
 typedef void (*reset_fn)(DevParams, DevState, const uint8_t*, float*, int);
 
@@ -117,7 +119,8 @@ int (*g_read_counters)(unsigned long long*) = exp_read_counters;
 //        the track.  (set_record_block / set_policy_block and the readers: salp_rollout_traits.h, next to IOPtrs.)
 //   act: ACT_READ — io.act, or generated in the kernel when that is NULL (only reached when can_generate_in_kernel());
 //        ACT_POLICY / ACT_POLICY_SAMPLED — io.act is a policy's device block (set_policy_block) (the caller has checked K = 3 and the
-//        four main outputs; ACT_POLICY_SAMPLED: a Gaussian policy, io.logp_out may be set)
+//        four main outputs; ACT_POLICY_SAMPLED: a Gaussian policy, io.logp_out may be set);  ACT_POLICY_WIDE / _WIDE_SAMPLED — the same
+//        two with a block of salp_policy_wide.h (policy_act(): the caller has a policy that passed the wide create)
 enum { kOutStreams = 0, kOutPacked = 1, kOutSummary = 2, kOutNav = 3 };
 struct RolloutKind { int out, act; };
 
@@ -148,7 +151,9 @@ int launch_rollout(salp_vec* h, const IOPtrs& io, int H, hipStream_t st, Rollout
   h->last_sigs[0] = full.sig;
   h->last_sigs[1] = ragged.sig;
   h->last_launch[0] = h->fmax; h->last_launch[1] = h->kmax; h->last_launch[2] = (h->kmax == 3) ? h->std_consts : 0;
-  h->last_launch[3] = h->P.forced; h->last_launch[4] = first.sig; h->last_launch[5] = gen;
+  h->last_wide = (gen == ACT_POLICY_WIDE || gen == ACT_POLICY_WIDE_SAMPLED) ? 1 : 0;
+  // [5] keeps its two policy values: 2 deterministic, 3 sampled, whichever scheme evaluates (salp_vec_last_launch_policy_wide tells)
+  h->last_launch[3] = h->P.forced; h->last_launch[4] = first.sig; h->last_launch[5] = h->last_wide ? gen - (ACT_POLICY_WIDE - ACT_POLICY) : gen;
   h->last_launch[6] = n_full; h->last_launch[7] = h->n - n_full;
   h->last_kernel = first.fn;     // the main (else the predicated) kernel
 #ifdef SALP_EXP_STAMPS
@@ -395,7 +400,7 @@ static int run_rollout(salp_vec_t* h, const IOPtrs& io, int32_t H, hipStream_t s
   const int rc = launch_rollout(h, io, H, st, kind);
   if (rc != SALP_OK) return rc;
   h->global_step += H;
-  return kind.act == ACT_POLICY_SAMPLED ? advance_noise(pol, H, st) : SALP_OK;
+  return (kind.act == ACT_POLICY_SAMPLED || kind.act == ACT_POLICY_WIDE_SAMPLED) ? advance_noise(pol, H, st) : SALP_OK;
 }
 
 static int rollout_impl(salp_vec_t* h, const float* act, int32_t H, float* obs, float* reward,
@@ -496,9 +501,9 @@ int salp_policy_words(const salp_vec_t* h, const salp_policy_desc_t* desc) { ret
 int salp_policy_words_gaussian(const salp_vec_t* h, const salp_policy_desc_t* desc) { return policy_words(policy_dims(h), desc, true); }
 
 static int policy_create_impl(salp_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags, void* stream,
-                              salp_policy_t** out, bool gaussian) {
+                              salp_policy_t** out, bool gaussian, bool wide = false) {
   // of `flags`, create and update read bit 0 (SALP_DEVICE_PTRS) and ignore the rest: every bit is a known one
-  const int rc = policy_create(policy_dims(h), desc, weights, flags, ~0u, stream, gaussian, out);
+  const int rc = policy_create(policy_dims(h), desc, weights, flags, ~0u, stream, gaussian, out, wide);
   if (rc == SALP_OK) (*out)->h = h;
   return rc;
 }
@@ -512,6 +517,23 @@ int salp_policy_create_gaussian(salp_vec_t* h, const salp_policy_desc_t* desc, c
                                 salp_policy_t** out) {
   return policy_create_impl(h, desc, weights, flags, stream, out, true);
 }
+
+// include/salp_vec_policy_wide.h: the same object with the ranges and the block of salp_policy_wide.h
+int salp_policy_words_wide(const salp_vec_t* h, const salp_policy_desc_t* desc, int gaussian) {
+  return policy_words(policy_dims(h), desc, gaussian != 0, true);
+}
+
+int salp_policy_create_wide(salp_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags, void* stream,
+                            salp_policy_t** out) {
+  return policy_create_impl(h, desc, weights, flags, stream, out, false, true);
+}
+
+int salp_policy_create_gaussian_wide(salp_vec_t* h, const salp_policy_desc_t* desc, const float* weights, uint32_t flags, void* stream,
+                                     salp_policy_t** out) {
+  return policy_create_impl(h, desc, weights, flags, stream, out, true, true);
+}
+
+int salp_vec_last_launch_policy_wide(const salp_vec_t* h) { return h ? h->last_wide : 0; }
 
 void salp_policy_destroy(salp_policy_t* pol) {
   if (pol) policy_free(pol, &pol->h->last_stream);     // its own uploads, and the handle's launches that read the block
@@ -540,7 +562,11 @@ static int check_policy_call(const salp_vec_t* h, const salp_policy_t* pol, bool
   if (sampled && !pol->gaussian) return fail(SALP_ERR_INVALID, "sampling needs a Gaussian policy (salp_policy_create_gaussian)");
   if (pol->h != h || pol->device != h->device || pol->obs_dim != h->obs_dim || pol->act_dim != h->act_dim || pol->n != h->n)
     return fail(SALP_ERR_INVALID, "the policy belongs to another handle (or other dimensions)");
-  return check_policy_dims(policy_dims(h), &pol->d, pol->gaussian != 0, nullptr);
+  return check_policy_dims(policy_dims(h), &pol->d, pol->gaussian != 0, nullptr, pol->wide != 0);
+}
+// The action source of a policy call: the policy's scheme (salp_policy.h or salp_policy_wide.h), deterministic or sampling.
+static int policy_act(const salp_policy_t* pol, bool sampled) {
+  return pol->wide ? (sampled ? ACT_POLICY_WIDE_SAMPLED : ACT_POLICY_WIDE) : (sampled ? ACT_POLICY_SAMPLED : ACT_POLICY);
 }
 
 // salp_vec_rollout_policy (sampled = false, logp_out = NULL) and salp_vec_rollout_policy_sampled
@@ -562,7 +588,7 @@ static int rollout_policy_impl(salp_vec_t* h, const salp_policy_t* pol, int32_t 
     io.obs = s[0].as<float>(); io.reward = s[1].as<float>(); io.terminated = s[2].as<uint8_t>(); io.truncated = s[3].as<uint8_t>();
     io.act_out = s[4].as<float>();
     if (sampled) io.logp_out = s[5].as<float>();
-    return run_rollout(h, io, H, f.st, {kOutStreams, sampled ? ACT_POLICY_SAMPLED : ACT_POLICY}, pol);
+    return run_rollout(h, io, H, f.st, {kOutStreams, policy_act(pol, sampled)}, pol);
   });
 }
 
@@ -601,7 +627,7 @@ static int rollout_policy_packed_impl(salp_vec_t* h, const salp_policy_t* pol, i
     set_record_block(io, s[0].as<float>(), with_final);
     io.act_out = s[1].as<float>();
     if (sampled) io.logp_out = s[2].as<float>();     // (the info slot: the record carries the counters)
-    return run_rollout(h, io, H, f.st, {kOutPacked, sampled ? ACT_POLICY_SAMPLED : ACT_POLICY}, pol);
+    return run_rollout(h, io, H, f.st, {kOutPacked, policy_act(pol, sampled)}, pol);
   });
 }
 
@@ -632,7 +658,7 @@ static int evaluate_policy_impl(salp_vec_t* h, const salp_policy_t* pol, int32_t
   HostStream s[] = {stream_out((int32_t*)rec, (size_t)h->n * SALP_EVAL_WORDS, accumulate)};
   return staged(h->stage, f.st, flags & SALP_DEVICE_PTRS, s, [&] {
     set_record_block(io, s[0].as<float>(), accumulate);
-    return run_rollout(h, io, H, f.st, {kOutSummary, sampled ? ACT_POLICY_SAMPLED : ACT_POLICY}, pol);
+    return run_rollout(h, io, H, f.st, {kOutSummary, policy_act(pol, sampled)}, pol);
   });
 }
 
@@ -670,7 +696,7 @@ int salp_vec_evaluate_navigation(salp_vec_t* h, const salp_policy_t* pol, int32_
                     stream_out(track, (size_t)H * (size_t)h->n * 2)};
   return staged(h->stage, f.st, flags & SALP_DEVICE_PTRS, s, [&] {
     io.nav_line = s[0].as<const double>(); set_record_block(io, s[1].as<float>(), accumulate); io.nav_track = s[2].as<double>();
-    return run_rollout(h, io, H, f.st, {kOutNav, ACT_POLICY}, pol);
+    return run_rollout(h, io, H, f.st, {kOutNav, policy_act(pol, false)}, pol);
   });
 }
 

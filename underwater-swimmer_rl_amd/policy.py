@@ -13,6 +13,10 @@ evaluation in the library's fixed order may be from it.
 `tanh(mu + exp(log_std) z) * scale + shift`, from the policy's own Philox stream (`noise`) and returns its log-probability
 (include/salp_vec.h "Sampled actions"); `reference(obs, z)` / `error_bound(obs, z)` state and bound that computation, and
 `sampling_stage(mu, ls_raw, z)` the part of it behind the two heads alone.
+
+`wide=True` (constructors, `from_layers`, `from_actor`, `stack`) asks for the WIDE evaluation scheme of
+include/salp_vec_policy_wide.h: 1 or 2 hidden layers of multiples of 32 up to 256 units, evaluated on the matrix cores of
+the one-food kernels.  The arithmetic and its order are the same, so `reference` and `error_bound` are too.
 """
 from __future__ import annotations
 
@@ -24,6 +28,7 @@ import numpy as np
 OUT_TANH, OUT_CLIP = 0, 1
 _OUT = {"tanh": OUT_TANH, "clip": OUT_CLIP}
 MAX_HIDDEN_LAYERS, HIDDEN_STEP, HIDDEN_MAX = 2, 16, 64
+WIDE_HIDDEN_STEP, WIDE_HIDDEN_MAX = 32, 256       # the wide scheme (include/salp_vec_policy_wide.h)
 U = 2.0 ** -24          # unit roundoff of float32
 
 
@@ -41,7 +46,9 @@ class MLPPolicy:
     """P >= 1 policies of one shape.  `layers`: [(W [P, out, in], b [P, out]), ...] float32, the last one the output
     layer; `scale`, `shift`: [P, act_dim] float32."""
 
-    def __init__(self, layers: Sequence[Tuple[np.ndarray, np.ndarray]], scale: np.ndarray, shift: np.ndarray, out: str = "tanh"):
+    def __init__(self, layers: Sequence[Tuple[np.ndarray, np.ndarray]], scale: np.ndarray, shift: np.ndarray, out: str = "tanh",
+                 wide: bool = False):
+        self.wide = bool(wide)
         if out not in _OUT:
             raise ValueError("out must be 'tanh' or 'clip'")
         if not 1 <= len(layers) <= MAX_HIDDEN_LAYERS + 1:
@@ -63,9 +70,12 @@ class MLPPolicy:
                 raise ValueError(f"layer input width {W.shape[2]} does not follow the previous layer's {d} outputs")
             d = W.shape[1]
             self.layers.append((W, b))
+        if self.wide and not self.hidden:
+            raise ValueError("a wide policy has 1 or 2 hidden layers")
+        step, top = (WIDE_HIDDEN_STEP, WIDE_HIDDEN_MAX) if self.wide else (HIDDEN_STEP, HIDDEN_MAX)
         for h in self.hidden:
-            if h % HIDDEN_STEP or not HIDDEN_STEP <= h <= HIDDEN_MAX:
-                raise ValueError(f"hidden width {h}: must be a multiple of {HIDDEN_STEP} in [{HIDDEN_STEP}, {HIDDEN_MAX}]")
+            if h % step or not step <= h <= top:
+                raise ValueError(f"hidden width {h}: must be a multiple of {step} in [{step}, {top}]")
         self.n_policies = int(P)
         self.obs_dim = int(self.layers[0][0].shape[2])
         self.act_dim = int(self.layers[-1][0].shape[1])
@@ -74,21 +84,22 @@ class MLPPolicy:
 
     # ------------------------------------------------------------------ constructors
     @classmethod
-    def from_layers(cls, layers, scale=None, shift=None, out: str = "tanh") -> "MLPPolicy":
+    def from_layers(cls, layers, scale=None, shift=None, out: str = "tanh", wide: bool = False) -> "MLPPolicy":
         """One policy from [(W [out, in], b [out]), ...]; scale / shift default to 1 / 0."""
         ls = [(np.asarray(W, dtype=np.float32)[None], np.asarray(b, dtype=np.float32)[None]) for W, b in layers]
         A = ls[-1][0].shape[1]
         sc = np.ones(A, np.float32) if scale is None else np.asarray(scale, dtype=np.float32)
         sh = np.zeros(A, np.float32) if shift is None else np.asarray(shift, dtype=np.float32)
-        return cls(ls, sc[None], sh[None], out)
+        return cls(ls, sc[None], sh[None], out, wide)
 
     @classmethod
-    def from_actor(cls, actor) -> "MLPPolicy":
-        """The deterministic action of a `sac.Actor` (its mean head, tanh, rescale) whose hidden sizes fit."""
+    def from_actor(cls, actor, wide: bool = False) -> "MLPPolicy":
+        """The deterministic action of a `sac.Actor` (its mean head, tanh, rescale) whose hidden sizes fit (`wide`: the wide
+        scheme's sizes — the default 256 x 256 actor among them)."""
         import torch.nn as nn
         lin = [m for m in actor.body if isinstance(m, nn.Linear)] + [actor.mu]
         layers = [(m.weight.detach().cpu().numpy(), m.bias.detach().cpu().numpy()) for m in lin]
-        return cls.from_layers(layers, actor.scale.detach().cpu().numpy(), actor.shift.detach().cpu().numpy(), "tanh")
+        return cls.from_layers(layers, actor.scale.detach().cpu().numpy(), actor.shift.detach().cpu().numpy(), "tanh", wide)
 
     @classmethod
     def linear(cls, W, b=None, out: str = "clip", scale=None, shift=None) -> "MLPPolicy":
@@ -98,15 +109,16 @@ class MLPPolicy:
         return cls.from_layers([(W, b)], scale, shift, out)
 
     @classmethod
-    def stack(cls, policies: Sequence["MLPPolicy"]) -> "MLPPolicy":
-        """A population: the policies of the list (each possibly a population itself), in order."""
+    def stack(cls, policies: Sequence["MLPPolicy"], wide: Optional[bool] = None) -> "MLPPolicy":
+        """A population: the policies of the list (each possibly a population itself), in order.  `wide` None: the first one's."""
         p0 = policies[0]
         for p in policies:
             if (p.hidden, p.obs_dim, p.act_dim, p.out) != (p0.hidden, p0.obs_dim, p0.act_dim, p0.out):
                 raise ValueError("stack: every policy must have the same shape and output activation")
         layers = [(np.concatenate([p.layers[l][0] for p in policies]), np.concatenate([p.layers[l][1] for p in policies]))
                   for l in range(len(p0.layers))]
-        return cls(layers, np.concatenate([p.scale for p in policies]), np.concatenate([p.shift for p in policies]), p0.out)
+        return cls(layers, np.concatenate([p.scale for p in policies]), np.concatenate([p.shift for p in policies]), p0.out,
+                   p0.wide if wide is None else wide)
 
     # ------------------------------------------------------------------ shape
     @property
@@ -266,8 +278,8 @@ class GaussianPolicy(MLPPolicy):
     on the same last hidden layer."""
     gaussian = True
 
-    def __init__(self, layers, log_std, scale, shift):
-        super().__init__(layers, scale, shift, "tanh")
+    def __init__(self, layers, log_std, scale, shift, wide: bool = False):
+        super().__init__(layers, scale, shift, "tanh", wide)
         W, b = log_std
         W = np.ascontiguousarray(W, dtype=np.float32)
         b = np.ascontiguousarray(b, dtype=np.float32)
@@ -277,32 +289,32 @@ class GaussianPolicy(MLPPolicy):
 
     # ------------------------------------------------------------------ constructors
     @classmethod
-    def from_layers(cls, layers, log_std, scale=None, shift=None) -> "GaussianPolicy":
+    def from_layers(cls, layers, log_std, scale=None, shift=None, wide: bool = False) -> "GaussianPolicy":
         """One policy from [(W [out, in], b [out]), ...] (the last one the mean head) and log_std = (W [A, in], b [A])."""
-        m = MLPPolicy.from_layers(layers, scale, shift, "tanh")
+        m = MLPPolicy.from_layers(layers, scale, shift, "tanh", wide)
         return cls(m.layers, (np.asarray(log_std[0], dtype=np.float32)[None], np.asarray(log_std[1], dtype=np.float32)[None]),
-                   m.scale, m.shift)
+                   m.scale, m.shift, wide)
 
     @classmethod
-    def from_actor(cls, actor) -> "GaussianPolicy":
+    def from_actor(cls, actor, wide: bool = False) -> "GaussianPolicy":
         """A `sac.Actor` whose hidden sizes fit: body, `mu`, `log_std`, scale, shift."""
-        m = MLPPolicy.from_actor(actor)
+        m = MLPPolicy.from_actor(actor, wide)
         ls = actor.log_std
-        return cls(m.layers, (ls.weight.detach().cpu().numpy()[None], ls.bias.detach().cpu().numpy()[None]), m.scale, m.shift)
+        return cls(m.layers, (ls.weight.detach().cpu().numpy()[None], ls.bias.detach().cpu().numpy()[None]), m.scale, m.shift, wide)
 
     @classmethod
     def linear(cls, *a, **k):
         raise TypeError("GaussianPolicy.from_layers builds a policy without hidden layers")
 
     @classmethod
-    def stack(cls, policies: Sequence["GaussianPolicy"]) -> "GaussianPolicy":
-        m = MLPPolicy.stack([p.mean_policy() for p in policies])
+    def stack(cls, policies: Sequence["GaussianPolicy"], wide: Optional[bool] = None) -> "GaussianPolicy":
+        m = MLPPolicy.stack([p.mean_policy() for p in policies], wide)
         return cls(m.layers, (np.concatenate([p.log_std[0] for p in policies]), np.concatenate([p.log_std[1] for p in policies])),
-                   m.scale, m.shift)
+                   m.scale, m.shift, m.wide)
 
     def mean_policy(self) -> MLPPolicy:
         """The `MLPPolicy` of the same body and mean head: what salp_vec_rollout_policy runs for this policy."""
-        return MLPPolicy(self.layers, self.scale, self.shift, "tanh")
+        return MLPPolicy(self.layers, self.scale, self.shift, "tanh", self.wide)
 
     # ------------------------------------------------------------------ shape
     @property

@@ -418,10 +418,12 @@ def train_sac(env, agent: SAC, total_vector_steps: int, buffer: Optional[DeviceR
 
 
 IN_KERNEL_HIDDEN_MAX = 64      # widest hidden layer of an actor that runs inside the rollout kernel (include/salp_vec.h "Policy")
+IN_KERNEL_WIDE_HIDDEN_MAX, IN_KERNEL_WIDE_STEP = 256, 32     # the wide scheme's (include/salp_vec_policy_wide.h): one-food snake envs
 
 
 @torch.no_grad()
-def collect_in_kernel(env, agent: SAC, buffer: DeviceReplayBuffer, horizon: int, handle=None, keep_truncated: bool = False):
+def collect_in_kernel(env, agent: SAC, buffer: DeviceReplayBuffer, horizon: int, handle=None, keep_truncated: bool = False,
+                      wide: bool = False):
     """`horizon` vector steps of experience in ONE launch: the agent's actor is packed as a `policy.GaussianPolicy`, the
     rollout kernel samples its tanh-Gaussian actions itself (`env.rollout_policy(..., sample=True)`), and the H x N
     transitions go to `buffer` in step order: `obs` = the row each action saw (the current observation, then obs[t - 1]),
@@ -432,13 +434,19 @@ def collect_in_kernel(env, agent: SAC, buffer: DeviceReplayBuffer, horizon: int,
     transitions are stored, as `train_sac` stores them.  `keep_truncated=True` does the same on a snake env: the launch is
     `env.rollout_policy_packed(..., sample=True, want_final_observation=True)`, whose records carry the terminal rows, and all
     H x N transitions are stored through `records.transitions` (on a robot env the flag changes nothing).  Returns the
-    policy handle: pass it back as `handle` and the next call only uploads the actor's new weights (`handle.update`)."""
+    policy handle: pass it back as `handle` and the next call only uploads the actor's new weights (`handle.update`).
+    `wide=True` (a one-food snake env): the actor runs under the wide scheme of include/salp_vec_policy_wide.h — 1 or 2 hidden
+    layers, multiples of 32 up to 256 units, the default (256, 256) among them."""
     from .policy import GaussianPolicy
-    wide = [h for h in agent.cfg.hidden_sizes if h > IN_KERNEL_HIDDEN_MAX]
-    if wide or len(agent.cfg.hidden_sizes) > 2:
+    sizes = tuple(agent.cfg.hidden_sizes)
+    if wide:
+        if not 1 <= len(sizes) <= 2 or any(h % IN_KERNEL_WIDE_STEP or not IN_KERNEL_WIDE_STEP <= h <= IN_KERNEL_WIDE_HIDDEN_MAX for h in sizes):
+            raise ValueError(f"collect_in_kernel(wide=True): the actor's hidden sizes {sizes} do not fit the wide policy kernels "
+                             f"(1 or 2 hidden layers, multiples of {IN_KERNEL_WIDE_STEP} up to {IN_KERNEL_WIDE_HIDDEN_MAX} units)")
+    elif [h for h in sizes if h > IN_KERNEL_HIDDEN_MAX] or len(sizes) > 2:
         raise ValueError(f"collect_in_kernel: the actor's hidden sizes {tuple(agent.cfg.hidden_sizes)} do not fit the rollout kernel "
                          f"(at most 2 hidden layers of at most {IN_KERNEL_HIDDEN_MAX} units, multiples of 16)")
-    pol = GaussianPolicy.from_actor(agent.actor)
+    pol = GaussianPolicy.from_actor(agent.actor, wide=wide)
     if handle is None:
         handle = env.make_policy(pol)
     else:
